@@ -1,6 +1,6 @@
 """bench.py's host logic: the synthetic R1CS it proves in `extras` is the oracle's synthetic circuit, and
 `python3 bench.py --gpus N` starts N ranks by itself (a driver-run SCALE record must never be a silent one-GPU
-number).  CPU tests; the two-rank rehearsal on a real GPU is gpu-marked."""
+number).  CPU tests; the runs on a real GPU are gpu-marked."""
 import json
 import os
 import subprocess
@@ -105,7 +105,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     both on GPU 0), weak and strong scaling lines."""
     env = dict(os.environ, PS_BENCH_DEVICE="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1"]
     res = subprocess.run(base + ["--log2n", "14"], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -128,7 +128,7 @@ def test_bench_many_ranks_rehearsal_verifies_every_share():
     env = dict(os.environ, PS_BENCH_DEVICE="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     for ranks in (4, 3):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--backend", "gloo", "--steps", "3", "--warmup", "1",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--backend", "gloo", "--steps", "3", "--warmup", "1",
                "--total-log2n", "20"]
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
@@ -144,9 +144,35 @@ def test_bench_side_configurations_print_their_line(flags):
     """The configurations tools/size_sweep.sh and the secondary numbers drive (`--group g2` once died on a missing PMC
     record after the G2 file name had been dropped from the table): one JSON line, roofline present, traffic null where no
     PMC pass exists."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"] + flags
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"] + flags
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["value"] > 0 and line["n_gpus"] == 1 and line["roofline"]["traffic"] is None
     assert line["unit"].startswith(flags[1].upper())
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps sums, prints the headline fields and none of the measurements that take
+    runs of their own, and --dump-outputs writes the sum of the last timed step: byte for byte (sum a_i k_i mod r) G over the
+    run's seeded inputs."""
+    import numpy as np
+
+    bench = _bench()
+    n, steps = 1 << 12, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "12", "--steps", str(steps), "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["unit"] == "G1 scalar-muls/s" and line["higher_is_better"] is True and line["dtype"] and line["metric"]
+    assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - n) < 1e-6 * n  # value = n sums' worth of muls per ms_per_step
+    assert not {"roofline", "stage_ms", "ms_per_step_one_at_a_time", "ms_per_step_with_h2d", "verified_dlog", "cpu_baseline",
+                "extras"} & set(line)
+    got = np.load(tmp_path / "out" / "result_affine.npy")
+    assert got.dtype == np.float64 and got.shape == (96,)
+    a = bench.uniform_scalars_be32(n, bench.SEED + 1000).tobytes()
+    k = bench.uniform_scalars_be32(n, bench.SEED + 2000).tobytes()
+    assert bytes(got.astype(np.uint8)) == bench.fixed_base_mul_bytes("g1", bench.dlog_of_sum(a, k))

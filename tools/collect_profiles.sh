@@ -6,10 +6,10 @@ set -e
 out=$1; tag=$2
 mkdir -p "$out"
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 echo "bench done"
-tools/prof_bench.sh "$out/${tag}_kernel_stats_bench_msm_2p20" --steps 20 --warmup 5 --no-extras --no-cpu-baseline
-tools/prof_bench.sh "$out/${tag}_kernel_stats_bench_msm_2p20_one_at_a_time" --steps 20 --warmup 5 --no-extras --no-cpu-baseline --in-flight 1
+tools/prof_bench.sh "$out/${tag}_kernel_stats_bench_msm_2p20" --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline
+tools/prof_bench.sh "$out/${tag}_kernel_stats_bench_msm_2p20_one_at_a_time" --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --in-flight 1
 echo "kernel stats of the bench done"
 for what in g16 phgr13; do
   d=$(mktemp -d /tmp/prof.XXXX)
@@ -20,7 +20,7 @@ done
 echo "kernel stats of the provers done"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   d=$(mktemp -d /tmp/pmc.XXXX)
-  rocprofv3 --pmc $ctr -d "$d" -o run -- python3 bench.py --no-cpu-baseline --no-extras --steps 4 --warmup 1 --in-flight 1 > /dev/null 2>&1
+  rocprofv3 --pmc $ctr -d "$d" -o run -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 4 --warmup 1 --in-flight 1 > /dev/null 2>&1
   cp "$(find "$d" -name '*.db' | head -1)" "/tmp/pmc_bench_$ctr.db"
   rm -rf "$d"
   d=$(mktemp -d /tmp/pmc.XXXX)
@@ -32,7 +32,7 @@ python3 tools/rocpd_pmc.py /tmp/pmc_bench_FETCH_SIZE.db /tmp/pmc_bench_WRITE_SIZ
 # the same two passes for the G2 accumulation (bench.py --group g2 carries their sum as roofline.traffic)
 for ctr in FETCH_SIZE WRITE_SIZE; do
   d=$(mktemp -d /tmp/pmc.XXXX)
-  rocprofv3 --pmc $ctr -d "$d" -o run -- python3 bench.py --group g2 --no-cpu-baseline --no-extras --steps 3 --warmup 1 --in-flight 1 > /dev/null 2>&1
+  rocprofv3 --pmc $ctr -d "$d" -o run -- python3 bench.py --full --group g2 --no-cpu-baseline --no-extras --steps 3 --warmup 1 --in-flight 1 > /dev/null 2>&1
   cp "$(find "$d" -name '*.db' | head -1)" "/tmp/pmc_g2_$ctr.db"
   rm -rf "$d"
 done
