@@ -48,8 +48,9 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  * "not present", and garbage in a member added by a later revision would be dereferenced.
  *   1  round 1;  2  Lagrange-form key arrays (lxi / lxi2 / lxi_t / lgsi), multi-device entries;
  *   3  ps_msm_info.window_table, ps_msm_set_tail, ps_ctx_set_table_budget, ps_qap_is_valid, ps_microbench_mad;
- *   4  ps_points_monomial_to_lagrange; index-range views build window tables of their own; PS_MSM_QUEUE 3 -> 4 (no struct changed) */
-#define PS_ABI_VERSION 4
+ *   4  ps_points_monomial_to_lagrange; index-range views build window tables of their own; PS_MSM_QUEUE 3 -> 4 (no struct changed);
+ *   5  ps_phgr13_prove_shard, ps_phgr13_prove_multi and its ps_phgr13_device (no existing struct changed) */
+#define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
 const char* ps_version(void);
@@ -293,9 +294,36 @@ typedef struct { /* PHGR13Proof (pinochio.go:180-203) */
 int ps_phgr13_prove(ps_ctx* ctx, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sol,
                     ps_phgr13_proof* out);
 
+/* One rank's share of PHGR13Prove when the sums are sharded over `world` GPUs (one process each), the twin of
+ * ps_groth16_prove_shard: every rank holds the WHOLE key and computes the quotient itself; rank g sums its index range of
+ * every array -- range(len(vs)) of the nine solution arrays (one digit sort), range(n-1) of gsi, or of lgsi when the key has
+ * it.  PHGR13 has no fixed points: `part` holds partial sums only (the identity for an empty range), and the element-wise
+ * ps_points_sum of all ranks' parts is the proof of ps_phgr13_prove, byte for byte.  The nine arrays must have one length
+ * (as ps_phgr13_setup / NewPHGR13TrustedSetup make them; PS_ERR_LENGTH otherwise). */
+int ps_phgr13_prove_shard(ps_ctx* ctx, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sol, int rank, int world,
+                          ps_phgr13_proof* part);
+
+/* PHGR13Prove over the devices of one process, every device holding only ITS index ranges of the evaluation key: device d
+ * of ndev holds vs .. ybs[range(nn)] (nn = len(vs) of the whole key) and gsi[range(n-1)], and lgsi[range(n-1)] if the key
+ * has the Lagrange form -- on every device or on none (PS_ERR_ARG); range = the d-th of ndev contiguous parts whose sizes
+ * differ by at most one (PS_ERR_LENGTH, naming the device, otherwise).  Each device has its own context (distinct), its own
+ * ps_qap of the circuit and its own copy of the solution; 1 <= ndev <= 64.  The quotient runs once, on dev[0]; every
+ * other device starts its solution sums at once and copies its range of h device to device when h exists.  Same proof
+ * bytes as ps_phgr13_prove.  ps_prove_last_phase_ms on each context gives that device's share. */
+typedef struct {
+    ps_ctx* ctx;
+    const ps_qap* qap;
+    const ps_scalars* sol;
+    ps_phgr13_ek ek; /* rank-local arrays */
+} ps_phgr13_device;
+int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, ps_phgr13_proof* out);
+
 /* Host wall-clock split of the last ps_groth16_prove / ps_phgr13_prove on this context, in ms:
  * [0] quotient h(x) (SpMV, gate check, interpolations, division), [1] scalar preparation (Groth16) or
- * the h(s) sum (PHGR13), [2] the remaining sums incl. host folds, [3] total.  For reports only. */
+ * the h(s) sum (PHGR13), [2] the remaining sums incl. host folds, [3] total.  For reports only.
+ * ps_phgr13_prove_shard / ps_phgr13_prove_multi set it for the context's own share: [0] computing h -- or, on a device of
+ * ps_phgr13_prove_multi other than dev[0], waiting for h including the copy of its range --, [1] the h(s) sum, [2] the
+ * solution sums (what is left of them after [1]), [3] total. */
 #define PS_PROVE_PHASES 4
 int ps_prove_last_phase_ms(ps_ctx* ctx, float ms[PS_PROVE_PHASES]);
 

@@ -29,7 +29,7 @@ SYMBOLS = [
     "ps_msm_last_info", "ps_msm_set_window", "ps_msm_set_slice", "ps_msm_set_tail", "ps_microbench_mad", "ps_ctx_set_timing", "ps_msm_last_stage_ms",
     "ps_qap_create", "ps_qap_free", "ps_qap_quotient", "ps_qap_is_valid", "ps_qap_interpolate", "ps_poly_mul",
     "ps_points_lincomb", "ps_msm_multi_device", "ps_groth16_prove_multi", "ps_points_monomial_to_lagrange",
-    "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_phgr13_prove", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
+    "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_phgr13_prove", "ps_phgr13_prove_shard", "ps_phgr13_prove_multi", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
 ]
 
 
@@ -80,6 +80,10 @@ class Phgr13Vk(C.Structure):
 
 class Phgr13Ek(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("vs", "ws", "ys", "vas", "was", "yas", "gsi", "vbs", "wbs", "ybs", "lgsi")]
+
+
+class Phgr13Device(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("qap", C.c_void_p), ("sol", C.c_void_p), ("ek", Phgr13Ek)]
 
 
 class Phgr13Toxic(C.Structure):
@@ -172,6 +176,8 @@ def _load():
     lib.ps_groth16_prove_shard.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, C.c_char_p, C.c_char_p, i, i, C.c_char_p,
                                            C.c_char_p, C.c_char_p]
     lib.ps_phgr13_prove.argtypes = [vp, C.POINTER(Phgr13Ek), vp, vp, C.POINTER(Phgr13Proof)]
+    lib.ps_phgr13_prove_shard.argtypes = [vp, C.POINTER(Phgr13Ek), vp, vp, i, i, C.POINTER(Phgr13Proof)]
+    lib.ps_phgr13_prove_multi.argtypes = [C.POINTER(Phgr13Device), sz, C.POINTER(Phgr13Proof)]
     lib.ps_groth16_setup.argtypes = [vp, vp, C.POINTER(Groth16Toxic), C.POINTER(Groth16Crs)]
     lib.ps_phgr13_setup.argtypes = [vp, vp, C.POINTER(Phgr13Toxic), C.POINTER(Phgr13Crs)]
     lib.ps_phgr13_crs_free.argtypes = [C.POINTER(Phgr13Crs)]
@@ -183,6 +189,8 @@ def _load():
     return lib
 
 
+PS_ABI_VERSION = 5  # include/playsnark_hip.h: the structs above mirror that revision
+
 lib = _load()
-if lib.ps_abi_version() != 4:  # include/playsnark_hip.h PS_ABI_VERSION: the structs above mirror that revision
-    raise ImportError("libplaysnark_hip.so has ABI %d, this binding is written for 3" % lib.ps_abi_version())
+if lib.ps_abi_version() != PS_ABI_VERSION:
+    raise ImportError("libplaysnark_hip.so has ABI %d, this binding is written for %d" % (lib.ps_abi_version(), PS_ABI_VERSION))

@@ -658,6 +658,26 @@ def PHGR13Prove(ek: PHGR13EvalKey, qap: QAP, solution: Poly) -> PHGR13Proof:
     return PHGR13Proof(out)
 
 
+def PHGR13ProveShard(ek: PHGR13EvalKey, qap: QAP, solution: Poly, rank: int, world: int) -> PHGR13Proof:
+    """One rank's share of PHGR13Prove over the whole key (ps_phgr13_prove_shard): partial sums of the eight elements over
+    the rank's index ranges.  The element-wise points_sum of all ranks' shares is PHGR13Prove's proof."""
+    out = _lib.Phgr13Proof()
+    s = ek._struct()
+    _check(lib.ps_phgr13_prove_shard(qap.ctx._h, C.byref(s), qap._h, solution._h, rank, world, C.byref(out)))
+    return PHGR13Proof(out)
+
+
+def PHGR13ProveMulti(devices: Sequence[tuple]) -> PHGR13Proof:
+    """PHGR13Prove over several devices of this process, each holding only its index ranges of the evaluation key
+    (ps_phgr13_prove_multi).  devices[d] = (PHGR13EvalKey with the d-th ranges, QAP on that device, solution on that device)."""
+    arr = (_lib.Phgr13Device * len(devices))()
+    for d, (ek, q, sol) in enumerate(devices):
+        arr[d].ctx, arr[d].qap, arr[d].sol, arr[d].ek = q.ctx._h, q._h, sol._h, ek._struct()
+    out = _lib.Phgr13Proof()
+    _check(lib.ps_phgr13_prove_multi(arr, len(devices), C.byref(out)))
+    return PHGR13Proof(out)
+
+
 # -----------------------------------------------------------------------------------------
 # verifiers (SURVEY.md section 8 row f1)
 # -----------------------------------------------------------------------------------------

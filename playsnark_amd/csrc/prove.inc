@@ -1367,3 +1367,313 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
     if (!rc) rc = ps_points_sum(PS_G1, fc.data(), ndev, C_out);
     return rc;
 }
+
+// ---------------------------------------------------------------------------------------
+// PHGR13Prove over index ranges: one rank's share over the whole key (ps_phgr13_prove_shard, one process per GPU), and the
+// devices of one process each holding only its ranges (ps_phgr13_prove_multi).  PHGR13 has no fixed points, so every proof
+// element is the sum of the ranks' partial sums.  A share's sums are those of ps_phgr13_prove over the share's ranges: the
+// seven solution sums (vs, ws, ys, vas, was, yas and the pointwise beta sum, one digit sort) and the h(s) sum.
+// ---------------------------------------------------------------------------------------
+static float phgr13_ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+static int phgr13_check_arrays(const ps_phgr13_ek* ek, const char* who) {
+    const ps_points* arrs[10] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, ek->gsi, ek->vbs, ek->wbs, ek->ybs};
+    for (auto* p : arrs)
+        if (!p) return fail(PS_ERR_ARG, std::string(who) + ": NULL evaluation-key array");
+    for (int k = 0; k < 10; k++)  // by position: the same array passed as vs and ws is still a G2 array where G1 belongs
+        if (arrs[k]->group != (k == 1 ? PS_G2 : PS_G1)) return fail(PS_ERR_ARG, std::string(who) + ": evaluation-key array in the wrong group");
+    if (ek->lgsi && ek->lgsi->group != PS_G1) return fail(PS_ERR_ARG, std::string(who) + ": evaluation-key array in the wrong group");
+    return PS_OK;
+}
+
+struct Phgr13Share {
+    const ps_points* pts[7];  // vs, ws, ys, vas, was, yas and the beta sum, over this share's range
+    const ps_scalars* sv;     // solution[diff + first, cnt]
+    const ps_points* hp;      // gsi -- or lgsi -- over this share's range of h
+};
+// hands over this share's range of h as a vector on the context (a view: phgr13_share_sums frees it)
+typedef std::function<int(ps_scalars**)> Phgr13GetH;
+
+// The sums of one share on context c.  h_first: h is at hand (the quotient ran on this context, alone): ps_phgr13_prove's
+// order -- digit sort, h(s) sum, point passes.  Otherwise the sort and the seven point passes are launched first and h is
+// awaited behind them; phase [0] is then that wait.  Whatever was launched is drained on every path, so that no sum stays
+// pending on c or on its workers and the next call on the same context starts clean.
+static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, const Phgr13GetH& get_h, ps_phgr13_proof* out) {
+    if (c->pending || (c->aux && c->aux->pending)) return fail(PS_ERR_ARG, "PHGR13 share: an MSM is pending on this context");
+    uint8_t* dst[7] = {out->vss, out->wss, out->yss, out->vass, out->wass, out->yass, out->gz};
+    const size_t cnt = sh.sv->n;
+    ps_ctx* ring[PS_MULTI_RING] = {nullptr, nullptr, nullptr, nullptr};
+    MsmPlan mpl{};
+    ps_scalars* h = nullptr;
+    bool sums = false, h_launched = false;
+    auto t_h = std::chrono::steady_clock::now();
+    auto launch_h = [&]() -> int {
+        const auto t_wait = std::chrono::steady_clock::now();
+        int r2 = get_h(&h);
+        if (!h_first) {
+            c->phase_ms[0] = phgr13_ms_since(t_wait);
+            t_h = std::chrono::steady_clock::now();
+            // not chained behind an accumulation of an earlier call's workspace (the point passes above re-recorded them)
+            c->last_chain = nullptr;
+        }
+        if (!r2 && !(r2 = msm_launch_impl(c, sh.hp, h, true))) h_launched = true;
+        return r2;
+    };
+    int rc = PS_OK;
+    if (cnt) {
+        rc = msm_multi_ring(c, false, 7, ring);
+        if (!rc) rc = msm_plan_checked(c, sh.pts, 7, cnt, sh.sv->max_bits, &mpl);
+        // without h first the beta sum (and a fresh window table) may still be in flight on the context stream: fork
+        if (!rc) rc = msm_multi_sort(c, ring, sh.sv, mpl, !h_first);
+    }
+    if (!rc && h_first) rc = launch_h();
+    if (!rc && cnt) {
+        hipEvent_t after_h = (h_first && h->n && c->last_chain) ? c->last_chain->ev_acc_local : nullptr;
+        if (!(rc = msm_multi_points(c, ring, sh.pts, 7, sh.sv, mpl, after_h))) sums = true;
+    }
+    if (!rc && !h_first) rc = launch_h();
+    if (rc) {  // what is in flight finishes before its buffers can be reused
+        for (ps_ctx* w : ring)
+            if (w) (void)ps_ctx_sync(w);
+        (void)ps_ctx_sync(c);
+    }
+    uint8_t dump[96];
+    if (h_launched) {
+        int r2 = ps_msm_finish(c, rc ? dump : out->hs);
+        if (!rc) rc = r2;
+    }
+    c->phase_ms[1] = phgr13_ms_since(t_h);
+    const auto t_sums = std::chrono::steady_clock::now();
+    if (sums) {
+        int r2 = msm_multi_finish(c, ring[0], sh.pts, 7, mpl, rc ? nullptr : dst);
+        if (!rc) rc = r2;
+    }
+    c->phase_ms[2] = phgr13_ms_since(t_sums);
+    if (!rc && !cnt)  // an empty range: every solution sum is the identity
+        for (int i = 0; i < 7; i++) write_identity(i == 1 ? PS_G2 : PS_G1, dst[i]);
+    ps_scalars_free(h);
+    return rc;
+}
+
+extern "C" int ps_phgr13_prove_shard(ps_ctx* c, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sol, int rank, int world,
+                                     ps_phgr13_proof* part) {
+    if (!c || !ek || !q || !sol || !part) return fail(PS_ERR_ARG, "ps_phgr13_prove_shard: NULL argument");
+    if (world < 1 || rank < 0 || rank >= world) return fail(PS_ERR_ARG, "ps_phgr13_prove_shard: bad rank / world");
+    int rc = phgr13_check_arrays(ek, "ps_phgr13_prove_shard");
+    if (rc) return rc;
+    if (sol->n != q->m) return fail(PS_ERR_ARG, "different number of solution variables than left polynomials");  // sanityCheck
+    if (q->n < 2) return fail(PS_ERR_ARG, "ps_phgr13_prove_shard: needs at least 2 gates");
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    const size_t n = q->n, diff = q->m - q->nio, nn = ek->vs->n;
+    for (const ps_points* p : {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, ek->vbs, ek->wbs, ek->ybs})
+        if (p->n != nn) return fail(PS_ERR_LENGTH, "ps_phgr13_prove_shard: the nine solution arrays of the key differ in length");
+    if (diff + nn > sol->n) return fail(PS_ERR_LENGTH, "evaluation-key array longer than the non-IO part of the solution");
+    if (ek->gsi->n != n - 1 || (ek->lgsi && ek->lgsi->n != n - 1))  // algebra.go:350-352
+        return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(n - 1) + " and blinded eval points " +
+                                       std::to_string(ek->gsi->n != n - 1 ? ek->gsi->n : ek->lgsi->n));
+    if (c->pending || (c->aux && c->aux->pending)) return fail(PS_ERR_ARG, "ps_phgr13_prove_shard: an MSM is pending on this context");
+    const ps_points* gsi = ek->lgsi ? ek->lgsi : ek->gsi;
+    if (nn) {  // as ps_phgr13_prove: the beta sum and the window tables of the whole arrays, once per key (views of them get their own)
+        if ((rc = phgr13_beta_sum(c, ek))) return rc;
+        if (tables_wanted(c, nn)) {
+            const ps_points* whole[7] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, c->phgr_bsum};
+            for (int i = 0; i < 7 && !rc; i++) rc = points_ensure_table(c, whole[i], 0, true);
+            if (!rc && gsi->n >= PS_TABLE_MIN_POINTS) rc = points_ensure_table(c, gsi, 0, true);
+            if (rc) return rc;
+        }
+    }
+    if ((rc = quotient_run(c, q, sol, ek->lgsi ? Q_H_VALUES : Q_H_ONLY))) return rc;
+    size_t fs, cs, fh, ch;
+    shard_range_c(nn, rank, world, &fs, &cs);
+    shard_range_c(n - 1, rank, world, &fh, &ch);
+    ps_scalars* h = nullptr;  // the context's own vector (slot 3, as ps_phgr13_prove): this rank's range of h only
+    if ((rc = prover_vector(c, 3, ch, &h))) return rc;
+    if (ch)
+        hipLaunchKernelGGL(k_fr_from_mont, dim3(nblk(ch)), dim3(256), 0, c->stream, (u32*)h->st->p,
+                           (const Fr*)(ek->lgsi ? q->qt.scratch : q->hbuf) + fh, (u64)ch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->phase_ms[0] = phgr13_ms_since(t_start);
+    const ps_points* whole[7] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, nn ? c->phgr_bsum : ek->vbs};
+    ps_points* views[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ps_scalars* sv = nullptr;
+    for (int i = 0; i < 7 && !rc; i++) rc = ps_points_slice(whole[i], fs, cs, &views[i]);
+    if (!rc) rc = ps_points_slice(gsi, fh, ch, &views[7]);
+    if (!rc) rc = ps_scalars_slice(sol, diff + fs, cs, &sv);
+    if (!rc) {
+        const Phgr13Share sh{{views[0], views[1], views[2], views[3], views[4], views[5], views[6]}, sv, views[7]};
+        rc = phgr13_share_sums(c, sh, true, [&](ps_scalars** o) { return ps_scalars_slice(h, 0, ch, o); }, part);
+    }
+    for (ps_points* v : views) ps_points_free(v);
+    ps_scalars_free(sv);
+    c->phase_ms[3] = phgr13_ms_since(t_start);
+    return rc;
+}
+
+// Peer access from `dev` to `peer`, asked for once per pair where the hardware allows it.  The copies of h do not depend on
+// it (hipMemcpyPeerAsync works either way); "already enabled", or a refusal, is cleared so that it does not surface as the
+// next launch's error.
+static void peer_access_once(int dev, int peer) {
+    static std::mutex mu;
+    static std::vector<std::pair<int, int>> asked;
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& p : asked)
+        if (p.first == dev && p.second == peer) return;
+    asked.push_back({dev, peer});
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, dev, peer) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(peer, 0);
+    (void)hipGetLastError();
+}
+
+// PHGR13Prove (pinochio.go:207-254) over `ndev` devices of this process, every device holding only its index ranges of the
+// evaluation key.  The quotient runs ONCE, on dev[0], alone (as in ps_phgr13_prove: it and the accumulations are both
+// VALU-bound) and leaves h, plain limbs, in dev[0]'s context vector; an event recorded behind that conversion is the only
+// thing the other devices wait for.  Devices 1.. launch their digit sort and seven point passes at once, then wait for h on
+// the host (a condition variable: released with h, or with the first error of any device), make their stream wait for the
+// event and copy their range of h device to device into their own context vector -- no byte of h crosses host memory, no
+// upload, no allocation once the contexts are warm -- and launch the h(s) sum.  One host thread per device; the partial
+// proofs are folded on the host.
+extern "C" int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, ps_phgr13_proof* out) {
+    if (!dev || ndev == 0 || !out) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: NULL argument");
+    if (ndev > 64) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: at most 64 devices");
+    for (size_t d = 0; d < ndev; d++) {
+        if (!dev[d].ctx || !dev[d].qap || !dev[d].sol) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: NULL handle");
+        int rc = phgr13_check_arrays(&dev[d].ek, "ps_phgr13_prove_multi");
+        if (rc) return rc;
+        for (size_t e = 0; e < d; e++)
+            if (dev[e].ctx == dev[d].ctx) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: one context per device (a context appears twice)");
+    }
+    const bool lag = dev[0].ek.lgsi != nullptr;
+    for (size_t d = 0; d < ndev; d++)
+        if ((dev[d].ek.lgsi != nullptr) != lag) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: lgsi must be on every device or on none");
+    const size_t n = dev[0].qap->n, m = dev[0].qap->m, diff = m - dev[0].qap->nio;
+    if (n < 2) return fail(PS_ERR_ARG, "ps_phgr13_prove_multi: needs at least 2 gates");
+    size_t nn = 0;
+    for (size_t d = 0; d < ndev; d++) nn += dev[d].ek.vs->n;
+    if (diff + nn > m)
+        return fail(PS_ERR_LENGTH, "ps_phgr13_prove_multi: the devices' ranges of vs add up to " + std::to_string(nn) +
+                                       " points, more than the non-IO part of the solution (" + std::to_string(m - diff) + ")");
+    for (size_t d = 0; d < ndev; d++) {  // every local array must be exactly this device's range (algebra.go:350-352 otherwise)
+        const ps_phgr13_ek& ek = dev[d].ek;
+        size_t f, cnt;
+        shard_range_c(nn, (int)d, (int)ndev, &f, &cnt);
+        bool ok = true;
+        for (const ps_points* p : {ek.vs, ek.ws, ek.ys, ek.vas, ek.was, ek.yas, ek.vbs, ek.wbs, ek.ybs}) ok = ok && p->n == cnt;
+        shard_range_c(n - 1, (int)d, (int)ndev, &f, &cnt);
+        ok = ok && ek.gsi->n == cnt && (!ek.lgsi || ek.lgsi->n == cnt);
+        if (!ok || dev[d].qap->n != n || dev[d].qap->m != m || dev[d].sol->n != m)
+            return fail(PS_ERR_LENGTH, "ps_phgr13_prove_multi: device " + std::to_string(d) + " does not hold its index range of the evaluation-key arrays");
+    }
+    ps_ctx* const c0 = dev[0].ctx;
+    struct {
+        std::mutex mu;
+        std::condition_variable cv;
+        int state = 0;    // 0: no h yet; 1: h on dev[0] (c0->ev_q recorded behind it); -1: released with an error
+        int err = PS_OK;  // the first error of any device, and its text
+        std::string msg;
+        ps_scalars* h0 = nullptr;
+    } ho;
+    auto fail_all = [&](int rc) {
+        std::lock_guard<std::mutex> lk(ho.mu);
+        if (!ho.err) { ho.err = rc; ho.msg = g_last_error; }
+        if (ho.state == 0) ho.state = -1;
+        ho.cv.notify_all();
+    };
+    std::vector<ps_phgr13_proof> parts(ndev);
+    auto work = [&](size_t d) {
+        ps_ctx* c = dev[d].ctx;
+        const ps_phgr13_ek& ek = dev[d].ek;
+        const auto t_start = std::chrono::steady_clock::now();
+        int rc = hipSetDevice(c->device) == hipSuccess ? PS_OK : fail(PS_ERR_HIP, "ps_phgr13_prove_multi: hipSetDevice failed");
+        size_t fs, cs, fh, ch;
+        shard_range_c(nn, (int)d, (int)ndev, &fs, &cs);
+        shard_range_c(n - 1, (int)d, (int)ndev, &fh, &ch);
+        const ps_points* hp = lag ? ek.lgsi : ek.gsi;
+        if (!rc && (c->pending || (c->aux && c->aux->pending))) rc = fail(PS_ERR_ARG, "ps_phgr13_prove_multi: an MSM is pending on a context");
+        if (!rc && cs) {  // as ps_phgr13_prove, over the local arrays
+            rc = phgr13_beta_sum(c, &ek);
+            if (!rc && tables_wanted(c, cs)) {
+                const ps_points* loc[7] = {ek.vs, ek.ws, ek.ys, ek.vas, ek.was, ek.yas, c->phgr_bsum};
+                for (int i = 0; i < 7 && !rc; i++) rc = points_ensure_table(c, loc[i], 0, true);
+                if (!rc && hp->n >= PS_TABLE_MIN_POINTS) rc = points_ensure_table(c, hp, 0, true);
+            }
+        }
+        ps_scalars* sv = nullptr;
+        if (!rc) rc = ps_scalars_slice(dev[d].sol, diff + fs, cs, &sv);
+        const Phgr13Share sh{{ek.vs, ek.ws, ek.ys, ek.vas, ek.was, ek.yas, cs ? c->phgr_bsum : ek.vbs}, sv, hp};
+        if (d == 0) {
+            const ps_qap* q = dev[0].qap;
+            ps_scalars* h = nullptr;  // the context's own vector (slot 3, as ps_phgr13_prove): all of h, the others copy from it
+            if (!rc) rc = quotient_run(c, q, dev[0].sol, lag ? Q_H_VALUES : Q_H_ONLY);
+            if (!rc) rc = prover_vector(c, 3, n - 1, &h);
+            if (!rc) {
+                hipLaunchKernelGGL(k_fr_from_mont, dim3(nblk(n - 1)), dim3(256), 0, c->stream, (u32*)h->st->p,
+                                   (const Fr*)(lag ? q->qt.scratch : q->hbuf), (u64)(n - 1));
+                hipError_t e = hipGetLastError();
+                if (e == hipSuccess && !c->ev_q) e = hipEventCreateWithFlags(&c->ev_q, hipEventDisableTiming);
+                if (e == hipSuccess) e = hipEventRecord(c->ev_q, c->stream);
+                if (e != hipSuccess) rc = fail(PS_ERR_HIP, std::string("ps_phgr13_prove_multi: h: ") + hipGetErrorString(e));
+            }
+            if (rc) {
+                fail_all(rc);
+            } else {
+                std::lock_guard<std::mutex> lk(ho.mu);
+                ho.h0 = h;
+                if (ho.state == 0) ho.state = 1;
+                ho.cv.notify_all();
+            }
+            if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PS_ERR_HIP, "ps_phgr13_prove_multi: quotient: stream synchronisation failed");
+            c->phase_ms[0] = phgr13_ms_since(t_start);
+            if (!rc) rc = phgr13_share_sums(c, sh, true, [&](ps_scalars** o) { return ps_scalars_slice(h, fh, ch, o); }, &parts[0]);
+        } else if (!rc) {
+            auto get_h = [&](ps_scalars** o) -> int {
+                {
+                    std::unique_lock<std::mutex> lk(ho.mu);
+                    ho.cv.wait(lk, [&] { return ho.state != 0; });
+                    if (ho.state < 0) return fail(ho.err, ho.msg);
+                }
+                ps_scalars* hl = nullptr;  // this device's context vector (slot 3): its range of h
+                int r2 = prover_vector(c, 3, ch, &hl);
+                if (r2) return r2;
+                HIP_TRY(hipStreamWaitEvent(c->stream, c0->ev_q, 0));
+                if (ch) {
+                    const u32* src = scalars_ptr(ho.h0) + 8 * fh;
+                    if (c->device == c0->device) {
+                        HIP_TRY(hipMemcpyAsync(hl->st->p, src, 32 * ch, hipMemcpyDeviceToDevice, c->stream));
+                    } else {
+                        peer_access_once(c->device, c0->device);
+                        HIP_TRY(hipMemcpyPeerAsync(hl->st->p, c->device, src, c0->device, 32 * ch, c->stream));
+                    }
+                }
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                return ps_scalars_slice(hl, 0, ch, o);
+            };
+            rc = phgr13_share_sums(c, sh, false, get_h, &parts[d]);
+        }
+        if (rc) fail_all(rc);
+        ps_scalars_free(sv);
+        c->phase_ms[3] = phgr13_ms_since(t_start);
+    };
+    {
+        std::vector<std::future<void>> jobs;
+        for (size_t d = 1; d < ndev; d++) jobs.push_back(std::async(std::launch::async, work, d));
+        work(0);
+        for (auto& j : jobs) j.get();
+    }
+    if (ho.err) return fail(ho.err, ho.msg);
+    const size_t off[8] = {offsetof(ps_phgr13_proof, vss), offsetof(ps_phgr13_proof, vass), offsetof(ps_phgr13_proof, wss),
+                           offsetof(ps_phgr13_proof, wass), offsetof(ps_phgr13_proof, yss), offsetof(ps_phgr13_proof, yass),
+                           offsetof(ps_phgr13_proof, hs), offsetof(ps_phgr13_proof, gz)};
+    for (int k = 0; k < 8; k++) {
+        const int group = off[k] == offsetof(ps_phgr13_proof, wss) ? PS_G2 : PS_G1;
+        const size_t wb = wire_bytes(group);
+        std::vector<uint8_t> flat(wb * ndev);
+        for (size_t d = 0; d < ndev; d++) memcpy(flat.data() + wb * d, (const uint8_t*)&parts[d] + off[k], wb);
+        int rc = ps_points_sum(group, flat.data(), ndev, (uint8_t*)out + off[k]);
+        if (rc) return rc;
+    }
+    return PS_OK;
+}

@@ -190,6 +190,21 @@ inline ps_phgr13_proof PHGR13Prove(Context& c, const ps_phgr13_ek& ek, const QAP
     return out;
 }
 
+// One rank's share of PHGR13Prove over the whole key; the ranks' eight elements add up (ps_points_sum) to the proof
+inline ps_phgr13_proof PHGR13ProveShard(Context& c, const ps_phgr13_ek& ek, const QAP& qap, const Poly& solution, int rank,
+                                        int world) {
+    ps_phgr13_proof out;
+    check(ps_phgr13_prove_shard(c.get(), &ek, qap.get(), solution.get(), rank, world, &out));
+    return out;
+}
+
+// PHGR13Prove over the devices of this process, dev[d].ek holding only device d's index ranges (ps_phgr13_prove_multi)
+inline ps_phgr13_proof PHGR13ProveMulti(const std::vector<ps_phgr13_device>& dev) {
+    ps_phgr13_proof out;
+    check(ps_phgr13_prove_multi(dev.data(), dev.size(), &out));
+    return out;
+}
+
 // func Groth16Verify(tr Groth16Setup, q QAP, p Groth16Proof, io Vector) bool (groth16.go:214)
 inline bool Groth16Verify(Context& c, const ps_groth16_vk& vk, const Groth16Proof& p, const Poly& io) {
     int ok = 0;

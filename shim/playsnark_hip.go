@@ -755,6 +755,106 @@ func PHGR13VerifyHIP(hp *HipPHGR13, p PHGR13Proof, io Vector) bool {
 	return ok != 0
 }
 
+// HipPHGR13Multi: every device holds only ITS index ranges of the evaluation key -- vs .. ybs over len(vs), gsi over
+// n-1 -- its own QAP of the circuit and its own copy of the solution.  The quotient runs once, on device 0; the other
+// devices copy their range of h from it device to device.
+type HipPHGR13Multi struct {
+	hd     *HipDevices
+	dev    []C.ps_phgr13_device
+	qaps   []*C.ps_qap
+	arrays []*HipShardedPoints
+}
+
+func NewHipPHGR13Multi(hd *HipDevices, ek PHGR13EvalKey, circuit R1CS) *HipPHGR13Multi {
+	hm := &HipPHGR13Multi{hd: hd, dev: make([]C.ps_phgr13_device, len(hd.ctxs))} // zero-initialised, as the header requires (lgsi NULL)
+	up := func(group C.int, pts []Commit) *HipShardedPoints {
+		sp := hd.UploadPoints(group, pts)
+		hm.arrays = append(hm.arrays, sp)
+		return sp
+	}
+	// check() panics on a library error: a device that fails after others succeeded must not leak their QAPs and shards
+	done := false
+	defer func() {
+		if !done {
+			hm.Free()
+		}
+	}()
+	vs, ws, ys := up(C.PS_G1, ek.vs), up(C.PS_G2, ek.ws), up(C.PS_G1, ek.ys)
+	vas, was, yas := up(C.PS_G1, ek.vas), up(C.PS_G1, ek.was), up(C.PS_G1, ek.yas)
+	gsi := up(C.PS_G1, ek.gsi)
+	// wbs is declared []G2 (pinochio.go:60) but generated from g1w: G1 points (pinochio.go:136)
+	vbs, wbs, ybs := up(C.PS_G1, ek.vbs), up(C.PS_G1, ek.wbs), up(C.PS_G1, ek.ybs)
+	l, r, o := newCsr(circuit.left), newCsr(circuit.right), newCsr(circuit.out)
+	defer l.free()
+	defer r.free()
+	defer o.free()
+	for d, c := range hd.ctxs {
+		var q *C.ps_qap
+		cc := c
+		check(func() C.int {
+			return C.ps_qap_create(cc, C.size_t(len(circuit.left)), C.size_t(len(circuit.vars)), C.size_t(circuit.nbIO()), &l.csr, &r.csr, &o.csr, &q)
+		})
+		hm.qaps = append(hm.qaps, q)
+		hm.dev[d].ctx, hm.dev[d].qap = c, q
+		e := &hm.dev[d].ek
+		e.vs, e.ws, e.ys = vs.parts[d], ws.parts[d], ys.parts[d]
+		e.vas, e.was, e.yas = vas.parts[d], was.parts[d], yas.parts[d]
+		e.gsi = gsi.parts[d]
+		e.vbs, e.wbs, e.ybs = vbs.parts[d], wbs.parts[d], ybs.parts[d]
+	}
+	done = true
+	return hm
+}
+
+func (hm *HipPHGR13Multi) Free() {
+	for _, q := range hm.qaps {
+		C.ps_qap_free(q)
+	}
+	for _, a := range hm.arrays {
+		a.Free()
+	}
+}
+
+// PHGR13ProveHIPMulti is PHGR13Prove (pinochio.go:207-254) over the devices of this process: same proof bytes as
+// PHGR13ProveHIP.  Deterministic.
+func PHGR13ProveHIPMulti(hm *HipPHGR13Multi, sol Vector) PHGR13Proof {
+	hm.hd.mu.Lock()
+	defer hm.hd.mu.Unlock()
+	vals := make([]C.int64_t, len(sol))
+	for i, v := range sol {
+		vals[i] = C.int64_t(v)
+	}
+	// the device structs go to C memory: they hold C pointers only, but live in a Go slice
+	cdev := (*C.ps_phgr13_device)(C.malloc(C.size_t(len(hm.dev)) * C.size_t(unsafe.Sizeof(hm.dev[0]))))
+	defer C.free(unsafe.Pointer(cdev))
+	devs := (*[1 << 16]C.ps_phgr13_device)(unsafe.Pointer(cdev))[:len(hm.dev):len(hm.dev)]
+	var vp *C.int64_t // an empty solution has no first element to point at (the library refuses it by length, not by a Go panic here)
+	if len(vals) > 0 {
+		vp = &vals[0]
+	}
+	for d := range hm.dev {
+		var h *C.ps_scalars
+		cc := hm.dev[d].ctx
+		check(func() C.int { return C.ps_scalars_upload_i64(cc, vp, C.size_t(len(vals)), &h) })
+		defer C.ps_scalars_free(h)
+		devs[d] = hm.dev[d]
+		devs[d].sol = h
+	}
+	var out C.ps_phgr13_proof
+	check(func() C.int { return C.ps_phgr13_prove_multi(cdev, C.size_t(len(hm.dev)), &out) })
+	g1 := func(p *C.uint8_t) Commit { return pointFrom(C.PS_G1, bytesOf(unsafe.Pointer(p), g1Wire), zeroG1) }
+	return PHGR13Proof{
+		vss:  g1(&out.vss[0]),
+		vass: g1(&out.vass[0]),
+		wss:  pointFrom(C.PS_G2, bytesOf(unsafe.Pointer(&out.wss[0]), g2Wire), zeroG2),
+		wass: g1(&out.wass[0]),
+		yss:  g1(&out.yss[0]),
+		yass: g1(&out.yass[0]),
+		hs:   g1(&out.hs[0]),
+		gz:   g1(&out.gz[0]),
+	}
+}
+
 // ---------------------------------------------------------------------------------------
 // the reference's own tests, pointed at the GPU backend (groth16_test.go:22-30, pinocchio_test.go:23-29):
 //
@@ -769,4 +869,6 @@ func PHGR13VerifyHIP(hp *HipPHGR13, p PHGR13Proof, io Vector) bool {
 //	require.True(t, hq.IsValidHIP(s))                                            // TestQAPValidity, qap_test.go
 //	hd := NewHipDevices(8); hm := NewHipGroth16Multi(hd, tr, r1cs)              // one process, eight GPUs
 //	require.True(t, Groth16Verify(tr, qap, Groth16ProveHIPMulti(hm, s), s[:qap.nbVars-qap.nbIO]))
+//	hpm := NewHipPHGR13Multi(hd, setup.EK, r1cs)                                 // PHGR13 on the same eight GPUs
+//	require.True(t, PHGR13Verify(setup.VK, qap, PHGR13ProveHIPMulti(hpm, s), s[:qap.nbVars-qap.nbIO]))
 // ---------------------------------------------------------------------------------------
