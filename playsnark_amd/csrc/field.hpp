@@ -357,7 +357,8 @@ PS_INL Fp f_norm(const Fp& a) {
     r.l[FP_L - 1] = a.l[FP_L - 1] + (a.l[FP_L - 2] >> 28);
     return r;
 }
-// full sequential carry: limbs 0..12 in [0, 2^28), signed top limb; unique for a given V
+// full sequential carry: limbs 0..12 in [0, 2^28), signed top limb; unique for a given V.  The carry is added to a limb in
+// 32 bits, so the input must be class <= 7 (a class-8 limb plus a carry leaves int32); the same holds for fp_canon.
 PS_INL Fp fp_propagate(const Fp& a) {
     Fp r;
     i32 c = 0;
@@ -922,6 +923,9 @@ PS_INL Fr fr_mul(const Fr& a_in, const Fr& b_in) {
     // On the device: the single-chain form above.  With a statement per multiply-add (194 compiler-inserted wait states per
     // product) it won only where the chip was full of waves (2^20 gates: -2.5 %) and lost 10 % at 2^10 .. 2^16 gates; with a
     // statement per column it wins 2-6 % at every size (A/B against the code below, 2^10 .. 2^20 gates).
+    // Device output contract (tests/test_device_field.py): the SAME value as the code below, in other limbs -- limbs 0..8 in
+    // (-2^28, 0] instead of [0, 2^28), the top limb small and signed, the value in (-r/8, 9r/8).  The digits m_k are the same;
+    // the upper columns carry the ceiling where the code below carries the floor.
     return fr_mul_chain(a_in, b_in);
 #endif
     Fr r;

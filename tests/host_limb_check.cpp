@@ -2,7 +2,10 @@
 // host-side pairing arithmetic (pairing_math.inc), compiled FOR THE HOST with
 //     g++ -std=c++17 -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -pthread
 // so that every signed 64-bit column sum, every shift and every array access of the product's field code runs under
-// UBSan / ASan (GPU sanitizers are not available on the pool; the arithmetic is the same source on both sides).
+// UBSan / ASan (GPU sanitizers are not available on the pool).  What runs here are the C++ forms of the products.  The
+// device compiles other code for them: the generated multiply-add chains (fp_chain.inc; fr_chain.inc, which works in the
+// negated domain and returns limbs in (-2^28, 0]), the lane-pair Fp2s with its DPP moves, and the noinline fp_mul_call /
+// fp_sqr_call.  Those are checked on the GPU, against big integers, by tests/test_device_field.py, not by this file.
 //
 // The contract (field.hpp): limbs are 28-bit, signed and lazy; "class c" means |limb| < c * 2^28.
 //   f_mul(a, b)                 needs class(a) class(b) <= 8
