@@ -634,7 +634,10 @@ static inline hipError_t ntt_run(const NttTables& tb, hipStream_t st, Fr* data, 
         fz.cnt = fuse.cnt;
         fz.top = fuse.top;
         // inverse: divide the doubling out in the last pass, and earlier only where the next pass would push
-        // the growth past 2^16 (the lazy top limb holds 2^16 r with room to spare)
+        // the growth past 2^16 (the lazy top limb holds 2^16 r with room to spare).  The margin is wide: without the early
+        // scaling a transform of 2^s points reaches |V| < 2^s * 9r/8, top limb < 2^s * 8.2, and still gives exact results at
+        // every size the tests reach (2^22, tests/test_quotient_shapes_gpu.py); it is 2^28-point transforms (n near 2^27
+        // gates) whose top limb would pass 2^31.
         int scale_log = 0;
         if (INV) {
             unscaled += k;

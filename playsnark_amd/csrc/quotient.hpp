@@ -207,7 +207,8 @@ __global__ void __launch_bounds__(256) k_spmv_long_rows(const u32* __restrict__ 
         if (threadIdx.x < stride) sm[threadIdx.x] = fr_norm(fr_add(sm[threadIdx.x], sm[threadIdx.x + stride]));
         __syncthreads();
     }
-    if (threadIdx.x == 0) y[r] = sm[0];
+    // 256 reduced values add up to (-32 r, 288 r): one more product brings the row back under the ~64 r of a stored vector
+    if (threadIdx.x == 0) y[r] = fr_reduce(sm[0]);
 }
 __global__ void __launch_bounds__(256) k_check_gates(const Fr* __restrict__ yA, const Fr* __restrict__ yB,
                                                      const Fr* __restrict__ yC, u32 n, u32* __restrict__ flag) {
