@@ -49,7 +49,10 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *   1  round 1;  2  Lagrange-form key arrays (lxi / lxi2 / lxi_t / lgsi), multi-device entries;
  *   3  ps_msm_info.window_table, ps_msm_set_tail, ps_ctx_set_table_budget, ps_qap_is_valid, ps_microbench_mad;
  *   4  ps_points_monomial_to_lagrange; index-range views build window tables of their own; PS_MSM_QUEUE 3 -> 4 (no struct changed);
- *   5  ps_phgr13_prove_shard, ps_phgr13_prove_multi and its ps_phgr13_device (no existing struct changed) */
+ *   5  ps_phgr13_prove_shard, ps_phgr13_prove_multi and its ps_phgr13_device (no existing struct changed);
+ *      later within 5: ps_groth16_prove_local, and ps_groth16_prove_multi reads the optional lxi / lxi2 / lxi_t of
+ *      ps_groth16_device.pk.  No struct changed, so the number stays: an entry point added within a revision is detected by
+ *      its symbol (dlsym), not by ps_abi_version(). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -259,7 +262,7 @@ int ps_groth16_prove(ps_ctx* ctx, const ps_groth16_pk* pk, const ps_qap* q, cons
                      uint8_t C[96]);
 
 /* One rank's share of Groth16Prove when the sums are sharded over `world` GPUs (one process each): rank g
- * takes its index range of every CRS array, rank 0 also the fixed points; A_part / B_part / C_part of all
+ * takes its index range of every CRS array, the LAST rank also the fixed points; A_part / B_part / C_part of all
  * ranks add up (ps_points_sum, after an all_gather) to the A, B, C of ps_groth16_prove.  Every rank
  * computes the quotient itself (beside its sums: the quotient runs on a stream of its own). */
 int ps_groth16_prove_shard(ps_ctx* ctx, const ps_groth16_pk* pk, const ps_qap* q, const ps_scalars* sol,
@@ -268,10 +271,25 @@ int ps_groth16_prove_shard(ps_ctx* ctx, const ps_groth16_pk* pk, const ps_qap* q
 
 /* Groth16Prove over the devices of one process, every device holding only ITS index range of the CRS arrays: device d
  * of ndev holds Xi[range(n)], Xi2[range(n)], NioLP[range(nbIO)], XiT[range(n-1)] with range = the d-th of ndev
- * contiguous parts whose sizes differ by at most one (PS_ERR_LENGTH otherwise); the fixed points are read from dev[0].pk.
- * Each device has its own context, its own ps_qap of the circuit and its own copy of the solution.  With three or more
- * devices the parts of the quotient (A, B, h) are computed side by side on devices 0, 1, 2.  Same proof bytes as
- * ps_groth16_prove. */
+ * contiguous parts whose sizes differ by at most one (PS_ERR_LENGTH, naming the device, otherwise); the fixed points are
+ * read from dev[0].pk.  Each device has its own context, its own ps_qap of the circuit and its own copy of the solution;
+ * 1 <= ndev <= 64.  Same proof bytes as ps_groth16_prove.
+ *
+ * The optional arrays of dev[d].pk select the route, as in ps_groth16_prove:
+ *   - lxi[range(n)], lxi2[range(n)], lxi_t[range(n-1)] on EVERY device (xi / xi2 / xi_t may then be NULL, and are not read):
+ *     the route without coefficient vectors.  The scalars of A, B and of B in G1 are the wire values of the device's OWN rows
+ *     of L.s and R.s -- computed, gate-checked and converted by one kernel on that device, no exchange at all; the four sums
+ *     that need no h start at once.  Only the values h(n+k) depend on the whole circuit: their three convolutions run on
+ *     devices 0, 1, 2 side by side (one each; ndev < 3: all on dev[0]), and every device copies its ranges of the three
+ *     results device to device -- 3 x 40 bytes per node of its range -- and finishes h there.  Nothing of A, B or h crosses
+ *     host memory, nothing is allocated once the contexts are warm.  The contexts must be distinct (PS_ERR_ARG).  The
+ *     divisibility test is the union of the devices' own-row checks: PS_ERR_NOT_DIVISIBLE from any of them fails the call,
+ *     and every device has drained what it launched when the call returns.  ps_prove_last_phase_ms on each context gives
+ *     that device's share.  PS_G16_MULTI_HSPLIT=0 in the environment of ps_ctx_create (read from dev[0].ctx; default 1) keeps
+ *     the three convolutions on dev[0] whatever ndev is: a knob for tests and measurements, as PS_G16_B1_MIN_N is.
+ *   - on some devices but not on all: PS_ERR_ARG.
+ *   - on none: the monomial arrays are required; with three or more devices the parts of the quotient (A, B, h) are
+ *     computed side by side on devices 0, 1, 2 and cross through host memory. */
 typedef struct {
     ps_ctx* ctx;
     const ps_qap* qap;
@@ -280,6 +298,17 @@ typedef struct {
 } ps_groth16_device;
 int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev, const uint8_t r_be32[32], const uint8_t s_be32[32],
                            uint8_t A[96], uint8_t B[192], uint8_t C[96]);
+
+/* One rank's share of Groth16Prove when the rank holds ONLY its index ranges of a Lagrange-form key (one process per GPU):
+ * pk_local has lxi[range(n)], lxi2[range(n)], lxi_t[range(n-1)], nio_lp[range(nbIO)] for (rank, world) -- PS_ERR_LENGTH
+ * otherwise; a key without all three L-arrays is PS_ERR_ARG (xi / xi2 / xi_t are not read) -- and the fixed points, which
+ * the LAST rank adds.  The share of ps_groth16_prove_multi's Lagrange route, with the values of h computed on this device
+ * (processes cannot copy peer to peer, and 2 ms replicated beats three broadcasts); the gate check covers all rows, so every
+ * rank reports an unsatisfied witness.  The element-wise ps_points_sum of all ranks' parts is the proof of
+ * ps_groth16_prove, byte for byte. */
+int ps_groth16_prove_local(ps_ctx* ctx, const ps_groth16_pk* pk_local, const ps_qap* q, const ps_scalars* sol,
+                           const uint8_t r_be32[32], const uint8_t s_be32[32], int rank, int world, uint8_t A_part[96],
+                           uint8_t B_part[192], uint8_t C_part[96]);
 
 typedef struct { /* PHGR13EvalKey (pinochio.go:37-62); ws is G2, every other array is G1 */
     const ps_points *vs, *ws, *ys, *vas, *was, *yas, *gsi, *vbs, *wbs, *ybs;
@@ -323,7 +352,10 @@ int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, ps_phgr13_pr
  * the h(s) sum (PHGR13), [2] the remaining sums incl. host folds, [3] total.  For reports only.
  * ps_phgr13_prove_shard / ps_phgr13_prove_multi set it for the context's own share: [0] computing h -- or, on a device of
  * ps_phgr13_prove_multi other than dev[0], waiting for h including the copy of its range --, [1] the h(s) sum, [2] the
- * solution sums (what is left of them after [1]), [3] total. */
+ * solution sums (what is left of them after [1]), [3] total.
+ * ps_groth16_prove_local, and ps_groth16_prove_multi over Lagrange-form local keys, likewise for the context's share: [0] the
+ * own rows (and whatever of the values route ran on this device) plus the wait for h, [1] the h sum, [2] the other sums and
+ * the host's weighting, [3] total. */
 #define PS_PROVE_PHASES 4
 int ps_prove_last_phase_ms(ps_ctx* ctx, float ms[PS_PROVE_PHASES]);
 

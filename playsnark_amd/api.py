@@ -509,11 +509,15 @@ class QAP:
 class Groth16Setup:
     """The prover's part of type Groth16Setup (groth16.go:30-61)."""
 
-    def __init__(self, Alpha: bytes, Beta: bytes, Delta: bytes, Beta2: bytes, Delta2: bytes, Xi: Points,
-                 Xi2: Points, NioLP: Points, XiT: Points, LXi: Optional[Points] = None, LXi2: Optional[Points] = None,
-                 LXiT: Optional[Points] = None):
+    def __init__(self, Alpha: bytes, Beta: bytes, Delta: bytes, Beta2: bytes, Delta2: bytes, Xi: Optional[Points],
+                 Xi2: Optional[Points], NioLP: Points, XiT: Optional[Points], LXi: Optional[Points] = None,
+                 LXi2: Optional[Points] = None, LXiT: Optional[Points] = None):
         """LXi, LXi2, LXiT: the same CRS in Lagrange form (l_j(x) G1, l_j(x) G2, lambda_k(x) t(x)/delta G1), as the device
-        setup emits it; with all three the prover needs no polynomial in coefficient form (ps_groth16_pk)."""
+        setup emits it; with all three the prover needs no polynomial in coefficient form (ps_groth16_pk), and Xi, Xi2, XiT
+        may then be None (a Lagrange-only key: half the upload and half the device memory)."""
+        lagrange = LXi is not None and LXi2 is not None and LXiT is not None
+        if not lagrange and (Xi is None or Xi2 is None or XiT is None):
+            raise ValueError("Groth16Setup: Xi, Xi2 and XiT may be None only when LXi, LXi2 and LXiT are all given")
         self.Alpha, self.Beta, self.Delta, self.Beta2, self.Delta2 = Alpha, Beta, Delta, Beta2, Delta2
         self.Xi, self.Xi2, self.NioLP, self.XiT = Xi, Xi2, NioLP, XiT
         self.LXi, self.LXi2, self.LXiT = LXi, LXi2, LXiT
@@ -521,6 +525,11 @@ class Groth16Setup:
     def monomial_only(self) -> "Groth16Setup":
         """The key as the reference's NewGroth16TrustedSetup makes it: the monomial arrays alone."""
         return Groth16Setup(self.Alpha, self.Beta, self.Delta, self.Beta2, self.Delta2, self.Xi, self.Xi2, self.NioLP, self.XiT)
+
+    def lagrange_only(self) -> "Groth16Setup":
+        """The key with its Lagrange-form arrays alone (Xi, Xi2, XiT dropped): all the fast route reads."""
+        return Groth16Setup(self.Alpha, self.Beta, self.Delta, self.Beta2, self.Delta2, None, None, self.NioLP, None,
+                            self.LXi, self.LXi2, self.LXiT)
 
     def with_lagrange(self, qap: "QAP") -> "Groth16Setup":
         """The same key with its Lagrange-form arrays computed from the monomial ones ALONE (no toxic waste, groth16.go:13-14):
@@ -533,7 +542,9 @@ class Groth16Setup:
         for name, src in (("alpha", self.Alpha), ("beta", self.Beta), ("delta", self.Delta),
                           ("beta2", self.Beta2), ("delta2", self.Delta2)):
             C.memmove(getattr(pk, name), src, len(src))
-        pk.xi, pk.xi2, pk.nio_lp, pk.xi_t = self.Xi._h, self.Xi2._h, self.NioLP._h, self.XiT._h
+        pk.nio_lp = self.NioLP._h
+        if self.Xi is not None and self.Xi2 is not None and self.XiT is not None:  # (NULL otherwise: a Lagrange-only key)
+            pk.xi, pk.xi2, pk.xi_t = self.Xi._h, self.Xi2._h, self.XiT._h
         if self.LXi is not None and self.LXi2 is not None and self.LXiT is not None:
             pk.lxi, pk.lxi2, pk.lxi_t = self.LXi._h, self.LXi2._h, self.LXiT._h
         return pk
@@ -572,9 +583,21 @@ def Groth16Prove(tr: Groth16Setup, q: QAP, sol: Poly, r: int, s: int) -> Groth16
     return Groth16Proof(r, s, A.raw, B.raw, Cc.raw)
 
 
+def Groth16ProveLocal(tr_local: Groth16Setup, q: QAP, sol: Poly, r: int, s: int, rank: int, world: int):
+    """One rank's share (A_part, B_part, C_part) of Groth16Prove when the rank holds ONLY its index ranges of a Lagrange-form
+    key (ps_groth16_prove_local): LXi[range(n)], LXi2[range(n)], LXiT[range(n-1)], NioLP[range(nbIO)].  The element-wise
+    points_sum of all ranks' parts is Groth16Prove's proof; the last rank adds the fixed points."""
+    A, B, Cc = C.create_string_buffer(96), C.create_string_buffer(192), C.create_string_buffer(96)
+    pk = tr_local._struct()
+    _check(lib.ps_groth16_prove_local(q.ctx._h, C.byref(pk), q._h, sol._h, _be32(r), _be32(s), rank, world, A, B, Cc))
+    return A.raw, B.raw, Cc.raw
+
+
 def Groth16ProveMulti(devices: Sequence[tuple], r: int, s: int) -> Groth16Proof:
     """Groth16Prove over several devices of this process, each holding only its index range of the CRS arrays
-    (ps_groth16_prove_multi).  devices[d] = (Groth16Setup with the d-th ranges, QAP on that device, solution on that device)."""
+    (ps_groth16_prove_multi).  devices[d] = (Groth16Setup with the d-th ranges, QAP on that device, solution on that device).
+    Keys that carry LXi / LXi2 / LXiT on every device (Xi / Xi2 / XiT may be None) take the route without coefficient
+    vectors; keys with the monomial arrays alone interpolate and divide."""
     arr = (_lib.Groth16Device * len(devices))()
     keep = []
     for d, (tr, q, sol) in enumerate(devices):

@@ -133,6 +133,7 @@ struct ps_ctx {
     bool g16_tabs = false;           // whether window tables were wanted when the arrays above were made
     bool g16_split = false;          // ... and whether PC was made for the split form of C (prove.inc, groth16_prove_impl)
     size_t g16_b1_min_n = (size_t)1 << 19;  // Lagrange-form keys of this many constraints or more: B in G1 as a sum of its own (PS_G16_B1_MIN_N)
+    bool g16_multi_hsplit = true;    // ps_groth16_prove_multi, Lagrange-form local keys, three or more devices: the three convolutions of the values route on devices 0, 1, 2 (PS_G16_MULTI_HSPLIT)
     hipEvent_t g16_ready = nullptr;
     // PHGR13 driver: vbs + wbs + ybs summed pointwise once per evaluation key (gz, pinochio.go:239-242)
     unsigned long long phgr_key[3] = {0, 0, 0};
@@ -254,6 +255,7 @@ extern "C" int ps_ctx_create(int device, ps_ctx** out) {
         return fail(PS_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", library is built for gfx950 only");
     ps_ctx* c = new ps_ctx();
     if (const char* e = getenv("PS_G16_B1_MIN_N")) c->g16_b1_min_n = (size_t)strtoull(e, nullptr, 10);  // tests / measurements
+    if (const char* e = getenv("PS_G16_MULTI_HSPLIT")) c->g16_multi_hsplit = strtol(e, nullptr, 10) != 0;  // likewise
     c->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {

@@ -32,6 +32,10 @@ struct ps_qap {
     Fr* coefB = nullptr;   // n
     Fr* coefC = nullptr;   // n
     Fr* hbuf = nullptr;    // n-1
+    // rows that are long in ANY of the three matrices, ascending (k_own_rows_long): on the device, and on the host so that a
+    // prover can cut the list to its range of rows
+    u32* long_any = nullptr;
+    std::vector<u32> long_any_h;
     std::vector<void*> owned;
 };
 
@@ -139,6 +143,12 @@ extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps
         if ((rc = upload(&t.val, h.tv))) continue;
         if (d.n_long && (rc = upload(&d.long_rows, h.lr))) continue;
         if (t.n_long && (rc = upload(&t.long_rows, h.lrT))) continue;
+        q->long_any_h.insert(q->long_any_h.end(), h.lr.begin(), h.lr.end());
+    }
+    if (rc == PS_OK && !q->long_any_h.empty()) {
+        std::sort(q->long_any_h.begin(), q->long_any_h.end());
+        q->long_any_h.erase(std::unique(q->long_any_h.begin(), q->long_any_h.end()), q->long_any_h.end());
+        rc = upload(&q->long_any, q->long_any_h);
     }
     FactTables ft = facts.get();
     if (rc == PS_OK) rc = dev_alloc(q, &q->sol_m, m);
@@ -1224,6 +1234,36 @@ extern "C" int ps_msm_multi_device(ps_ctx* const* ctxs, const ps_points* const* 
 // route, which also carries the divisibility test) are computed side by side on devices 0, 1, 2; the coefficient vectors
 // cross through host memory, each device takes its ranges, and the partial proofs are folded on the host.  A Go caller
 // cannot start one process per GPU around a function call; this is its multi-GPU entry.
+// That is the route of MONOMIAL local keys.  When every device's pk carries lxi / lxi2 / lxi_t the call goes to
+// groth16_prove_multi_lagrange (end of this file): no coefficient vectors, nothing through host memory.
+// The fixed points of a proof, added on the host to ONE share (the sums themselves ran elsewhere):
+//   A += r Delta + Alpha ;  B += s Delta2 + Beta2 ;  C += rs Delta + s Alpha + r Beta   (expanded from groth16.go:149-200)
+static int g16_add_fixed_points(const ps_groth16_pk& pk, const uint8_t* r_be32, const uint8_t* s_be32, uint8_t* A, uint8_t* B, uint8_t* C) {
+    Fr rm = fr_mont_from_be32(r_be32), sm = fr_mont_from_be32(s_be32);
+    uint8_t one[32] = {0}, rs[32];
+    one[31] = 1;
+    fr_mont_to_be32(rs, fr_mul(rm, sm));
+    uint8_t pts3[3 * 96], sc3[96], fx[96], fx2[192], pts2[2 * 192], acc2[2 * 192];
+    memcpy(pts3, pk.delta, 96); memcpy(pts3 + 96, pk.alpha, 96);
+    memcpy(sc3, r_be32, 32); memcpy(sc3 + 32, one, 32);
+    int rc = ps_points_lincomb(PS_G1, pts3, sc3, 2, fx);
+    memcpy(pts3, A, 96); memcpy(pts3 + 96, fx, 96);
+    if (!rc) rc = ps_points_sum(PS_G1, pts3, 2, A);
+    memcpy(pts2, pk.delta2, 192); memcpy(pts2 + 192, pk.beta2, 192);
+    memcpy(sc3, s_be32, 32); memcpy(sc3 + 32, one, 32);
+    if (!rc) rc = ps_points_lincomb(PS_G2, pts2, sc3, 2, fx2);
+    memcpy(acc2, B, 192); memcpy(acc2 + 192, fx2, 192);
+    if (!rc) rc = ps_points_sum(PS_G2, acc2, 2, B);
+    memcpy(pts3, pk.delta, 96); memcpy(pts3 + 96, pk.alpha, 96); memcpy(pts3 + 192, pk.beta, 96);
+    memcpy(sc3, rs, 32); memcpy(sc3 + 32, s_be32, 32); memcpy(sc3 + 64, r_be32, 32);
+    if (!rc) rc = ps_points_lincomb(PS_G1, pts3, sc3, 3, fx);
+    memcpy(pts3, C, 96); memcpy(pts3 + 96, fx, 96);
+    if (!rc) rc = ps_points_sum(PS_G1, pts3, 2, C);
+    return rc;
+}
+// every device's pk carries lxi / lxi2 / lxi_t: the route without coefficient vectors (at the end of this file)
+static int groth16_prove_multi_lagrange(const ps_groth16_device* dev, size_t ndev, size_t nn, const uint8_t* r_be32, const uint8_t* s_be32,
+                                        uint8_t* A_out, uint8_t* B_out, uint8_t* C_out);
 static int g16_download_all(ps_ctx* c, const ps_scalars* s, std::vector<uint8_t>& host) {
     host.resize(32 * s->n);
     return ps_scalars_download(c, s, 0, s->n, host.data());
@@ -1233,8 +1273,15 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
     if (!dev || ndev == 0 || !r_be32 || !s_be32 || !A_out || !B_out || !C_out) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: NULL argument");
     if (ndev > 64) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: at most 64 devices");
     for (size_t d = 0; d < ndev; d++)
-        if (!dev[d].ctx || !dev[d].qap || !dev[d].sol || !dev[d].pk.xi || !dev[d].pk.xi2 || !dev[d].pk.nio_lp || !dev[d].pk.xi_t)
-            return fail(PS_ERR_ARG, "ps_groth16_prove_multi: NULL handle");
+        if (!dev[d].ctx || !dev[d].qap || !dev[d].sol || !dev[d].pk.nio_lp) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: NULL handle");
+    // Lagrange-form local keys (lxi, lxi2, lxi_t on EVERY device; the monomial arrays may then be NULL, as in ps_groth16_prove)
+    // take the route without coefficient vectors; monomial keys take the route below, as before
+    const bool lag = g16_lagrange(&dev[0].pk);
+    for (size_t d = 0; d < ndev; d++) {
+        if (g16_lagrange(&dev[d].pk) != lag)
+            return fail(PS_ERR_ARG, "ps_groth16_prove_multi: lxi / lxi2 / lxi_t must be on every device or on none");
+        if (!lag && (!dev[d].pk.xi || !dev[d].pk.xi2 || !dev[d].pk.xi_t)) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: NULL handle");
+    }
     const size_t n = dev[0].qap->n, m = dev[0].qap->m, diff = m - dev[0].qap->nio;
     if (n < 2) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: needs at least 2 gates");
     size_t nn = 0;
@@ -1244,14 +1291,16 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
         size_t f, cnt;
         const ps_groth16_pk& pk = dev[d].pk;
         shard_range_c(n, (int)d, (int)ndev, &f, &cnt);
-        bool ok = pk.xi->n == cnt && pk.xi2->n == cnt;
+        const ps_points *xi = lag ? pk.lxi : pk.xi, *xi2 = lag ? pk.lxi2 : pk.xi2, *xi_t = lag ? pk.lxi_t : pk.xi_t;
+        bool ok = xi->n == cnt && xi2->n == cnt;
         shard_range_c(n - 1, (int)d, (int)ndev, &f, &cnt);
-        ok = ok && pk.xi_t->n == cnt;
+        ok = ok && xi_t->n == cnt;
         shard_range_c(nn, (int)d, (int)ndev, &f, &cnt);
         ok = ok && pk.nio_lp->n == cnt;
         if (!ok || dev[d].qap->n != n || dev[d].qap->m != m || dev[d].sol->n != m)
             return fail(PS_ERR_LENGTH, "ps_groth16_prove_multi: device " + std::to_string(d) + " does not hold its index range of the CRS arrays");
     }
+    if (lag) return groth16_prove_multi_lagrange(dev, ndev, nn, r_be32, s_be32, A_out, B_out, C_out);
     // ---- quotient: A, B, h as big-endian scalars in host memory ----
     std::vector<uint8_t> hA, hB, hH;
     {
@@ -1323,28 +1372,7 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
             memcpy(pt.A, pa, 96);
             memcpy(pt.B, pb2, 192);
         }
-        if (!rc && d == 0) {
-            Fr rm = fr_mont_from_be32(r_be32), sm = fr_mont_from_be32(s_be32);
-            uint8_t one[32] = {0}, rs[32];
-            one[31] = 1;
-            fr_mont_to_be32(rs, fr_mul(rm, sm));
-            uint8_t pts3[3 * 96], sc3[96], fx[96], fx2[192], pts2[2 * 192], acc2[2 * 192];
-            memcpy(pts3, pk.delta, 96); memcpy(pts3 + 96, pk.alpha, 96);                       // A += r Delta + Alpha
-            memcpy(sc3, r_be32, 32); memcpy(sc3 + 32, one, 32);
-            rc = ps_points_lincomb(PS_G1, pts3, sc3, 2, fx);
-            memcpy(pts3, pt.A, 96); memcpy(pts3 + 96, fx, 96);
-            if (!rc) rc = ps_points_sum(PS_G1, pts3, 2, pt.A);
-            memcpy(pts2, pk.delta2, 192); memcpy(pts2 + 192, pk.beta2, 192);                     // B += s Delta2 + Beta2
-            memcpy(sc3, s_be32, 32); memcpy(sc3 + 32, one, 32);
-            if (!rc) rc = ps_points_lincomb(PS_G2, pts2, sc3, 2, fx2);
-            memcpy(acc2, pt.B, 192); memcpy(acc2 + 192, fx2, 192);
-            if (!rc) rc = ps_points_sum(PS_G2, acc2, 2, pt.B);
-            memcpy(pts3, pk.delta, 96); memcpy(pts3 + 96, pk.alpha, 96); memcpy(pts3 + 192, pk.beta, 96);  // C += rs Delta + s Alpha + r Beta
-            memcpy(sc3, rs, 32); memcpy(sc3 + 32, s_be32, 32); memcpy(sc3 + 64, r_be32, 32);
-            if (!rc) rc = ps_points_lincomb(PS_G1, pts3, sc3, 3, fx);
-            memcpy(pts3, pt.C, 96); memcpy(pts3 + 96, fx, 96);
-            if (!rc) rc = ps_points_sum(PS_G1, pts3, 2, pt.C);
-        }
+        if (!rc && d == 0) rc = g16_add_fixed_points(pk, r_be32, s_be32, pt.A, pt.B, pt.C);
         pt.rc = rc;
         if (rc) pt.err = g_last_error;
     };
@@ -1676,4 +1704,302 @@ extern "C" int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, p
         if (rc) return rc;
     }
     return PS_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Groth16Prove over rank-local LAGRANGE-form keys: ps_groth16_prove_multi (the devices of one process) and
+// ps_groth16_prove_local (one process per GPU).  With lxi / lxi2 in the key the scalars of A, B and B1' are the wire values
+// a_j = (L.s)_j, b_j = (R.s)_j, so a device that holds lxi[range] and lxi2[range] gets exactly the scalars it needs from its
+// OWN rows of the three sparse products (k_own_rows): those three sums need no exchange at all.  Only the n-1 values h(n+k)
+// depend on the whole circuit.  C's share is N + H + s A + r B1' as in the split form of groth16_prove_impl.
+// ---------------------------------------------------------------------------------------
+struct G16LocalShare {
+    const ps_points *lxi, *lxi2, *lxi_t, *nio_lp;  // this share's ranges of the key
+    const ps_qap* q;
+    const ps_scalars* sol;
+    int rank, world;
+    size_t nn;                    // len(NioLP) of the whole key
+    const ps_groth16_pk* fixed;   // the key whose fixed points this share adds, or nullptr
+};
+// Called once the own-row kernels are enqueued on the share's stream (the witness is in q->sol_m): whatever this device
+// contributes to the values route.
+typedef std::function<int(hipStream_t)> G16Produce;
+// Hands over S[0..2]: this share's range (ch values from node index fh on) of the three convolutions, in memory of this
+// device, valid for work enqueued on the stream afterwards.  May block the host until the convolutions exist.
+typedef std::function<int(hipStream_t, const Fr* S[3])> G16GetS;
+
+static int g16_lagrange_share(ps_ctx* c, const G16LocalShare& sh, const uint8_t* r_be32, const uint8_t* s_be32, const G16Produce& produce,
+                              const G16GetS& get_s, uint8_t* A_part, uint8_t* B_part, uint8_t* C_part) {
+    const ps_qap* q = sh.q;
+    const ps_scalars* sol = sh.sol;
+    const size_t n = q->n, diff = q->m - q->nio;
+    size_t fn, cn, fh, ch, fq, cq;
+    shard_range_c(n, sh.rank, sh.world, &fn, &cn);
+    shard_range_c(n - 1, sh.rank, sh.world, &fh, &ch);
+    shard_range_c(sh.nn, sh.rank, sh.world, &fq, &cq);
+    if (c->pending || (c->aux && c->aux->pending)) return fail(PS_ERR_ARG, "Groth16 share: an MSM is pending on this context");
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    int rc = PS_OK;
+    // window tables over the local arrays, once per array (lxi serves A and B1'); an int64 witness keeps its short-scalar
+    // plan over NioLP, which no table of full-width windows helps
+    for (const ps_points* arr : {sh.lxi2, sh.lxi, sh.lxi_t, sh.nio_lp})
+        if (!rc && tables_wanted(c, arr->n) && (arr != sh.nio_lp || sol->max_bits >= 255)) rc = points_ensure_table(c, arr, 0, true);
+    ps_scalars *va = nullptr, *vb = nullptr, *vh = nullptr, *sn = nullptr;  // the context's own vectors, and a view of the solution
+    if (!rc) rc = prover_vector(c, 0, cn, &va);
+    if (!rc) rc = prover_vector(c, 1, cn, &vb);
+    if (!rc) rc = prover_vector(c, 2, ch, &vh);
+    if (!rc && !c->ev_q && hipEventCreateWithFlags(&c->ev_q, hipEventDisableTiming) != hipSuccess) rc = fail(PS_ERR_HIP, "Groth16 share: event creation failed");
+    if (!rc) rc = ps_scalars_slice(sol, diff + fq, cq, &sn);
+    if (rc) { ps_scalars_free(sn); return rc; }
+    // the share's own kernels run on the context's high-priority stream, as the quotient of groth16_prove_impl does: the sums
+    // launched right behind them (worker contexts) must not hold back what every other device may be waiting for
+    hipStream_t qs = c->tail;
+    std::vector<int> fifo;  // sums pending on the context, oldest first: 0 B.lxi2, 1 A.lxi, 2 B1' = b.lxi, 3 sol.NioLP, 4 h.lxi_t
+    uint8_t part[5][192];
+    for (int k = 0; k < 5; k++) write_identity(k == 0 ? PS_G2 : PS_G1, part[k]);
+    int rcb = PS_OK;
+    auto t_h = t_start;
+    float h_ms = 0.f;
+    auto finish_one = [&]() {
+        const int kind = fifo.front();
+        fifo.erase(fifo.begin());
+        int r2 = ps_msm_finish(c, part[kind]);
+        if (r2 && !rcb) rcb = r2;
+        if (kind == 4) h_ms = phgr13_ms_since(t_h);
+    };
+    auto launch = [&](int kind, const ps_points* pts, const ps_scalars* sc) -> int {
+        while (fifo.size() + 1 > PS_PROVER_QUEUE) finish_one();  // the oldest sum is the furthest along
+        int r2 = msm_launch_impl(c, pts, sc, false);
+        if (!r2) fifo.push_back(kind);
+        return r2;
+    };
+    float own_ms = 0.f, wait_ms = 0.f;
+    do {
+        hipError_t e = hipEventRecord(c->ev_q, c->stream);  // ordered after whatever the caller left on the context stream
+        if (e == hipSuccess) e = hipStreamWaitEvent(qs, c->ev_q, 0);
+        if (e != hipSuccess || storage_wait_ready(sol->st, qs)) { rc = fail(PS_ERR_HIP, "Groth16 share: event wait failed"); break; }
+        // 1. the witness in Montgomery form, then a_j, b_j of the own rows, their gate check and their scalars in one pass
+        hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(q->m)), dim3(256), 0, qs, q->sol_m, scalars_ptr(sol), (u64)q->m);
+        e = hipMemsetAsync(c->d_flag, 0, 4, qs);
+        if (cn) {
+            Csr3 m3;
+            for (int k = 0; k < 3; k++) m3.m[k] = CsrView{q->mat[k].row_ptr, q->mat[k].col, q->mat[k].val};
+            u32 *a = (u32*)va->st->p, *b = (u32*)vb->st->p;
+            hipLaunchKernelGGL(k_own_rows, dim3(nblk(cn)), dim3(256), 0, qs, m3, (const Fr*)q->sol_m, (u32)fn, (u32)cn, a, b, c->d_flag);
+            // the part of the QAP's (global, ascending) list of long rows that lies in [fn, fn + cn)
+            const auto lo = std::lower_bound(q->long_any_h.begin(), q->long_any_h.end(), (u32)fn);
+            const auto hi = std::lower_bound(lo, q->long_any_h.end(), (u32)(fn + cn));
+            if (hi != lo)
+                hipLaunchKernelGGL(k_own_rows_long, dim3((unsigned)(hi - lo)), dim3(256), 0, qs, m3, (const Fr*)q->sol_m,
+                                   (const u32*)q->long_any + (lo - q->long_any_h.begin()), (u32)fn, a, b, c->d_flag);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { rc = fail(PS_ERR_HIP, std::string("Groth16 share: own rows: ") + hipGetErrorString(e)); break; }
+        if (storage_mark_ready(va->st, qs) || storage_mark_ready(vb->st, qs)) { rc = fail(PS_ERR_HIP, "event record failed"); break; }
+        if (produce && (rc = produce(qs))) break;
+        // 2. at once, without waiting for any h: B.lxi2 (G2, the longest point pass) first, A.lxi, B1' = b.lxi, then sol.NioLP
+        if ((rc = launch(0, sh.lxi2, vb)) || (rc = launch(1, sh.lxi, va)) || (rc = launch(2, sh.lxi, vb))) break;
+        u32 flag = 0;  // the gate check's answer for the own rows
+        if (hipMemcpyAsync(&flag, c->d_flag, 4, hipMemcpyDeviceToHost, qs) != hipSuccess || hipStreamSynchronize(qs) != hipSuccess) {
+            rc = fail(PS_ERR_HIP, "Groth16 share: reading the gate check failed");
+            break;
+        }
+        own_ms = phgr13_ms_since(t_start);
+        if (flag) { rc = fail(PS_ERR_NOT_DIVISIBLE, "apocalypse"); break; }  // qap.go:158-160
+        if ((rc = launch(3, sh.nio_lp, sn))) break;
+        // 3. h on the own range of nodes, from the three convolutions wherever they were computed, then h.lxi_t behind it
+        const auto t_wait = std::chrono::steady_clock::now();
+        if (ch) {
+            const Fr* S[3] = {nullptr, nullptr, nullptr};
+            if ((rc = get_s(qs, S))) break;
+            hipLaunchKernelGGL(k_h_values_range, dim3(nblk(ch)), dim3(256), 0, qs, (u32*)vh->st->p, S[0], S[1], S[2], (const Fr*)q->qt.fact2,
+                               (const Fr*)q->qt.invfact, (u64)n, (u64)fh, (u64)ch);
+            if (hipGetLastError() != hipSuccess) { rc = fail(PS_ERR_HIP, "Groth16 share: h on the own range failed"); break; }
+        }
+        if (storage_mark_ready(vh->st, qs)) { rc = fail(PS_ERR_HIP, "event record failed"); break; }
+        wait_ms = phgr13_ms_since(t_wait);
+        t_h = std::chrono::steady_clock::now();
+        if ((rc = launch(4, sh.lxi_t, vh))) break;
+    } while (0);
+    // everything that was launched is drained on every path: the next call on this context starts clean
+    while (!fifo.empty()) finish_one();
+    (void)hipStreamSynchronize(qs);
+    ps_scalars_free(sn);
+    if (rc || rcb) {
+        std::string keep = g_last_error;
+        (void)ps_ctx_sync(c);
+        g_last_error = keep;
+        return rc ? rc : rcb;
+    }
+    // C_part = N + H + s A_part + r B1'_part (groth16.go:180-205, the fixed points apart)
+    uint8_t two[2 * 96], sc2[64], w[96], three[3 * 96];
+    memcpy(two, part[1], 96); memcpy(two + 96, part[2], 96);
+    memcpy(sc2, s_be32, 32); memcpy(sc2 + 32, r_be32, 32);
+    rc = ps_points_lincomb(PS_G1, two, sc2, 2, w);
+    memcpy(three, part[3], 96); memcpy(three + 96, part[4], 96); memcpy(three + 192, w, 96);
+    if (!rc) rc = ps_points_sum(PS_G1, three, 3, C_part);
+    memcpy(A_part, part[1], 96);
+    memcpy(B_part, part[0], 192);
+    if (!rc && sh.fixed) rc = g16_add_fixed_points(*sh.fixed, r_be32, s_be32, A_part, B_part, C_part);
+    c->phase_ms[0] = own_ms + wait_ms;
+    c->phase_ms[1] = h_ms;
+    c->phase_ms[3] = phgr13_ms_since(t_start);
+    c->phase_ms[2] = std::max(0.f, c->phase_ms[3] - c->phase_ms[0] - c->phase_ms[1]);
+    return rc;
+}
+
+static int g16_local_key_check(const ps_groth16_pk& pk, const char* who) {
+    if (pk.lxi->group != PS_G1 || pk.lxi_t->group != PS_G1 || pk.nio_lp->group != PS_G1 || pk.lxi2->group != PS_G2)
+        return fail(PS_ERR_ARG, std::string(who) + ": CRS array in the wrong group");
+    return PS_OK;
+}
+
+// ps_groth16_prove_multi, every device with lxi / lxi2 / lxi_t (the caller has checked handles and ranges).  One host thread
+// per device runs g16_lagrange_share.  The values route -- three convolutions of length 2 np -- is split over devices 0, 1, 2
+// BY POLYNOMIAL (device k: the full sparse product of matrix k, its Lagrange weights, one convolution), not by node range: a
+// range of n / D outputs of a length-n convolution still needs a transform of >= n + n / D points, which rounds up to the same
+// 2 np, so a split by range saves nothing.  With fewer than three devices (or PS_G16_MULTI_HSPLIT=0) dev[0] runs all three as
+// the batch of quotient_h_values.  Either way an event is recorded behind each convolution; every device makes its stream
+// wait for the three events, copies its ranges of S_0, S_1, S_2 (3 x 40 bytes per node of its range) device to device into
+// buffers of its own QAP (coefA / coefB / coefC: idle on this route) and runs k_h_values_range.  No byte of A, B or h crosses
+// host memory, nothing is allocated once the contexts are warm.  The gate check is the union of the devices' own-row flags:
+// the first error of any device releases every device that waits, and every device drains what it launched.
+static int groth16_prove_multi_lagrange(const ps_groth16_device* dev, size_t ndev, size_t nn, const uint8_t* r_be32, const uint8_t* s_be32,
+                                        uint8_t* A_out, uint8_t* B_out, uint8_t* C_out) {
+    for (size_t d = 0; d < ndev; d++) {
+        int rc = g16_local_key_check(dev[d].pk, "ps_groth16_prove_multi");
+        if (rc) return rc;
+        for (size_t e = 0; e < d; e++)
+            if (dev[e].ctx == dev[d].ctx) return fail(PS_ERR_ARG, "ps_groth16_prove_multi: one context per device (a context appears twice)");
+    }
+    const size_t n = dev[0].qap->n;
+    const bool hsplit = ndev >= 3 && dev[0].ctx->g16_multi_hsplit;
+    struct {
+        std::mutex mu;
+        std::condition_variable cv;
+        int err = PS_OK;  // the first error of any device, and its text
+        std::string msg;
+        int have = 0;     // convolutions at hand (3: all)
+        const Fr* S[3] = {nullptr, nullptr, nullptr};
+        int sdev[3] = {0, 0, 0};
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    } ho;
+    auto fail_all = [&](int rc) {
+        std::lock_guard<std::mutex> lk(ho.mu);
+        if (!ho.err) { ho.err = rc; ho.msg = g_last_error; }
+        ho.cv.notify_all();
+    };
+    struct Part { uint8_t A[96], B[192], C[96]; };
+    std::vector<Part> parts(ndev);
+    auto work = [&](size_t d) {
+        ps_ctx* c = dev[d].ctx;
+        const ps_qap* q = dev[d].qap;
+        const ps_groth16_pk& pk = dev[d].pk;
+        size_t fh, ch;
+        shard_range_c(n - 1, (int)d, (int)ndev, &fh, &ch);
+        const G16LocalShare sh{pk.lxi, pk.lxi2, pk.lxi_t, pk.nio_lp, q, dev[d].sol, (int)d, (int)ndev, nn, d == 0 ? &dev[0].pk : nullptr};
+        // The values route ahead of the device's own sums (as the quotient of groth16_prove_impl runs first): every other
+        // device waits for it.  (Behind the sums instead: not measured yet.)
+        auto produce = [&](hipStream_t qs) -> int {
+            if (hsplit ? d >= 3 : d != 0) return PS_OK;
+            const NttTables& tabs = *ctx_tabs(c);
+            Fr* S[3] = {nullptr, nullptr, nullptr};
+            hipError_t e;
+            if (hsplit) {
+                spmv_launch(qs, q->mat[d], (const Fr*)q->sol_m, q->y[d], (u32)n);
+                e = quotient_h_conv_one(tabs, qs, q->qt, q->y[d], &S[d]);
+            } else {
+                for (int k = 0; k < 3; k++) spmv_launch(qs, q->mat[k], (const Fr*)q->sol_m, q->y[k], (u32)n);
+                e = quotient_h_convs(tabs, qs, q->qt, q->y[0], q->y[1], q->y[2], S);
+            }
+            if (e == hipSuccess) e = hipEventRecord(c->ev_q, qs);
+            if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_prove_multi: values route: ") + hipGetErrorString(e));
+            std::lock_guard<std::mutex> lk(ho.mu);
+            for (int k = 0; k < 3; k++)
+                if (S[k]) { ho.S[k] = S[k]; ho.sdev[k] = c->device; ho.ev[k] = c->ev_q; ho.have++; }
+            ho.cv.notify_all();
+            return PS_OK;
+        };
+        auto get_s = [&](hipStream_t qs, const Fr* out[3]) -> int {
+            const Fr* S[3];
+            int sdev[3];
+            hipEvent_t ev[3];
+            {
+                std::unique_lock<std::mutex> lk(ho.mu);
+                ho.cv.wait(lk, [&] { return ho.err != PS_OK || ho.have == 3; });
+                if (ho.err) return fail(ho.err, ho.msg);
+                for (int k = 0; k < 3; k++) { S[k] = ho.S[k]; sdev[k] = ho.sdev[k]; ev[k] = ho.ev[k]; }
+            }
+            Fr* dst[3] = {q->coefA, q->coefB, q->coefC};
+            for (int k = 0; k < 3; k++) {
+                HIP_TRY(hipStreamWaitEvent(qs, ev[k], 0));
+                const Fr* src = S[k] + (n - 1 + fh);  // S_P for hv[i] sits at n - 1 + i
+                if (sdev[k] == c->device) {
+                    HIP_TRY(hipMemcpyAsync(dst[k], src, sizeof(Fr) * ch, hipMemcpyDeviceToDevice, qs));
+                } else {
+                    peer_access_once(c->device, sdev[k]);
+                    HIP_TRY(hipMemcpyPeerAsync(dst[k], c->device, src, sdev[k], sizeof(Fr) * ch, qs));
+                }
+                out[k] = dst[k];
+            }
+            return PS_OK;
+        };
+        int rc = g16_lagrange_share(c, sh, r_be32, s_be32, produce, get_s, parts[d].A, parts[d].B, parts[d].C);
+        if (rc) fail_all(rc);
+    };
+    {
+        std::vector<std::future<void>> jobs;
+        for (size_t d = 1; d < ndev; d++) jobs.push_back(std::async(std::launch::async, work, d));
+        work(0);
+        for (auto& j : jobs) j.get();
+    }
+    if (ho.err) return fail(ho.err, ho.msg);
+    std::vector<uint8_t> fa(96 * ndev), fb(192 * ndev), fc(96 * ndev);
+    for (size_t d = 0; d < ndev; d++) {
+        memcpy(fa.data() + 96 * d, parts[d].A, 96);
+        memcpy(fb.data() + 192 * d, parts[d].B, 192);
+        memcpy(fc.data() + 96 * d, parts[d].C, 96);
+    }
+    int rc = ps_points_sum(PS_G1, fa.data(), ndev, A_out);
+    if (!rc) rc = ps_points_sum(PS_G2, fb.data(), ndev, B_out);
+    if (!rc) rc = ps_points_sum(PS_G1, fc.data(), ndev, C_out);
+    return rc;
+}
+
+// One rank's share when the rank holds ONLY its index ranges of a Lagrange-form key (one process per GPU).  Processes cannot
+// copy peer to peer, and the values route is 2 ms at 2^20 constraints: every rank computes it itself (with the gate check
+// over ALL rows, so every rank of an unsatisfied witness reports it) rather than wait for three broadcasts.
+extern "C" int ps_groth16_prove_local(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* q, const ps_scalars* sol, const uint8_t* r_be32,
+                                      const uint8_t* s_be32, int rank, int world, uint8_t* A_part, uint8_t* B_part, uint8_t* C_part) {
+    if (!c || !pk || !q || !sol || !r_be32 || !s_be32 || !A_part || !B_part || !C_part) return fail(PS_ERR_ARG, "ps_groth16_prove_local: NULL argument");
+    if (world < 1 || rank < 0 || rank >= world) return fail(PS_ERR_ARG, "ps_groth16_prove_local: bad rank / world");
+    if (!pk->nio_lp || !g16_lagrange(pk)) return fail(PS_ERR_ARG, "ps_groth16_prove_local: the key must carry lxi, lxi2 and lxi_t (and NioLP)");
+    int rc = g16_local_key_check(*pk, "ps_groth16_prove_local");
+    if (rc) return rc;
+    const size_t n = q->n, nn = q->nio;  // len(NioLP) = nbVars - diff = nbIO (groth16.go:86-91)
+    if (n < 2) return fail(PS_ERR_ARG, "ps_groth16_prove_local: needs at least 2 gates");
+    if (sol->n != q->m) return fail(PS_ERR_ARG, "different number of solution variables than left polynomials");  // sanityCheck
+    size_t f, cn, fh, ch, cq;
+    shard_range_c(n, rank, world, &f, &cn);
+    shard_range_c(n - 1, rank, world, &fh, &ch);
+    shard_range_c(nn, rank, world, &f, &cq);
+    if (pk->lxi->n != cn || pk->lxi2->n != cn || pk->lxi_t->n != ch || pk->nio_lp->n != cq)
+        return fail(PS_ERR_LENGTH, "ps_groth16_prove_local: rank " + std::to_string(rank) + " of " + std::to_string(world) +
+                                       " does not hold its index range of the CRS arrays");
+    Fr* S[3] = {nullptr, nullptr, nullptr};
+    auto produce = [&](hipStream_t qs) -> int {
+        for (int k = 0; k < 3; k++) spmv_launch(qs, q->mat[k], (const Fr*)q->sol_m, q->y[k], (u32)n);
+        hipLaunchKernelGGL(k_check_gates, dim3(nblk(n)), dim3(256), 0, qs, (const Fr*)q->y[0], (const Fr*)q->y[1], (const Fr*)q->y[2], (u32)n,
+                           c->d_flag);
+        hipError_t e = quotient_h_convs(*ctx_tabs(c), qs, q->qt, q->y[0], q->y[1], q->y[2], S);
+        if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_prove_local: values route: ") + hipGetErrorString(e));
+        return PS_OK;
+    };
+    auto get_s = [&](hipStream_t, const Fr* out[3]) -> int {
+        for (int k = 0; k < 3; k++) out[k] = S[k] + (n - 1 + fh);
+        return PS_OK;
+    };
+    const G16LocalShare sh{pk->lxi, pk->lxi2, pk->lxi_t, pk->nio_lp, q, sol, rank, world, nn, rank == world - 1 ? pk : nullptr};
+    return g16_lagrange_share(c, sh, r_be32, s_be32, produce, get_s, A_part, B_part, C_part);
 }

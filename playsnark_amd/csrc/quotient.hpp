@@ -282,6 +282,93 @@ __global__ void __launch_bounds__(256) k_h_values(Fr* __restrict__ hv, const Fr*
     Fr zs = fr_mul(fact[n + i], invfact[i]);
     hv[i] = fr_norm(fr_sub(fr_mul(fr_mul(zs, SA[idx]), SB[idx]), SC[idx]));
 }
+// ---- Groth16 over rank-local Lagrange-form keys: a device needs the wire values of ITS rows only ----
+// With lxi / lxi2 in the key the scalars of A, B and B1' are a_j = (L.s)_j and b_j = (R.s)_j themselves, so a device that
+// holds lxi[first, first + cnt) reads rows first .. first + cnt - 1 of the three matrices and nothing else: a_j, b_j, c_j, the
+// gate check a_j b_j == c_j (k_check_gates) and a_j, b_j as plain 8 x 32-bit scalars (k_fr_from_mont) in ONE pass -- no y[]
+// round trip (3 x 40 B written and 3 x 40 B read back per row) and no conversion launch.  The kernels are shaped by memory and
+// latency, not by multiplications: a row of an R1CS matrix has a handful of entries, each a dependent gather of 40 B from
+// the witness, so a thread per row with the three rows' loads independent of each other is what hides them; the scalars
+// leave as two 16-byte stores per value (a row of eight dwords per lane would be eight store instructions).
+struct CsrView { const u32* row_ptr; const u32* col; const Fr* val; };
+struct Csr3 { CsrView m[3]; };
+__device__ inline void fr_store_plain(u32* __restrict__ dst, const Fr& v) {  // dst 32-byte aligned
+    u32 w[8];
+    fr_to_words8(w, fr_from_mont(v));
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    d4[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    d4[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+__device__ inline Fr spmv_row(const CsrView& m, const Fr* __restrict__ x, u32 r) {  // k_spmv's sum, value for value
+    const u32 e0 = m.row_ptr[r], e1 = m.row_ptr[r + 1];
+    Fr acc = fr_zero();
+    for (u32 e = e0; e < e1; e++) {
+        acc = fr_norm(fr_add(acc, fr_mul(m.val[e], x[m.col[e]])));
+        if (((e - e0) & 31u) == 31u) acc = fr_reduce(acc);
+    }
+    return acc;
+}
+// rows first .. first + cnt - 1; a row that is long (more than SPMV_LONG_ROW entries) in ANY of the three matrices is left to
+// k_own_rows_long, whole
+__global__ void __launch_bounds__(256) k_own_rows(Csr3 m, const Fr* __restrict__ x, u32 first, u32 cnt, u32* __restrict__ a_out,
+                                                  u32* __restrict__ b_out, u32* __restrict__ flag) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= cnt) return;
+    const u32 r = first + t;
+    bool lng = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) lng = lng || m.m[k].row_ptr[r + 1] - m.m[k].row_ptr[r] > SPMV_LONG_ROW;
+    if (lng) return;
+    const Fr a = spmv_row(m.m[0], x, r), b = spmv_row(m.m[1], x, r), c = spmv_row(m.m[2], x, r);
+    if (!fr_is_zero(fr_sub(fr_mul(a, b), c))) atomicOr(flag, 1u);
+    fr_store_plain(a_out + 8 * (size_t)t, a);
+    fr_store_plain(b_out + 8 * (size_t)t, b);
+}
+// One workgroup per row of `rows` (the rows of the device's range that are long in any matrix: the QAP's list is global and
+// sorted, the host passes the part of it inside [first, first + cnt), so a long row outside the range costs nothing here and
+// one inside it is summed exactly once).  All three rows by the whole workgroup, short ones too.  Every sum ends with
+// k_spmv_long_rows's final fr_reduce: 256 reduced values add up to (-32 r, 288 r), the product brings the value back under
+// the bound of a stored vector before it meets fr_mul in the gate check.
+__global__ void __launch_bounds__(256) k_own_rows_long(Csr3 m, const Fr* __restrict__ x, const u32* __restrict__ rows, u32 first,
+                                                       u32* __restrict__ a_out, u32* __restrict__ b_out, u32* __restrict__ flag) {
+    __shared__ Fr sm[256];
+    const u32 r = rows[blockIdx.x];
+    Fr res[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {  // (unrolled: res[] stays in registers)
+        const CsrView& mk = m.m[k];
+        Fr acc = fr_zero();
+        u32 seen = 0;
+        for (u32 e = mk.row_ptr[r] + threadIdx.x; e < mk.row_ptr[r + 1]; e += blockDim.x) {
+            acc = fr_norm(fr_add(acc, fr_mul(mk.val[e], x[mk.col[e]])));
+            if ((++seen & 31u) == 0) acc = fr_reduce(acc);
+        }
+        sm[threadIdx.x] = fr_reduce(acc);
+        __syncthreads();
+        for (u32 stride = 128; stride > 0; stride >>= 1) {
+            if (threadIdx.x < stride) sm[threadIdx.x] = fr_norm(fr_add(sm[threadIdx.x], sm[threadIdx.x + stride]));
+            __syncthreads();
+        }
+        res[k] = fr_reduce(sm[0]);
+        __syncthreads();  // sm is the next matrix's
+    }
+    if (threadIdx.x != 0) return;
+    if (!fr_is_zero(fr_sub(fr_mul(res[0], res[1]), res[2]))) atomicOr(flag, 1u);
+    fr_store_plain(a_out + 8 * (size_t)(r - first), res[0]);
+    fr_store_plain(b_out + 8 * (size_t)(r - first), res[1]);
+}
+// k_h_values on the nodes first .. first + cnt - 1 of hv's index space, straight to plain scalars: out[t] = h(n + 1 + first + t)
+// from SA[t], SB[t], SC[t] = the entries n - 1 + first + t of the three convolutions -- ranges of cnt values each, which may
+// have been copied in from the devices that computed them.
+__global__ void __launch_bounds__(256) k_h_values_range(u32* __restrict__ out, const Fr* __restrict__ SA, const Fr* __restrict__ SB,
+                                                        const Fr* __restrict__ SC, const Fr* __restrict__ fact,
+                                                        const Fr* __restrict__ invfact, u64 n, u64 first, u64 cnt) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= cnt) return;
+    const u64 i = first + t;
+    const Fr zs = fr_mul(fact[n + i], invfact[i]);
+    fr_store_plain(out + 8 * t, fr_norm(fr_sub(fr_mul(fr_mul(zs, SA[t]), SB[t]), SC[t])));
+}
 // ---- trusted-setup helpers ----
 struct FrPow2Table { Fr p[32]; };  // p[k] = x^(2^k)
 // out[i] = shift * x^i  (GeneratePowersCommit's exponents, algebra.go:371-384)
@@ -448,12 +535,14 @@ static inline hipError_t interpolate2_on_1_to_n(const NttTables& tabs, hipStream
 // hv[k-1] = h(n+k), k = 1..n-1, into qt.scratch: three cyclic convolutions and one element-wise kernel.  These values
 // are all a prover needs of h when its key carries the Lagrange-form points of the nodes n+1..2n-1 (ps_groth16_pk.lxi_t,
 // ps_phgr13_ek.lgsi): h(x) G = sum_k h(n+k) lambda_k(x) G, no interpolation at all.
-static inline hipError_t quotient_h_values(const NttTables& tabs, hipStream_t st, const QapTables& qt, const Fr* yA, const Fr* yB,
-                                           const Fr* yC) {
+// The three convolutions alone: S[k] points at the cyclic convolution of polynomial k (S_P(i) for hv[i] at index n-1+i), in the
+// QAP's own buffers.  quotient_h_values below finishes with k_h_values; a prover whose devices each hold a range of the nodes
+// reads ranges of S[0..2] instead (k_h_values_range).
+static inline hipError_t quotient_h_convs(const NttTables& tabs, hipStream_t st, const QapTables& qt, const Fr* yA, const Fr* yB,
+                                          const Fr* yC, Fr* S[3]) {
     const u64 n = qt.n, L = 2 * qt.np;
-    if (n < 2) return hipSuccess;
     const Fr* ys[3] = {yA, yB, yC};
-    Fr* S[3] = {qt.t1, qt.pa, qt.pb};
+    S[0] = qt.t1; S[1] = qt.pa; S[2] = qt.pb;
     if (qt.s4 && qt.batch_h) {
         // Short transforms are latency: a 2^11-point transform is two workgroups walking eleven butterfly stages, ~40 us for
         // the forward and inverse pair whatever the chip could do beside it (kernel trace of Groth16Prove on 2^10 constraints:
@@ -470,6 +559,23 @@ static inline hipError_t quotient_h_values(const NttTables& tabs, hipStream_t st
         hipLaunchKernelGGL(k_lagrange_weights, dim3(nblk(L)), dim3(256), 0, st, S[k], ys[k], qt.invfact, n, L);
         QT_TRY(ntt_conv(tabs, st, S[k], L, qt.lognp + 1, NttFuse(), NttFuse(), qt.rhat));
     }
+    return hipGetLastError();
+}
+// ONE of the three convolutions (k = 0 left, 1 right, 2 out), not batched: what a device does that shares the values route
+// with two others (ps_groth16_prove_multi).  The result is in qt.t1.
+static inline hipError_t quotient_h_conv_one(const NttTables& tabs, hipStream_t st, const QapTables& qt, const Fr* y, Fr** S) {
+    const u64 L = 2 * qt.np;
+    *S = qt.t1;
+    hipLaunchKernelGGL(k_lagrange_weights, dim3(nblk(L)), dim3(256), 0, st, qt.t1, y, qt.invfact, qt.n, L);
+    QT_TRY(ntt_conv(tabs, st, qt.t1, L, qt.lognp + 1, NttFuse(), NttFuse(), qt.rhat));
+    return hipGetLastError();
+}
+static inline hipError_t quotient_h_values(const NttTables& tabs, hipStream_t st, const QapTables& qt, const Fr* yA, const Fr* yB,
+                                           const Fr* yC) {
+    const u64 n = qt.n;
+    if (n < 2) return hipSuccess;
+    Fr* S[3];
+    QT_TRY(quotient_h_convs(tabs, st, qt, yA, yB, yC, S));
     hipLaunchKernelGGL(k_h_values, dim3(nblk(n - 1)), dim3(256), 0, st, qt.scratch, (const Fr*)S[0], (const Fr*)S[1], (const Fr*)S[2],
                        (const Fr*)qt.fact2, (const Fr*)qt.invfact, n);
     return hipGetLastError();

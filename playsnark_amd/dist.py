@@ -179,7 +179,7 @@ class ShardedPHGR13:
 
 class ShardedGroth16:
     """Groth16Prove (groth16.go:122-211) with its three sums sharded over the ranks: ps_groth16_prove_shard
-    gives this rank's partial A, B, C (its index ranges of Xi, Xi2, NioLP, XiT; rank 0 also the fixed
+    gives this rank's partial A, B, C (its index ranges of Xi, Xi2, NioLP, XiT; the last rank also the fixed
     points); one all_gather of 96 + 192 + 96 bytes per rank and a local fold give every rank the proof."""
 
     def __init__(self, ctx, dist=None, world: int = 1, rank: int = 0):
@@ -242,7 +242,13 @@ class ShardedGroth16Local:
     test: Apocalypse), side by side; three broadcasts of 32 n bytes hand the vectors round and every rank keeps its
     ranges.  With fewer ranks each computes all three itself.  Sums per rank: B.Xi2 (G2), A.Xi, B.Xi, sol.NioLP, h.XiT over
     its ranges; C's share is N + H + s (A.Xi) + r (B.Xi) (two host scalar multiplications), rank 0 adds the fixed points;
-    one all_gather of 96 + 192 + 96 bytes and a local fold give every rank the proof -- the bytes of the unsharded prover."""
+    one all_gather of 96 + 192 + 96 bytes and a local fold give every rank the proof -- the bytes of the unsharded prover.
+
+    Which route runs: the one above when the local key has the monomial arrays alone.  A local key that carries LXi / LXi2 /
+    LXiT (its ranges of the Lagrange form; Xi / Xi2 / XiT may be None) goes through ps_groth16_prove_local instead: no
+    interpolation, no division and NO broadcast -- the scalars of A, B and B1' are the wire values of the rank's own rows,
+    h on the rank's nodes comes from the values route computed on the rank itself (2 ms at 2^20 constraints), and the
+    LAST rank adds the fixed points."""
 
     def __init__(self, ctx, dist=None, world: int = 1, rank: int = 0):
         self.ctx, self.dist, self.world, self.rank = ctx, dist, world, rank
@@ -276,6 +282,8 @@ class ShardedGroth16Local:
 
     def partials(self, tr_local: "api.Groth16Setup", q: "api.QAP", sol: "api.Poly", r: int, s: int, rank=None):
         rank = self.rank if rank is None else rank
+        if tr_local.LXi is not None and tr_local.LXi2 is not None and tr_local.LXiT is not None:
+            return api.Groth16ProveLocal(tr_local, q, sol, r, s, rank, self.world)
         ctx = self.ctx
         n, nn, diff = q.nbGates, q.nbIO, q.nbVars - q.nbIO  # len(NioLP) = nbVars - diff = nbIO (groth16.go:86-91)
         fq, cq = shard_range(nn, rank, self.world)

@@ -183,6 +183,24 @@ inline Groth16Proof Groth16ProveShard(Context& c, const ps_groth16_pk& tr, const
     return p;
 }
 
+// One rank's share when the rank holds ONLY its index ranges of a Lagrange-form key (tr_local: lxi / lxi2 / lxi_t / nio_lp cut
+// for (rank, world); ps_groth16_prove_local); the ranks' A, B, C add up to the proof, the last rank adds the fixed points
+inline Groth16Proof Groth16ProveLocal(Context& c, const ps_groth16_pk& tr_local, const QAP& q, const Poly& sol, const Scalar& r,
+                                      const Scalar& s, int rank, int world) {
+    Groth16Proof p{r, s, {}, {}, {}};
+    check(ps_groth16_prove_local(c.get(), &tr_local, q.get(), sol.get(), r.data(), s.data(), rank, world, p.A.data(), p.B.data(),
+                                 p.C.data()));
+    return p;
+}
+
+// Groth16Prove over the devices of this process, dev[d].pk holding only device d's index ranges (ps_groth16_prove_multi): with
+// lxi / lxi2 / lxi_t on every device the route without coefficient vectors, with the monomial arrays alone the other one
+inline Groth16Proof Groth16ProveMulti(const std::vector<ps_groth16_device>& dev, const Scalar& r, const Scalar& s) {
+    Groth16Proof p{r, s, {}, {}, {}};
+    check(ps_groth16_prove_multi(dev.data(), dev.size(), r.data(), s.data(), p.A.data(), p.B.data(), p.C.data()));
+    return p;
+}
+
 // func PHGR13Prove(ek PHGR13EvalKey, qap QAP, solution Vector) PHGR13Proof
 inline ps_phgr13_proof PHGR13Prove(Context& c, const ps_phgr13_ek& ek, const QAP& qap, const Poly& solution) {
     ps_phgr13_proof out;

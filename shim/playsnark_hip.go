@@ -630,8 +630,85 @@ func (hm *HipGroth16Multi) Free() {
 	}
 }
 
+// distributeDevicePoints cuts a device-resident array (on ctx `from`) by index range over the devices: device d gets
+// shardRange(len, d, ndev) as an array of its own (downloaded once in affine form, uploaded per device).
+func (hd *HipDevices) distributeDevicePoints(from *C.ps_ctx, src *C.ps_points) *HipShardedPoints {
+	n := int(C.ps_points_len(src))
+	group := C.ps_points_group(src)
+	wire := g1Wire
+	if group == C.PS_G2 {
+		wire = g2Wire
+	}
+	raw := make([]byte, wire*maxInt(n, 1))
+	check(func() C.int { return C.ps_points_download(from, src, 0, C.size_t(n), u8(raw)) })
+	sp := &HipShardedPoints{n: n}
+	for d, c := range hd.ctxs {
+		first, cnt := shardRange(n, d, len(hd.ctxs))
+		part := raw[first*wire : (first+cnt)*wire]
+		if cnt == 0 {
+			part = raw[:1] // never read: cnt is 0
+		}
+		var h *C.ps_points
+		cc := c
+		check(func() C.int { return C.ps_points_upload(cc, group, u8(part), C.size_t(cnt), C.PS_FMT_AFFINE, &h) })
+		sp.parts = append(sp.parts, h)
+	}
+	return sp
+}
+
+func maxInt(a, b int) int {
+	if a > b {
+		return a
+	}
+	return b
+}
+
+// UseLagrange puts the multi-device key onto the route without coefficient vectors: hs is the same key on ONE device with its
+// Lagrange form present (ToLagrange, or NewHipGroth16FromToxicWaste); its lxi, lxi2, lxi_t are cut by index range over the
+// devices and handed to ps_groth16_prove_multi as the optional arrays of every device's pk.  From then on a proof moves
+// 3 x 40 bytes per node of a device's range between devices and nothing through host memory (playsnark_hip.h).
+func (hm *HipGroth16Multi) UseLagrange(hs *HipGroth16) {
+	if hs.pk.lxi == nil || hs.pk.lxi2 == nil || hs.pk.lxi_t == nil {
+		panic("playsnark_hip: UseLagrange needs a key with its Lagrange form (HipGroth16.ToLagrange)")
+	}
+	lxi := hm.hd.distributeDevicePoints(hipCtx, hs.pk.lxi)
+	lxi2 := hm.hd.distributeDevicePoints(hipCtx, hs.pk.lxi2)
+	lxit := hm.hd.distributeDevicePoints(hipCtx, hs.pk.lxi_t)
+	hm.arrays = append(hm.arrays, lxi, lxi2, lxit)
+	for d := range hm.dev { // on every device or on none (PS_ERR_ARG otherwise)
+		pk := &hm.dev[d].pk
+		pk.lxi, pk.lxi2, pk.lxi_t = lxi.parts[d], lxi2.parts[d], lxit.parts[d]
+	}
+}
+
+// Groth16ProveHIPLocal is ONE rank's share of Groth16Prove when this process holds only its index ranges of a Lagrange-form
+// key (one process per GPU; ps_groth16_prove_local): pk has lxi / lxi2 / lxi_t / nio_lp cut for (rank, world) and the fixed
+// points, which the last rank adds.  The element-wise sum of all ranks' (A, B, C) is the proof of Groth16ProveHIP for the
+// same (r, s); the caller gathers and adds them (Commit.Add).
+func Groth16ProveHIPLocal(pk *C.ps_groth16_pk, qap *C.ps_qap, sol Vector, r, s Element, rank, world int) (Commit, Commit, Commit) {
+	rb, _ := r.MarshalBinary()
+	sb, _ := s.MarshalBinary()
+	vals := make([]C.int64_t, len(sol))
+	for i, v := range sol {
+		vals[i] = C.int64_t(v)
+	}
+	var vp *C.int64_t
+	if len(vals) > 0 {
+		vp = &vals[0]
+	}
+	var h *C.ps_scalars
+	check(func() C.int { return C.ps_scalars_upload_i64(hipCtx, vp, C.size_t(len(vals)), &h) })
+	defer C.ps_scalars_free(h)
+	A, B, Cc := make([]byte, g1Wire), make([]byte, g2Wire), make([]byte, g1Wire)
+	check(func() C.int {
+		return C.ps_groth16_prove_local(hipCtx, pk, qap, h, u8(rb), u8(sb), C.int(rank), C.int(world), u8(A), u8(B), u8(Cc))
+	})
+	return pointFrom(C.PS_G1, A, zeroG1), pointFrom(C.PS_G2, B, zeroG2), pointFrom(C.PS_G1, Cc, zeroG1)
+}
+
 // Groth16ProveHIPMulti is Groth16Prove (groth16.go:122-211) over the devices of this process: same proof bytes as
-// Groth16ProveHIP for the same (r, s).
+// Groth16ProveHIP for the same (r, s).  After UseLagrange the devices' pk carry lxi / lxi2 / lxi_t and the library takes the
+// route without interpolation, division or host staging.
 func Groth16ProveHIPMulti(hm *HipGroth16Multi, sol Vector) Groth16Proof {
 	r := NewElement().Pick(random.New())
 	s := NewElement().Pick(random.New())
