@@ -416,6 +416,30 @@ int ps_phgr13_verify(ps_ctx* ctx, const ps_phgr13_vk* vk, const ps_scalars* io, 
 int ps_pairing_equal(const uint8_t a1_g1[96], const uint8_t b1_g2[192], const uint8_t a2_g1[96], const uint8_t b2_g2[192],
                      int* equal);
 
+/* prod_i e(g1[i], g2[i]) == 1 ?  Miller loops and their product on the device, one final exponentiation on the host.
+ * Arrays of equal length (PS_ERR_LENGTH otherwise), n = 0 gives 1.  check != 0: both arrays go through
+ * ps_points_check_subgroup first (PS_ERR_ENCODING outside the subgroup); 0 for arrays the caller made itself.
+ * At most 2^24 pairs (PS_ERR_ARG beyond). */
+int ps_pairing_product_is_one(ps_ctx* ctx, const ps_points* g1, const ps_points* g2, int check, int* is_one);
+
+/* Groth16Verify (groth16.go:214-233) for nproofs proofs under ONE key, by random linear combination: for weights rho_i
+ *     prod_i e(rho_i A_i, B_i) * e(-(sum rho_i) alpha, beta2) * e(-X, gamma) * e(-sum rho_i C_i, delta2) == 1,
+ *     X = sum_j (sum_i rho_i io_ij) IoLP_j
+ * -- nproofs Miller loops on the device, ONE sum over IoLP, one over the C_i, three host Miller loops, one final
+ * exponentiation.  proofs: nproofs x (A 96 B || B 192 B || C 96 B), PS_FMT_AFFINE.  io: nproofs x diff scalars, proof-major
+ * (len(io) != nproofs * len(vk->io_lp): PS_ERR_LENGTH).  rho_be32: nproofs x 32 B, canonical (PS_ERR_ENCODING), non-zero
+ * (PS_ERR_ARG: a zero weight would skip a proof); drawn by the caller AFTER the proofs are fixed, as r and s are drawn
+ * by the caller elsewhere in this header; 128 random bits each are enough.
+ * *ok = 1 iff the combined equation holds: every proof valid => 1 for every rho; some proof invalid => 0 except with
+ * probability <= nproofs / 2^bits(rho) over the choice of rho.  Every point is untrusted, as in ps_groth16_verify
+ * (encoding, curve, subgroup: PS_ERR_ENCODING; ps_last_error() names the proof of a bad encoding).  nproofs = 0: *ok = 1.
+ * nproofs = 1 with rho = 1 is exactly ps_groth16_verify.  nproofs <= 2^24 (PS_ERR_ARG beyond).  Needs an empty MSM
+ * queue, like every one-call form.  The call costs ~50 ms up to ~1 000 proofs (subgroup tests, scaling and Miller loops
+ * are latency chains of one lane each): a lone proof is 14 times slower than ps_groth16_verify (49.7 against 3.6 ms), the
+ * batch wins from ~16 proofs on and is 155 times faster per proof at 4 096 (20 us; profiles/verify_batch.txt). */
+int ps_groth16_verify_batch(ps_ctx* ctx, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs, size_t nproofs,
+                            const uint8_t* rho_be32, int* ok);
+
 #ifdef __cplusplus
 }
 #endif

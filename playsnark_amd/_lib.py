@@ -30,6 +30,7 @@ SYMBOLS = [
     "ps_qap_create", "ps_qap_free", "ps_qap_quotient", "ps_qap_is_valid", "ps_qap_interpolate", "ps_poly_mul",
     "ps_points_lincomb", "ps_msm_multi_device", "ps_groth16_prove_multi", "ps_points_monomial_to_lagrange",
     "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_groth16_prove_local", "ps_phgr13_prove", "ps_phgr13_prove_shard", "ps_phgr13_prove_multi", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
+    "ps_pairing_product_is_one", "ps_groth16_verify_batch",
 ]
 
 
@@ -188,6 +189,8 @@ def _load():
     lib.ps_groth16_verify.argtypes = [vp, C.POINTER(Groth16Vk), vp, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
     lib.ps_phgr13_verify.argtypes = [vp, C.POINTER(Phgr13Vk), vp, C.POINTER(Phgr13Proof), C.POINTER(C.c_int)]
     lib.ps_pairing_equal.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
+    lib.ps_pairing_product_is_one.argtypes = [vp, vp, vp, i, C.POINTER(C.c_int)]
+    lib.ps_groth16_verify_batch.argtypes = [vp, C.POINTER(Groth16Vk), vp, C.c_char_p, sz, C.c_char_p, C.POINTER(C.c_int)]
     return lib
 
 

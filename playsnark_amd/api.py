@@ -723,6 +723,46 @@ def Groth16Verify(ctx: Context, Alpha: bytes, Beta2: bytes, Gamma: bytes, Delta2
     return bool(ok.value)
 
 
+def pairing_product_is_one(ctx: Context, g1: Points, g2: Points, check: bool = True) -> bool:
+    """prod_i e(g1[i], g2[i]) == 1: Miller loops and their product on the device, one final exponentiation on the host.
+    check=True sends both arrays through the subgroup test first (arrays from outside)."""
+    one = C.c_int(0)
+    _check(lib.ps_pairing_product_is_one(ctx._h, g1._h, g2._h, 1 if check else 0, C.byref(one)))
+    return bool(one.value)
+
+
+def Groth16VerifyBatch(ctx: Context, Alpha: bytes, Beta2: bytes, Gamma: bytes, Delta2: bytes, IoLP: Points, proofs: Sequence[Groth16Proof],
+                       ios: Sequence[Poly], rhos: Sequence[int], locate: bool = False):
+    """Groth16Verify (groth16.go:214) for many proofs under one key by a random linear combination with the weights `rhos`
+    (non-zero, below r, drawn AFTER the proofs are fixed; 128 random bits each are enough).  ios[i] are proof i's public
+    inputs (a Poly each, or ONE Poly of len(proofs) * len(IoLP) scalars, proof-major).  Returns the verdict; with locate=True
+    a rejected batch is checked proof by proof with Groth16Verify and the list of the bad indices is returned instead
+    (empty for an accepted batch)."""
+    vk = _lib.Groth16Vk()
+    for name, src in (("alpha", Alpha), ("beta2", Beta2), ("gamma", Gamma), ("delta2", Delta2)):
+        C.memmove(getattr(vk, name), src, len(src))
+    vk.io_lp = IoLP._h
+    n, diff = len(proofs), len(IoLP)
+    if isinstance(ios, Poly):
+        io = ios
+    else:
+        if len(ios) != n:
+            raise LengthMismatch(f"{len(ios)} public-input vectors for {n} proofs")
+        io = Poly.upload(ctx, b"".join(v.download_bytes() for v in ios))
+    raw = b"".join(bytes(p.A) + bytes(p.B) + bytes(p.C) for p in proofs)
+    if len(rhos) != n:
+        raise LengthMismatch(f"{len(rhos)} weights for {n} proofs")
+    rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
+    ok = C.c_int(0)
+    _check(lib.ps_groth16_verify_batch(ctx._h, C.byref(vk), io._h, raw, n, rho, C.byref(ok)))
+    if not locate:
+        return bool(ok.value)
+    if ok.value:
+        return []
+    return [i for i, p in enumerate(proofs)
+            if not Groth16Verify(ctx, Alpha, Beta2, Gamma, Delta2, IoLP, p, io.slice(i * diff, diff))]
+
+
 def PHGR13Verify(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, p: "PHGR13Proof", io: Poly) -> bool:
     """func PHGR13Verify(vk PHGR13VerifKey, qap QAP, p PHGR13Proof, io Vector) bool (pinochio.go:281).
     vk_points: av, aw, ay, gamma, bgamma, bgamma2, yts as affine bytes."""

@@ -88,6 +88,9 @@ struct ps_ctx {
     DevBuf counts, offs, bsum, keys, ranks, vals, sorted, buckets, parts, segs, wins, heavy, hparts, coarse;
     DevBuf affine_tmp;  // XYZZ points + chain products of k_batch_to_affine (fixed-base multiplications, window tables)
     DevBuf staging;                  // byte staging for uploads / downloads
+    DevBuf vb_f12, vb_xyzz, vb_rho, vb_cols;  // the batch verifier's workspaces (verify_batch.inc): Miller values, rho A, rho, column sums
+    float vb_ms[6] = {0, 0, 0, 0, 0, 0};  // stages of the last timed ps_groth16_verify_batch (ps_debug_verify_batch_stage_ms)
+    u32 simds = 0;                   // SIMDs of the device (how far k_miller_batch spreads a small batch), 0: not asked yet
     // ps_msm_be32 / ps_msm_i64 (seam S1: one upload per BlindEval call): the converted scalars of the call live in a vector
     // the context keeps, so a call does not pay a hipMalloc and a hipFree (which synchronises the device) of 32 bytes per
     // scalar on top of its copy over PCIe
@@ -280,7 +283,8 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->tail) (void)hipStreamSynchronize(c->tail);
     for (DevBuf* b : {&c->counts, &c->offs, &c->bsum, &c->keys, &c->ranks, &c->sorted, &c->buckets, &c->parts,
-                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->fb_table[0], &c->fb_table[1]})
+                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->fb_table[0], &c->fb_table[1],
+                      &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols})
         b->release();
     quotient_cache_free(c->qcache);
     if (c->up_scalars) ps_scalars_free(c->up_scalars);
@@ -1950,3 +1954,5 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "prove.inc"
 #include "lagrange.inc"
 #include "pairing.inc"
+#include "pairing_dev.hpp"
+#include "verify_batch.inc"

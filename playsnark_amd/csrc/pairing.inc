@@ -8,7 +8,8 @@
 // 2030-bit exponentiation it replaced stay there as the reference of tests/host_limb_check.cpp: 73 -> 11 ms for
 // ps_pairing_equal).  A handful of pairings per proof: CPU is the right
 // place (the IO MSMs -- size nbVars-nbIO because of the reference's `diff` convention -- go
-// through the GPU MSM).  Included by capi.hip; host code only.
+// through the GPU MSM).  MANY proofs under one key are another matter: verify_batch.inc runs their Miller loops on the
+// device (pairing_dev.hpp) and shares one final exponentiation.  Included by capi.hip; host code only.
 
 #define PS_HOSTFIELD 1
 #include "pairing_math.inc"

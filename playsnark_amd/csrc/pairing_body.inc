@@ -5,23 +5,23 @@
 struct Fp6 { Base2 c0, c1, c2; };
 struct Fp12 { Fp6 c0, c1; };
 
-static inline Base2 mul_xi(const Base2& a) {  // * (1 + u)
+PS_TOWER_HD static inline Base2 mul_xi(const Base2& a) {  // * (1 + u)
     return f_norm(Base2{f_sub(a.c0, a.c1), f_add(a.c0, a.c1)});
 }
-static inline Fp6 f6_add(const Fp6& a, const Fp6& b) { return Fp6{f_add(a.c0, b.c0), f_add(a.c1, b.c1), f_add(a.c2, b.c2)}; }
-static inline Fp6 f6_sub(const Fp6& a, const Fp6& b) { return Fp6{f_sub(a.c0, b.c0), f_sub(a.c1, b.c1), f_sub(a.c2, b.c2)}; }
-static inline Fp6 f6_neg(const Fp6& a) { return Fp6{f_neg(a.c0), f_neg(a.c1), f_neg(a.c2)}; }
-static inline Fp6 f6_norm(const Fp6& a) { return Fp6{f_norm(a.c0), f_norm(a.c1), f_norm(a.c2)}; }
-static inline Fp6 f6_zero() { Base2 z = f_zero((const Base2*)0); return Fp6{z, z, z}; }
-static inline Fp6 f6_one() { Base2 z = f_zero((const Base2*)0); return Fp6{f_one((const Base2*)0), z, z}; }
-static Fp6 f6_mul(const Fp6& a, const Fp6& b) {  // v^3 = xi
+PS_TOWER_HD static inline Fp6 f6_add(const Fp6& a, const Fp6& b) { return Fp6{f_add(a.c0, b.c0), f_add(a.c1, b.c1), f_add(a.c2, b.c2)}; }
+PS_TOWER_HD static inline Fp6 f6_sub(const Fp6& a, const Fp6& b) { return Fp6{f_sub(a.c0, b.c0), f_sub(a.c1, b.c1), f_sub(a.c2, b.c2)}; }
+PS_TOWER_HD static inline Fp6 f6_neg(const Fp6& a) { return Fp6{f_neg(a.c0), f_neg(a.c1), f_neg(a.c2)}; }
+PS_TOWER_HD static inline Fp6 f6_norm(const Fp6& a) { return Fp6{f_norm(a.c0), f_norm(a.c1), f_norm(a.c2)}; }
+PS_TOWER_HD static inline Fp6 f6_zero() { Base2 z = f_zero((const Base2*)0); return Fp6{z, z, z}; }
+PS_TOWER_HD static inline Fp6 f6_one() { Base2 z = f_zero((const Base2*)0); return Fp6{f_one((const Base2*)0), z, z}; }
+PS_TOWER_HD PS_TOWER_F6 static Fp6 f6_mul(const Fp6& a, const Fp6& b) {  // v^3 = xi
     Base2 a0b0 = f_mul(a.c0, b.c0), a1b1 = f_mul(a.c1, b.c1), a2b2 = f_mul(a.c2, b.c2);
     Base2 c0 = f_add(a0b0, mul_xi(f_norm(f_add(f_mul(a.c1, b.c2), f_mul(a.c2, b.c1)))));
     Base2 c1 = f_add(f_add(f_mul(a.c0, b.c1), f_mul(a.c1, b.c0)), mul_xi(a2b2));
     Base2 c2 = f_add(f_add(f_mul(a.c0, b.c2), a1b1), f_mul(a.c2, b.c0));
     return f6_norm(Fp6{c0, c1, c2});
 }
-static inline Fp6 f6_mul_v(const Fp6& a) { return Fp6{mul_xi(a.c2), a.c0, a.c1}; }
+PS_TOWER_HD static inline Fp6 f6_mul_v(const Fp6& a) { return Fp6{mul_xi(a.c2), a.c0, a.c1}; }
 static Fp6 f6_inv(const Fp6& a) {
     Base2 t0 = f_norm(f_sub(f_sqr(a.c0), mul_xi(f_mul(a.c1, a.c2))));
     Base2 t1 = f_norm(f_sub(mul_xi(f_sqr(a.c2)), f_mul(a.c0, a.c1)));
@@ -30,8 +30,8 @@ static Fp6 f6_inv(const Fp6& a) {
     Base2 di = f_inv(d);
     return Fp6{f_mul(t0, di), f_mul(t1, di), f_mul(t2, di)};
 }
-static inline Fp12 f12_one() { return Fp12{f6_one(), f6_zero()}; }
-static Fp12 f12_mul(const Fp12& a, const Fp12& b) {  // w^2 = v
+PS_TOWER_HD static inline Fp12 f12_one() { return Fp12{f6_one(), f6_zero()}; }
+PS_TOWER_HD static Fp12 f12_mul(const Fp12& a, const Fp12& b) {  // w^2 = v
     Fp6 t0 = f6_mul(a.c0, b.c0), t1 = f6_mul(a.c1, b.c1);
     Fp6 c0 = f6_norm(f6_add(t0, f6_mul_v(t1)));
     Fp6 c1 = f6_norm(f6_add(f6_mul(a.c0, b.c1), f6_mul(a.c1, b.c0)));
@@ -106,27 +106,27 @@ static Fp12 final_exp_generic(const Fp12& f) {
 
 // ---- the fast path: inversion-free Miller loop, sparse line products, final exponentiation by the x-chain ----
 // (a0 + a1 w)^2 = (a0^2 + v a1^2) + 2 a0 a1 w, two Fp6 products
-static Fp12 f12_sqr(const Fp12& a) {
+PS_TOWER_HD static Fp12 f12_sqr(const Fp12& a) {
     Fp6 t = f6_mul(a.c0, a.c1);
     Fp6 s = f6_mul(f6_norm(f6_add(a.c0, a.c1)), f6_norm(f6_add(a.c0, f6_mul_v(a.c1))));
     Fp6 c0 = f6_norm(f6_sub(f6_sub(s, t), f6_mul_v(t)));
     return Fp12{c0, f6_norm(f6_add(t, t))};
 }
 // x * (a + b v) and x * (c v) in Fp6
-static Fp6 f6_mul_01(const Fp6& x, const Base2& a, const Base2& b) {
+PS_TOWER_HD PS_TOWER_F6 static Fp6 f6_mul_01(const Fp6& x, const Base2& a, const Base2& b) {
     Base2 c0 = f_add(f_mul(x.c0, a), mul_xi(f_mul(x.c2, b)));
     Base2 c1 = f_add(f_mul(x.c0, b), f_mul(x.c1, a));
     Base2 c2 = f_add(f_mul(x.c1, b), f_mul(x.c2, a));
     return f6_norm(Fp6{c0, c1, c2});
 }
-static Fp6 f6_mul_1(const Fp6& x, const Base2& c) { return Fp6{mul_xi(f_mul(x.c2, c)), f_mul(x.c0, c), f_mul(x.c1, c)}; }
+PS_TOWER_HD static Fp6 f6_mul_1(const Fp6& x, const Base2& c) { return Fp6{mul_xi(f_mul(x.c2, c)), f_mul(x.c0, c), f_mul(x.c1, c)}; }
 // f * (a + b w^2 + c w^3): the shape of a line value (w^2 = v, w^3 = v w): 15 Base2 products instead of 18
-static Fp12 f12_mul_line(const Fp12& f, const Base2& a, const Base2& b, const Base2& c) {
+PS_TOWER_HD static Fp12 f12_mul_line(const Fp12& f, const Base2& a, const Base2& b, const Base2& c) {
     Fp6 t0 = f6_mul_01(f.c0, a, b), t1 = f6_mul_1(f.c1, c);
     Fp6 m = f6_mul_01(f6_norm(f6_add(f.c0, f.c1)), a, f_norm(f_add(b, c)));
     return Fp12{f6_norm(f6_add(t0, f6_mul_v(t1))), f6_norm(f6_sub(f6_sub(m, t0), t1))};
 }
-static inline Base2 f2_scale(const Base2& a, const Base& k) { return Base2{f_mul(f_norm(a.c0), k), f_mul(f_norm(a.c1), k)}; }
+PS_TOWER_HD static inline Base2 f2_scale(const Base2& a, const Base& k) { return Base2{f_mul(f_norm(a.c0), k), f_mul(f_norm(a.c1), k)}; }
 
 // Running point T = (X : Y : Z) on the twist, x = X/Z, y = Y/Z.  A line value may be scaled by any non-zero element of
 // Base2 (the final exponentiation kills proper subfields), so with the slope lam = N / D the affine line
@@ -134,7 +134,7 @@ static inline Base2 f2_scale(const Base2& a, const Base& k) { return Base2{f_mul
 // D = 2 Y Z) and (u x_Q - v y_Q) - u x_P w^2 + v y_P w^3 for an addition of the affine Q (u = y_Q Z - Y, v = x_Q Z - X).
 // Point formulas: dbl-2007-bl (a = 0) and madd-1998-cmo.  Every stored coordinate is a product or a short sum of
 // products, so the lazy limbs stay bounded without re-canonicalising.
-static Fp12 miller(const Affine<Base>& P, const Affine<Base2>& Q) {
+PS_TOWER_HD static Fp12 miller(const Affine<Base>& P, const Affine<Base2>& Q) {
     if (affine_is_identity<Base>(P) || affine_is_identity<Base2>(Q)) return f12_one();
     Fp12 f = f12_one();
     Base2 X = Q.x, Y = Q.y, Z = f_one((const Base2*)0);

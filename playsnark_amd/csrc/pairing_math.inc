@@ -14,7 +14,22 @@ static inline Fp canon_wide(const Fp& a) {
 }
 static inline Fp2 canon_wide(const Fp2& a) { return Fp2{canon_wide(a.c0), canon_wide(a.c1)}; }
 
+// This instance is also what the batch verifier's kernels run (pairing_dev.hpp): the tower functions the projective
+// miller() and f12_mul() are made of compile for the device too.  Empty on a host-only build and for the Fq instance.
+// PS_MILLER_F6_CALL: the Fp6 products of the tower as out-of-line device functions (operands and results through the
+// lane's private memory) instead of inlined over registers -- the A/B of k_miller_batch's layout (pairing_dev.hpp).
+#ifndef PS_MILLER_F6_CALL
+#define PS_MILLER_F6_CALL 0
+#endif
+#define PS_TOWER_HD PS_HD
+#if defined(__HIP_DEVICE_COMPILE__) && PS_MILLER_F6_CALL
+#define PS_TOWER_F6 __attribute__((noinline))
+#else
+#define PS_TOWER_F6
+#endif
 #include "pairing_body.inc"
+#undef PS_TOWER_HD
+#undef PS_TOWER_F6
 }  // namespace pairing_dev
 
 #if defined(PS_HOSTFIELD)
@@ -23,6 +38,10 @@ typedef Fq Base;
 typedef Fq2 Base2;
 static inline Fq canon_wide(const Fq& a) { return a; }  // always reduced
 static inline Fq2 canon_wide(const Fq2& a) { return a; }
+#define PS_TOWER_HD
+#define PS_TOWER_F6
 #include "pairing_body.inc"
+#undef PS_TOWER_HD
+#undef PS_TOWER_F6
 }  // namespace pairing
 #endif

@@ -229,6 +229,20 @@ inline bool Groth16Verify(Context& c, const ps_groth16_vk& vk, const Groth16Proo
     check(ps_groth16_verify(c.get(), &vk, io.get(), p.A.data(), p.B.data(), p.C.data(), &ok));
     return ok != 0;
 }
+// prod_i e(g1[i], g2[i]) == 1, Miller loops and their product on the device (check: subgroup tests first)
+inline bool pairing_product_is_one(Context& c, const ps_points* g1, const ps_points* g2, bool check_subgroup = true) {
+    int one = 0;
+    check(ps_pairing_product_is_one(c.get(), g1, g2, check_subgroup ? 1 : 0, &one));
+    return one != 0;
+}
+// Groth16Verify for nproofs proofs under one key by a random linear combination: proofs = nproofs x (A || B || C), io =
+// nproofs x diff scalars (proof-major), rho_be32 = nproofs x 32 bytes drawn after the proofs are fixed
+inline bool Groth16VerifyBatch(Context& c, const ps_groth16_vk& vk, const Poly& io, const uint8_t* proofs, size_t nproofs,
+                               const uint8_t* rho_be32) {
+    int ok = 0;
+    check(ps_groth16_verify_batch(c.get(), &vk, io.get(), proofs, nproofs, rho_be32, &ok));
+    return ok != 0;
+}
 // func PHGR13Verify(vk PHGR13VerifKey, qap QAP, p PHGR13Proof, io Vector) bool (pinochio.go:281)
 inline bool PHGR13Verify(Context& c, const ps_phgr13_vk& vk, const ps_phgr13_proof& p, const Poly& io) {
     int ok = 0;

@@ -468,6 +468,39 @@ func Groth16VerifyHIP(hs *HipGroth16, p Groth16Proof, io Vector) bool {
 	return ok != 0
 }
 
+// Groth16VerifyBatchHIP checks many proofs under one key with ONE final exponentiation (ps_groth16_verify_batch): the
+// weights of the random linear combination are drawn here, after the proofs are in hand, 128 bits each.
+func Groth16VerifyBatchHIP(hs *HipGroth16, proofs []Groth16Proof, ios []Vector) bool {
+	if len(proofs) != len(ios) {
+		panic("Groth16VerifyBatchHIP: one public-input vector per proof")
+	}
+	if len(proofs) == 0 {
+		return true
+	}
+	var all Vector
+	raw := make([]byte, 0, 384*len(proofs))
+	rho := make([]byte, 32*len(proofs))
+	for i, p := range proofs {
+		all = append(all, ios[i]...)
+		raw = append(raw, affineOf(C.PS_G1, p.A)...)
+		raw = append(raw, affineOf(C.PS_G2, p.B)...)
+		raw = append(raw, affineOf(C.PS_G1, p.C)...)
+		for zero := true; zero; { // 128 random bits, drawn again in the (2^-128) case that they are all zero
+			random.Bytes(rho[32*i+16:32*i+32], random.New())
+			for _, b := range rho[32*i+16 : 32*i+32] {
+				zero = zero && b == 0
+			}
+		}
+	}
+	dio := uploadSolution(all)
+	defer C.ps_scalars_free(dio)
+	var ok C.int
+	call(func() C.int {
+		return C.ps_groth16_verify_batch(hipCtx, &hs.vk, dio, u8(raw), C.size_t(len(proofs)), u8(rho), &ok)
+	})
+	return ok != 0
+}
+
 // ---------------------------------------------------------------------------------------
 // Several GPUs from ONE process (a cgo caller cannot wrap a function call in one process per GPU, which is how
 // bench.py and playsnark_amd/dist.py scale): ps_msm_multi_device and ps_groth16_prove_multi run one context per
