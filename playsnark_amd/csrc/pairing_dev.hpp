@@ -1,6 +1,8 @@
 // Device side of the batch verifier (verify_batch.inc): Miller loops of many pairs at once, the product of their
 // values, and the weighted column sums of the public inputs.  Included by capi.hip after pairing.inc, and -- its PS_HD
 // helpers only -- by tests/host_pairing_batch_check.cpp, which drives them on the host with the lanes emulated by a loop.
+// tests/device_pairing_check.hip includes it whole and launches these kernels on the device, any lane layout, next to the
+// same functions compiled for the host (tests/test_device_pairing.py: every value against Python integers).
 // Needs pairing_math.inc (namespace pairing_dev: the tower over Fp / Fp2) in scope.
 //
 // Layout: ONE Miller loop per lane, the tower in plain C++ over field.hpp (pairing_body.inc's projective miller(): no

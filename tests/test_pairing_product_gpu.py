@@ -104,3 +104,35 @@ def test_errors(ps_api, ctx, co, pr, off_subgroup):
     with pytest.raises(ps_api.PlaysnarkError) as e:  # the groups the wrong way round
         ps_api.pairing_product_is_one(ctx, ok2, ok1)
     assert e.value.code == _lib.PS_ERR_ARG
+
+
+def _device_simds():
+    """SIMDs of device 0 (four per compute unit on CDNA, as verify_batch.inc counts them), asked in a child process"""
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                         capture_output=True, text=True, timeout=300, check=True).stdout
+    return 4 * int(out.split()[-1])
+
+
+def _spread_lanes(n, simds):  # pairing_dev.hpp, restated
+    return min(64, max(1, -(-n // max(simds, 1))))
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["full-waves", "ragged-last-wave"])
+def test_full_waves_and_a_ragged_last_wave(ps_api, ctx, pr, ragged):
+    """65 536 pairs fill every lane of 1 024 waves on 1 024 SIMDs, 70 001 leave a last wave of 49: the only shapes where
+    k_miller_batch runs lpw = 64 through the API.  The device's SIMD count is read, and n grows with it."""
+    simds = _device_simds()
+    n = max(65536, 64 * simds) + (4465 if ragged else 0)
+    assert _spread_lanes(n, simds) == 64 and (n % 64 != 0) == ragged
+    a, b, free = _scalars(pr, n, 7000 + ragged)
+    assert free[-1] == n - 1
+    g1, g2 = _upload(ps_api, ctx, a, b)
+    assert ps_api.pairing_product_is_one(ctx, g1, g2, check=False) is True
+    last_wave = range((n - 1) // 64 * 64, n)
+    k = last_wave[len(last_wave) // 2]  # one pair of the last wave
+    a[k] = (a[k] + 1) % pr.R
+    g1, g2 = _upload(ps_api, ctx, a, b)
+    assert ps_api.pairing_product_is_one(ctx, g1, g2, check=False) is False

@@ -220,3 +220,60 @@ def test_two_threads_two_contexts_one_key(ps_api, co, pr, mat):
         t.join()
     assert not errors, errors
     assert results[0] == results[1] == [True, False] * 3
+
+
+def test_three_passes_of_column_sums(ps_api, ctx, pr, mat):
+    """N = 5 000: weighted_columns (verify_batch.inc) sums 5 000 rows in 79 chunks, those in 2, those in 1 -- three passes,
+    where 300 proofs take two.  The 300 proofs repeated, fresh non-zero weights."""
+    n = 5000
+    rng = pr.SplitMix64(SEED + 5000)
+    proofs = [mat.proofs[i % vc.NPROOFS] for i in range(n)]
+    ios = [list(mat.ios[i % vc.NPROOFS]) for i in range(n)]
+    per = lambda r: max(64, -(-r // max(1, min(4096, -(-65536 // mat.diff)))))
+    chunks = [n]
+    while chunks[-1] > 1:
+        chunks.append(-(-chunks[-1] // per(chunks[-1])))
+    assert chunks == [5000, 79, 2, 1]
+    rhos = _rhos(pr, rng, n, 128)
+    assert all(0 < v < pr.R for v in rhos)
+    assert _batch(ps_api, ctx, mat, proofs, ios, rhos) is True
+    ios[n - 1][1] = (ios[n - 1][1] + 1) % pr.R
+    assert _batch(ps_api, ctx, mat, proofs, ios, rhos) is False
+    assert _batch(ps_api, ctx, mat, proofs, ios, rhos, locate=True) == [n - 1]
+
+
+def test_more_than_256_public_inputs(ps_api, ctx, co, pr):
+    """A 300-gate circuit has 299 public inputs in the reference's convention (nbVars - nbIO): k_fr_weighted_columns runs
+    with two grid columns (blockIdx.x > 0).  130 proofs made by Groth16Prove; proof 0 also goes through Groth16Verify and,
+    live, through oracle.pairing.groth16_verify."""
+    from oracle import pairing as pg
+    from oracle import restate as rs
+
+    n, gates = 130, 300
+    rng = pr.SplitMix64(SEED + 300)
+    circuits = [rs.synthetic_circuit(gates, x0) for x0 in (3, 4)]
+    c, sols = circuits[0][0], [s for _, s in circuits]
+    diff = c.nbVars - c.nbIO
+    assert diff > 256
+    tr = rs.groth16_setup(c, *[rng.fr() for _ in range(5)])
+    up = lambda g, b: ps_api.Points.upload(ctx, g, b)
+    q = ps_api.QAP(ctx, c.nbVars, c.nbIO, c.left, c.right, c.out)
+    pk = ps_api.Groth16Setup(tr.Alpha, tr.Beta, tr.Delta, tr.Beta2, tr.Delta2, up(ps_api.G1, tr.Xi), up(ps_api.G2, tr.Xi2),
+                             up(ps_api.G1, tr.NioLP), up(ps_api.G1, tr.XiT))
+    dsols = [ps_api.Poly.upload(ctx, s) for s in sols]
+    proofs = [ps_api.Groth16Prove(pk, q, dsols[i % 2], rng.fr(), rng.fr()) for i in range(n)]
+    ios = [sols[i % 2][:diff] for i in range(n)]
+    iolp = up(ps_api.G1, tr.IoLP)
+    assert len(iolp) == diff
+    rhos = _rhos(pr, rng, n, 128)
+    batch = lambda pub, **kw: ps_api.Groth16VerifyBatch(ctx, tr.Alpha, tr.Beta2, tr.Gamma, tr.Delta2, iolp, proofs, _io(ps_api, ctx, pub), rhos, **kw)
+    assert batch(ios) is True
+    assert ps_api.Groth16Verify(ctx, tr.Alpha, tr.Beta2, tr.Gamma, tr.Delta2, iolp, proofs[0], ps_api.Poly.upload(ctx, ios[0])) is True
+    trp = rs.Bag(Alpha=co.G1.from_b(tr.Alpha), Beta2=co.G2.from_b(tr.Beta2), IoLP=co.G1.unpack(tr.IoLP), Gamma=co.G2.from_b(tr.Gamma),
+                 Delta2=co.G2.from_b(tr.Delta2))
+    p = proofs[0]
+    assert pg.groth16_verify(trp, co.G1.from_b(p.A), co.G2.from_b(p.B), co.G1.from_b(p.C), ios[0]) is True
+    # a public input in the second grid column (j >= 256) of the last proof
+    bad = [list(v) for v in ios]
+    bad[n - 1][diff - 1] = (bad[n - 1][diff - 1] + 1) % pr.R
+    assert batch(bad) is False
