@@ -1186,8 +1186,17 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     const u32 qlpb = qfix ? std::min<u32>((u32)pl.lpb, 256 / QTraits<KF>::GL) : 0;
     const u64 heavy_slices = qfix ? std::min<u64>(HEAVY_SPAN, (u64)QFIX_HEAVY * qlpb - 1) : HEAVY_SPAN;
     const size_t max_heavy = (size_t)(total / (heavy_slices * (u64)pl.M)) + 2;
-    // heavy: [count][bucket list: max_heavy][job_base: max_heavy + 1]; hparts: one point per job
-    if ((rc = wc->heavy.ensure(4 * (2 * max_heavy + 2)))) return rc;
+    // the long sums' fix-up in three kernels (msm.hpp section 5).  Short sums with too many buckets for a quad each keep the
+    // one-lane fix-up in ONE kernel: they are bound by the number of their launches, not by lane-time.
+#if defined(PS_FIXUP_ONE_KERNEL)
+    const bool split_fixup = false;
+#else
+    const bool split_fixup = !pl.shortsum;
+#endif
+    // a bucket on chain_list holds a whole slice of its own and shares the slices at its ends with at most one other each
+    const size_t max_chain = split_fixup ? (size_t)nthreads_acc / 2 + 2 : 0;
+    // heavy: [heavy count][chain count][heavy list: max_heavy][job_base: max_heavy + 1][chain list: max_chain]; hparts: one point per job
+    if ((rc = wc->heavy.ensure(4 * (2 * max_heavy + 3 + max_chain)))) return rc;
     const u32 heavy_npb = 256 / QTraits<KF>::GL;  // a job is at least one block's worth of slices (heavy_chunk_of)
     const size_t max_jobs = (size_t)nthreads_acc / heavy_npb + max_heavy + 1;
     if ((rc = wc->hparts.ensure(sizeof(Xyzz<F>) * max_jobs))) return rc;
@@ -1214,14 +1223,28 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
         // quads of a bucket must fit THIS group's 256-thread block (64 G1 points, 32 G2 points)
         const u32 lpb = qlpb;
         hipLaunchKernelGGL(k_qfixup<KF>, dim3(nblocks(G * (u64)lpb * QTraits<KF>::GL)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M,
-                           nthreads_acc, lpb, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 1);
+                           nthreads_acc, lpb, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2);
+    } else if (split_fixup) {
+        u32* ccount = (u32*)wc->heavy.p + 1;
+        u32* clist = (u32*)wc->heavy.p + 2 + 2 * max_heavy + 1;
+        hipLaunchKernelGGL(k_fixup_classify<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
+                           (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2, ccount, clist);
+        if (nthreads_acc > 1)  // one logical thread per slice boundary
+            hipLaunchKernelGGL(k_fixup_pair<KF>, dim3(nblocks((size_t)(nthreads_acc - 1) * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G,
+                               pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p);
+        // a quad per listed bucket; the list's length stays on the device, so the grid is that of the longest list, within
+        // one round of blocks
+        constexpr u32 chain_npb = 256 / QTraits<KF>::GL;
+        hipLaunchKernelGGL(k_qfixup_chain<KF>, dim3((unsigned)std::min<size_t>((max_chain + chain_npb - 1) / chain_npb, 512)), dim3(256), 0, st,
+                           (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p,
+                           (const u32*)ccount, (const u32*)clist);
     } else
     hipLaunchKernelGGL(k_fixup<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
-                       (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 1);
+                       (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2);
     {
         const u32* hcount = (const u32*)wc->heavy.p;
-        const u32* hlist = hcount + 1;
-        u32* job_base = (u32*)wc->heavy.p + 1 + max_heavy;
+        const u32* hlist = hcount + 2;
+        u32* job_base = (u32*)wc->heavy.p + 2 + max_heavy;
         hipLaunchKernelGGL(k_heavy_jobs, dim3(1), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, hcount, hlist, job_base, heavy_npb);
         // two levels of quad trees for every plan (qtail.hpp): the one-lane kernels of rounds 1-2 (jobs of 1024 slices, strided
         // chains, an 8-level LDS tree of 14-36 us additions) took 0.43 ms for the 2^19 ones of a boolean witness at 2^20 points

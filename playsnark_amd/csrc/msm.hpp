@@ -13,7 +13,8 @@
 //                   witness vectors, repeated scalars) -- and walks it with an XYZZ accumulator,
 //                   flushing whenever the bucket id changes.  Buckets that lie inside one slice
 //                   are final; runs cut by a slice boundary go to a head/tail partial slot.
-//   5 k_fixup       per bucket: add up the partial slots of the slices it spans
+//   5 k_fixup_classify / k_fixup_pair / k_qfixup_chain   add up the partial slots of the buckets a slice boundary cuts
+//                   (short sums: k_qfixup, or k_fixup in one kernel)
 //   6 k_reduce_l1/pyr/sum/fin  per bucket set  sum_b (b+1)*B[b]: 8-bucket running sums, then sums by the bits of the
 //     segment index; their weights 2^k are applied on the host
 //   host            the weights of the reduction's partial results, Horner over the W window sums (c doublings each)
@@ -24,6 +25,7 @@
 // digit kernel's stores are coalesced across scalars; buckets and partials AoS XYZZ.
 #pragma once
 #include "curve.hpp"
+#include "fixup_class.hpp"
 
 namespace ps {
 
@@ -810,19 +812,7 @@ __device__ inline void block_tree_sum(Xyzz<typename FieldTraits<KF>::Store>* sm,
 // ---------------------------------------------------------------------------------------
 // 4. bucket accumulation over fixed slices of the sorted entry list
 // ---------------------------------------------------------------------------------------
-// Slice length a sum actually uses.  The plan is made before the sort has run, for W digits per scalar; a witness of bits or
-// small values leaves one digit per scalar, and 2^19 entries in slices of 32 are 256 waves on a chip that holds 2 048 (the
-// accumulation of Groth16's A over 2^20 booleanity gates: 0.46-0.60 ms for 0.06 ms of work).  So every kernel that walks the
-// slices derives their length from the length of the sorted list E = offs[G], the planned slice count T and the planned M:
-// M again as soon as the list is a quarter of the plan, shorter below, never under 4 (or a shorter planned M).
-__device__ inline int eff_slice(u32 E, u32 T, int M) {
-#if defined(PS_NO_EFF_SLICE)  // measurement builds: the planned length throughout
-    return M;
-#endif
-    const u64 m = (4ull * E + T - 1) / (T ? T : 1u);
-    const u64 lo = M < 4 ? (u64)M : 4ull;
-    return m >= (u64)M ? M : (int)(m < lo ? lo : m);
-}
+// (eff_slice, the slice length a sum actually uses, is in fixup_class.hpp with the rest of the slice arithmetic.)
 
 template <class F>
 PS_INL bool affine_is_identity(const Affine<F>& p) { return fp_all_zero(p.x) && fp_all_zero(p.y); }  // stored points are canonical
@@ -883,7 +873,7 @@ __global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_accumulate(const char
     const u32 E = offs[G];
     const int M = eff_slice(E, T, Mplan);
     const u32 t = logical_tid<KF>();
-    if (blockIdx.x == 0 && threadIdx.x == 0) *heavy_count = 0;  // the fix-up's list of heavy buckets starts empty (no memset launch)
+    if (blockIdx.x == 0 && threadIdx.x == 0) heavy_count[0] = heavy_count[1] = 0;  // the fix-up's lists of heavy and chain buckets start empty (no memset launch)
     const u64 start64 = (u64)t * (u64)M;
     if (start64 >= E) return;
     const u32 start = (u32)start64;
@@ -941,7 +931,6 @@ __global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_accumulate(const char
 // ---------------------------------------------------------------------------------------
 // 5. fix-up of buckets cut by slice boundaries
 // ---------------------------------------------------------------------------------------
-constexpr u32 HEAVY_SPAN = 8;  // buckets cut into more slices than this go to the heavy-bucket kernels
 
 // Waves per SIMD the tail kernels are compiled for.  2 = at most 256 registers per wave.  With "1" the compiler took 306
 // (k_reduce_l1<Fp>: 256 VGPRs + 50 AGPRs) and 357 (G2): such a wave cannot share a SIMD's 512 registers with ONE wave of
@@ -980,6 +969,56 @@ __global__ void __launch_bounds__(256, PS_TAIL_WAVES) k_fixup(const u32* __restr
         Xyzz<KF> part = ld_xyzz<KF>(&parts[2 * (size_t)t + (rs == slice_start ? 0 : 1)]);
         xyzz_add_inl<KF>(acc, part);
     }
+    st_xyzz<KF>(&buckets[g], acc);
+}
+
+// The long sums' fix-up is that kernel cut in three, so that no wave pays for more than ONE addition per lane.  In k_fixup a
+// wave costs as many additions as its worst lane needs: at 2^20 points over a 20-bit table (13.6 M entries, slices of 32)
+// three quarters of the 2^19 buckets are cut, all but ~4 000 of them exactly once, yet those few sit in more than a third
+// of the 8 192 waves and make all 64 lanes wait through a second addition, while the quarter of the lanes whose bucket is not
+// cut idles through the first: 1.6-1.75 lane-additions paid per addition the result needs.  Instead (fixup_class.hpp):
+//   k_fixup_classify  one thread per bucket, no field arithmetic: identity into an empty bucket, buckets cut more than
+//                     once onto chain_list (3 .. HEAVY_SPAN slots) or heavy_list (more)
+//   k_fixup_pair      one thread per slice BOUNDARY: where it cuts a bucket that is cut nowhere else, add the left slice's
+//                     tail slot and the right slice's head slot -- every active lane does exactly one addition
+//   k_qfixup_chain    a lane quad per bucket of chain_list (qtail.hpp)
+// Same group elements as k_fixup's chains, hence the same bytes out of the sum.  Short sums that take the one-lane fix-up
+// (MsmPlan::shortsum with lpb == 0) keep k_fixup: they are bound by their launches, not by lane-time.
+// -DPS_FIXUP_ONE_KERNEL: k_fixup for every plan (A/B builds).
+template <class KF>
+__global__ void __launch_bounds__(256) k_fixup_classify(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
+                                                        Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
+                                                        u32* __restrict__ heavy_count, u32* __restrict__ heavy_list,
+                                                        u32* __restrict__ chain_count, u32* __restrict__ chain_list) {
+    PS_TAIL_PRIO_HERE;
+    const u32 g = logical_tid<KF>();
+    if (g >= G) return;
+    const int M = eff_slice(offs[G], T, Mplan);
+    const int cls = bucket_class(offs[g], offs[g + 1], (u32)M, HEAVY_SPAN);
+    if (cls == BUCKET_EMPTY) {  // the identity (no memset of the bucket array: every bucket is written by exactly one of the
+                                // accumulation's flush, this kernel, k_fixup_pair, k_qfixup_chain and k_qfixup_heavy)
+        st_xyzz<KF>(&buckets[g], xyzz_identity<KF>());
+    } else if (cls == BUCKET_CHAIN) {
+        if (pair_leader<KF>()) chain_list[atomicAdd(chain_count, 1u)] = g;
+    } else if (cls == BUCKET_HEAVY) {
+        if (pair_leader<KF>()) heavy_list[atomicAdd(heavy_count, 1u)] = g;
+    }
+}
+
+template <class KF>
+__global__ void __launch_bounds__(256, PS_TAIL_WAVES) k_fixup_pair(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
+                                                       const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
+                                                       Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets) {
+    PS_TAIL_PRIO_HERE;
+    const u32 t = logical_tid<KF>() + 1;  // slice boundary t lies between slices t - 1 and t
+    if (t >= T) return;
+    const u32 E = offs[G];
+    const int M = eff_slice(E, T, Mplan);
+    u32 g;
+    if (!pair_boundary_bucket(offs, G, E, t, (u32)M, HEAVY_SPAN, g)) return;
+    Xyzz<KF> acc = ld_xyzz<KF>(&parts[part_slot(offs[g], t - 1, (u32)M)]);
+    const Xyzz<KF> right = ld_xyzz<KF>(&parts[2 * (size_t)t]);
+    xyzz_add_inl<KF>(acc, right);
     st_xyzz<KF>(&buckets[g], acc);
 }
 

@@ -219,6 +219,31 @@ __global__ void __launch_bounds__(256) k_qfixup(const u32* __restrict__ offs, u3
     if (store && sub == 0) q_store<KF>(&buckets[g], acc);
 }
 
+// ---- the long sums' buckets that are cut more than once but are not heavy (msm.hpp section 5): a quad per bucket ----
+// chain_list holds the buckets with 3 .. HEAVY_SPAN partial slots (k_fixup_classify); a quad adds them up in a row, 2 .. 7
+// quad additions deep.  The grid is sized on the host for the longest list the plan allows; quads take the list in strides.
+template <class KF>
+__global__ void __launch_bounds__(256) k_qfixup_chain(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
+                                                      const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
+                                                      Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
+                                                      const u32* __restrict__ chain_count, const u32* __restrict__ chain_list) {
+    PS_TAIL_PRIO_HERE;
+    constexpr u32 GL = QTraits<KF>::GL, NPB = 256 / GL;
+    const u32 nchain = *chain_count;
+    const int M = eff_slice(offs[G], T, Mplan);
+    for (u32 h = blockIdx.x * NPB + threadIdx.x / GL; h < nchain; h += gridDim.x * NPB) {
+        const u32 g = chain_list[h];
+        const u32 lo = offs[g], hi = offs[g + 1];
+        const u32 t0 = lo / (u32)M, t1 = (hi - 1) / (u32)M;
+        KF acc = q_load<KF>(&parts[part_slot(lo, t0, (u32)M)]);
+        for (u32 t = t0 + 1; t <= t1; t++) {  // every later slice starts inside the bucket: its head slot
+            const KF p = q_load<KF>(&parts[2 * (size_t)t]);
+            q_add<KF>(acc, p);
+        }
+        q_store<KF>(&buckets[g], acc);
+    }
+}
+
 // ---- heavy buckets (a witness that is half ones puts n/2 digits into one bucket) ----
 // Two levels of quad trees: jobs of a block's worth of slices (64 G1 / 32 G2 quads; s partial sums per quad for the largest
 // buckets, heavy_chunk_of), a tree as deep as the job is long, then per bucket the same over its jobs' results.  512 partial sums of a G2 bucket (Groth16's B on 2^12
