@@ -52,7 +52,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *   5  ps_phgr13_prove_shard, ps_phgr13_prove_multi and its ps_phgr13_device (no existing struct changed);
  *      later within 5: ps_groth16_prove_local, and ps_groth16_prove_multi reads the optional lxi / lxi2 / lxi_t of
  *      ps_groth16_device.pk.  No struct changed, so the number stays: an entry point added within a revision is detected by
- *      its symbol (dlsym), not by ps_abi_version(). */
+ *      its symbol (dlsym), not by ps_abi_version().  Likewise ps_qap_column_sums, ps_groth16_setup_from_srs (with the new
+ *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -393,6 +394,57 @@ void ps_phgr13_crs_free(ps_phgr13_crs* crs); /* frees the 14 arrays */
  * not exactly cnt points long.  The points must lie in the subgroup of order r, as the points of a key do (the scalar
  * multiplications split their scalars with the curve's endomorphism, which acts as a scalar only there). */
 int ps_points_monomial_to_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* mono, int nodes, ps_points** out);
+
+/* ---- a circuit's key from a powers-of-tau string, without the toxic waste ----
+ * NewGroth16TrustedSetup (groth16.go:64-101) computes every key element from alpha, beta, delta, x, gamma in the clear, values
+ * that "must be delete[d] after a trusted setup" (groth16.go:13-14).  A deployment instead starts from a universal string
+ * {x^i G} that no single party knows (phase 1), derives the circuit's key from it with delta = gamma = 1, and lets every party
+ * fold a delta / gamma share of its own into that key (phase 2); anybody can check a fold.  Entry points added within
+ * revision 5 (found by symbol, no existing struct changed).
+ *
+ * Column sums of an R1CS matrix over points: out[i] = sum_j M[j][i] p[j], i < n_vars; M = L, R, O for which = 0, 1, 2; p has
+ * n_gates points (PS_ERR_LENGTH otherwise), either group.  The per-variable sums of fullLinearPoly (groth16.go:254-264) when
+ * only {l_j(x) G} is known, not x: the sparse matrix applied to a vector of points.  The coefficients are the int64 of
+ * ps_csr, so a column costs at most 64 doublings plus one addition per set coefficient bit, not a 255-bit multiplication per
+ * non-zero.  Identity points, repeated points and terms that cancel are handled; a variable that occurs in no gate gives the
+ * identity.  Canonical affine output (the bytes ps_points_from_scalars gives for the same group element); caller frees. */
+int ps_qap_column_sums(ps_ctx* ctx, const ps_qap* q, int which, const ps_points* p, ps_points** out);
+
+typedef struct {                   /* phase-1 output, the layout public ceremonies publish; n = n_gates */
+    const ps_points* tau_g1;       /* x^i G1,        i < 2n-1 */
+    const ps_points* tau_g2;       /* x^i G2,        i < n    */
+    const ps_points* alpha_tau_g1; /* alpha x^i G1,  i < n    */
+    const ps_points* beta_tau_g1;  /* beta  x^i G1,  i < n    */
+    uint8_t beta_g2[192];          /* beta G2                 */
+} ps_groth16_srs;
+/* The key of ps_groth16_setup for the same alpha, beta, x and delta = gamma = 1, byte for byte, from the string alone:
+ * alpha, beta = the first points of the scaled arrays, beta2 copied, delta = G1, delta2 = gamma = G2; xi, xi2 = the first n
+ * powers, lxi / lxi2 their ps_points_monomial_to_lagrange; io_lp | nio_lp = ps_qap_column_sums of L over the Lagrange form of
+ * beta_tau_g1, plus R over that of alpha_tau_g1, plus O over lxi, split at diff = n_vars - n_io; xi_t[i] = sum_k z_k tau_g1[i+k]
+ * with z = prod_{j=1..n} (X - j) (one NTT over points: the correlation of lagrange.hpp); lxi_t its conversion on the nodes
+ * n+1..2n-1.  Five conversions dominate the cost (seconds each at 2^16 gates).  An array of another length than the comment
+ * above says: PS_ERR_LENGTH; n < 2: PS_ERR_ARG.  `out` is overwritten; the caller frees its eight arrays with ps_points_free.
+ * The caller is responsible for the string being well formed (checking that is a pairing test per power, not done here)
+ * and for its points lying in the subgroup of order r -- ps_points_check_subgroup on each array: the scalar multiplications
+ * split their scalars with the curve's endomorphism, which acts as a scalar only there. */
+int ps_groth16_setup_from_srs(ps_ctx* ctx, const ps_qap* q, const ps_groth16_srs* srs, ps_groth16_crs* out);
+/* out = in with delta *= d and gamma *= g: nio_lp, xi_t and lxi_t scaled by 1/d, io_lp by 1/g (groth16.go:86-97), delta and
+ * delta2 by d, gamma by g -- the key ps_groth16_setup makes for (delta d, gamma g), byte for byte.  d or g zero (mod r):
+ * PS_ERR_ARG.  The drawing of d and g, and their deletion, are the caller's.  out != in.  The four scaled arrays of `out` are
+ * new; its xi, xi2, lxi, lxi2 are views of in's storage (ps_points_slice: reference counted), so BOTH keys are freed as
+ * usual, each of its eight handles with ps_points_free, in either order. */
+int ps_groth16_crs_contribute(ps_ctx* ctx, const ps_groth16_crs* in, const uint8_t d_be32[32], const uint8_t g_be32[32],
+                              ps_groth16_crs* out);
+/* *ok = 1 iff `after` is `before` with SOME (d, g) folded in -- one fold or several:
+ *   e(delta', G2) = e(G1, delta2');   e(sum rho_i N'_i, delta2') = e(sum rho_i N_i, delta2) for N = nio_lp, xi_t, lxi_t;
+ *   e(sum rho_i I'_i, gamma') = e(sum rho_i I_i, gamma) for io_lp;   alpha, beta, beta2, xi, xi2, lxi, lxi2 byte-equal.
+ * rho: nrho weights of 32 B, canonical (PS_ERR_ENCODING), drawn by the caller AFTER both keys are fixed, as for
+ * ps_groth16_verify_batch (128 random bits each are enough); nrho at least the longest scaled array (PS_ERR_LENGTH).  A key
+ * that was not made by a fold passes with probability <= 2^-bits(rho) per array.  Arrays of different lengths: *ok = 0.
+ * The fixed points are tested for the subgroup; the arrays of an untrusted `after` go through ps_points_check_subgroup
+ * first.  Needs an empty MSM queue. */
+int ps_groth16_crs_check_update(ps_ctx* ctx, const ps_groth16_crs* before, const ps_groth16_crs* after, const uint8_t* rho_be32,
+                                size_t nrho, int* ok);
 
 /* ---- verifiers (host-side ate pairing; the IO commitments go through the GPU MSM) ---- */
 typedef struct { /* the verifier's part of Groth16Setup (groth16.go:30-61) */

@@ -31,6 +31,7 @@ SYMBOLS = [
     "ps_points_lincomb", "ps_msm_multi_device", "ps_groth16_prove_multi", "ps_points_monomial_to_lagrange",
     "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_groth16_prove_local", "ps_phgr13_prove", "ps_phgr13_prove_shard", "ps_phgr13_prove_multi", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
     "ps_pairing_product_is_one", "ps_groth16_verify_batch",
+    "ps_qap_column_sums", "ps_groth16_setup_from_srs", "ps_groth16_crs_contribute", "ps_groth16_crs_check_update",
 ]
 
 
@@ -102,6 +103,11 @@ class Phgr13Proof(C.Structure):
     _fields_ = [("vss", C.c_uint8 * 96), ("vass", C.c_uint8 * 96), ("wss", C.c_uint8 * 192),
                 ("wass", C.c_uint8 * 96), ("yss", C.c_uint8 * 96), ("yass", C.c_uint8 * 96),
                 ("hs", C.c_uint8 * 96), ("gz", C.c_uint8 * 96)]
+
+
+class Groth16Srs(C.Structure):  # phase-1 output (ps_groth16_srs): x^i G1 (2n-1), x^i G2 (n), alpha x^i G1 (n), beta x^i G1 (n), beta G2
+    _fields_ = [("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p),
+                ("beta_g2", C.c_uint8 * 192)]
 
 
 def _load():
@@ -191,6 +197,10 @@ def _load():
     lib.ps_pairing_equal.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
     lib.ps_pairing_product_is_one.argtypes = [vp, vp, vp, i, C.POINTER(C.c_int)]
     lib.ps_groth16_verify_batch.argtypes = [vp, C.POINTER(Groth16Vk), vp, C.c_char_p, sz, C.c_char_p, C.POINTER(C.c_int)]
+    lib.ps_qap_column_sums.argtypes = [vp, vp, i, vp, pp]
+    lib.ps_groth16_setup_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs)]
+    lib.ps_groth16_crs_contribute.argtypes = [vp, C.POINTER(Groth16Crs), C.c_char_p, C.c_char_p, C.POINTER(Groth16Crs)]
+    lib.ps_groth16_crs_check_update.argtypes = [vp, C.POINTER(Groth16Crs), C.POINTER(Groth16Crs), C.c_char_p, sz, C.POINTER(C.c_int)]
     return lib
 
 

@@ -494,6 +494,14 @@ class QAP:
         _check(lib.ps_qap_quotient(self.ctx._h, self._h, sol._h, None, None, None, C.byref(h)))
         return Poly(self.ctx, h)
 
+    def column_sums(self, which: int, points: Points) -> Points:
+        """out[i] = sum_j M[j][i] * points[j] for every variable i; M = left, right, out for which = 0, 1, 2 and one point per
+        gate (ps_qap_column_sums): the per-variable sums of fullLinearPoly (groth16.go:254-264) over group elements, as a
+        setup without the secret point needs them.  LengthMismatch when len(points) != nbGates."""
+        h = C.c_void_p()
+        _check(lib.ps_qap_column_sums(self.ctx._h, self._h, which, points._h, C.byref(h)))
+        return Points(self.ctx, h)
+
     def free(self):
         if getattr(self, "_h", None):
             lib.ps_qap_free(self._h)
@@ -563,6 +571,75 @@ def NewGroth16TrustedSetup(qap: "QAP", alpha: int, beta: int, delta: int, x: int
     tr = Groth16Setup(bytes(crs.alpha), bytes(crs.beta), bytes(crs.delta), bytes(crs.beta2), bytes(crs.delta2),
                       pts["xi"], pts["xi2"], pts["nio_lp"], pts["xi_t"], pts["lxi"], pts["lxi2"], pts["lxi_t"])
     return tr, {"Gamma": bytes(crs.gamma), "IoLP": pts["io_lp"]}
+
+
+class Groth16SRS:
+    """Phase-1 output (a powers-of-tau string, ps_groth16_srs) for a circuit of n gates: TauG1 = {x^i G1} (2n-1 points), TauG2 =
+    {x^i G2} (n), AlphaTauG1 = {alpha x^i G1} (n), BetaTauG1 = {beta x^i G1} (n), BetaG2 = beta G2 (192 bytes).  The caller
+    vouches for its shape and for its points lying in the subgroup (Points.in_subgroup)."""
+
+    def __init__(self, TauG1: Points, TauG2: Points, AlphaTauG1: Points, BetaTauG1: Points, BetaG2: bytes):
+        self.TauG1, self.TauG2, self.AlphaTauG1, self.BetaTauG1, self.BetaG2 = TauG1, TauG2, AlphaTauG1, BetaTauG1, BetaG2
+
+    def _struct(self):
+        s = _lib.Groth16Srs()
+        s.tau_g1, s.tau_g2, s.alpha_tau_g1, s.beta_tau_g1 = self.TauG1._h, self.TauG2._h, self.AlphaTauG1._h, self.BetaTauG1._h
+        C.memmove(s.beta_g2, self.BetaG2, 192)
+        return s
+
+
+_CRS_ARRAYS = ("xi", "xi2", "io_lp", "nio_lp", "xi_t", "lxi", "lxi2", "lxi_t")
+
+
+def _crs_to_pair(ctx: Context, crs: "_lib.Groth16Crs"):
+    """(Groth16Setup, {"Gamma", "IoLP"}) over the arrays of a filled ps_groth16_crs; the Points own the handles."""
+    pts = {f: Points(ctx, C.c_void_p(getattr(crs, f))) if getattr(crs, f) else None for f in _CRS_ARRAYS}
+    tr = Groth16Setup(bytes(crs.alpha), bytes(crs.beta), bytes(crs.delta), bytes(crs.beta2), bytes(crs.delta2),
+                      pts["xi"], pts["xi2"], pts["nio_lp"], pts["xi_t"], pts["lxi"], pts["lxi2"], pts["lxi_t"])
+    return tr, {"Gamma": bytes(crs.gamma), "IoLP": pts["io_lp"]}
+
+
+def _crs_from_pair(tr: Groth16Setup, vk: dict) -> "_lib.Groth16Crs":
+    crs = _lib.Groth16Crs()
+    for name, src in (("alpha", tr.Alpha), ("beta", tr.Beta), ("delta", tr.Delta), ("beta2", tr.Beta2), ("delta2", tr.Delta2),
+                      ("gamma", vk["Gamma"])):
+        C.memmove(getattr(crs, name), src, len(src))
+    for f, p in (("xi", tr.Xi), ("xi2", tr.Xi2), ("io_lp", vk["IoLP"]), ("nio_lp", tr.NioLP), ("xi_t", tr.XiT), ("lxi", tr.LXi),
+                 ("lxi2", tr.LXi2), ("lxi_t", tr.LXiT)):
+        if p is not None:
+            setattr(crs, f, p._h)
+    return crs
+
+
+def NewGroth16SetupFromSRS(qap: "QAP", srs: Groth16SRS):
+    """The key NewGroth16TrustedSetup(qap, alpha, beta, 1, x, 1) makes (groth16.go:64-101), byte for byte, from a powers-of-tau
+    string alone: nobody's alpha, beta or x is needed (ps_groth16_setup_from_srs).  Returns the same pair, (Groth16Setup for the
+    prover, dict with Gamma / IoLP for the verifier); Groth16Contribute then folds delta / gamma shares into it."""
+    s = srs._struct()
+    crs = _lib.Groth16Crs()
+    _check(lib.ps_groth16_setup_from_srs(qap.ctx._h, qap._h, C.byref(s), C.byref(crs)))
+    return _crs_to_pair(qap.ctx, crs)
+
+
+def Groth16Contribute(ctx: Context, tr: Groth16Setup, vk: dict, d: int, g: int):
+    """The key (tr, vk) with delta multiplied by d and gamma by g (ps_groth16_crs_contribute): NioLP, XiT, LXiT scaled by 1/d,
+    IoLP by 1/g, Delta, Delta2 by d, Gamma by g.  d and g are the caller's to draw and to delete.  Returns a new pair; its Xi,
+    Xi2, LXi, LXi2 share device memory with the input's (reference counted: either key may be dropped first)."""
+    src = _crs_from_pair(tr, vk)
+    out = _lib.Groth16Crs()
+    _check(lib.ps_groth16_crs_contribute(ctx._h, C.byref(src), _be32(d % R_ORDER), _be32(g % R_ORDER), C.byref(out)))
+    return _crs_to_pair(ctx, out)
+
+
+def Groth16CheckUpdate(ctx: Context, before, after, rhos: Sequence[int]) -> bool:
+    """Was the key `after` = (tr, vk) made from `before` = (tr, vk) by folding in SOME shares (one Groth16Contribute or several)?
+    rhos: weights below r drawn AFTER both keys are fixed, at least as many as the longest of NioLP, XiT, IoLP
+    (ps_groth16_crs_check_update; LengthMismatch otherwise)."""
+    a, b = _crs_from_pair(*before), _crs_from_pair(*after)
+    rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
+    ok = C.c_int(0)
+    _check(lib.ps_groth16_crs_check_update(ctx._h, C.byref(a), C.byref(b), rho, len(rhos), C.byref(ok)))
+    return bool(ok.value)
 
 
 class Groth16Proof:

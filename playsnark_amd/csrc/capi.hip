@@ -19,6 +19,7 @@
 #include "msm.hpp"
 #include "quotient.hpp"
 #include "lagrange.hpp"
+#include "ec_spmv.hpp"
 
 namespace ps {
 #include "hostfield.inc"
@@ -1979,3 +1980,4 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "pairing.inc"
 #include "pairing_dev.hpp"
 #include "verify_batch.inc"
+#include "srs_setup.inc"

@@ -288,5 +288,13 @@ __global__ void __launch_bounds__(256) k_fr_v_rev(Fr* __restrict__ dst, const Fr
     const u64 j = (2 * np - i) & (2 * np - 1);
     dst[i] = j < np ? ((j & 1) ? fr_neg(invfact[j]) : invfact[j]) : fr_zero();
 }
+// dst[i] = v[(-i) mod S], v_j = src[j] for j < cnt and 0 beyond; i < S = 2^logS   (a multiplier of any length, read backwards:
+// the correlation sum_k src[k] g[i + k] of the setup from a powers-of-tau string, srs_setup.inc)
+__global__ void __launch_bounds__(256) k_fr_rev_pad(Fr* __restrict__ dst, const Fr* __restrict__ src, u64 cnt, int logS) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x, S = 1ull << logS;
+    if (i >= S) return;
+    const u64 j = (S - i) & (S - 1);
+    dst[i] = j < cnt ? src[j] : fr_zero();
+}
 
 }  // namespace ps

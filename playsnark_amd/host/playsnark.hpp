@@ -81,6 +81,7 @@ class Points {
     }
 
   private:
+    friend class QAP;
     Points(Context& c, ps_points* h) : ctx_(&c), h_(h) {}
     Context* ctx_;
     ps_points* h_ = nullptr;
@@ -151,6 +152,13 @@ class QAP {
         ps_scalars* h = nullptr;
         check(ps_qap_quotient(ctx_->get(), h_, sol.get(), nullptr, nullptr, nullptr, &h));
         return Poly(*ctx_, h);
+    }
+    // out[i] = sum_j M[j][i] * points[j] over the variables i; M = left, right, out for which = 0, 1, 2, one point per gate
+    // (ps_qap_column_sums): the per-variable sums of fullLinearPoly (groth16.go:254-264) over group elements
+    Points column_sums(int which, const Points& points) const {
+        ps_points* h = nullptr;
+        check(ps_qap_column_sums(ctx_->get(), h_, which, points.get(), &h));
+        return Points(*ctx_, h);
     }
 
   private:
@@ -254,6 +262,31 @@ inline ps_groth16_crs NewGroth16TrustedSetup(Context& c, const QAP& q, const ps_
     ps_groth16_crs out;
     check(ps_groth16_setup(c.get(), q.get(), &tw, &out));
     return out;
+}
+
+// Phase-1 output (a powers-of-tau string): x^i G1 (2n-1), x^i G2 (n), alpha x^i G1 (n), beta x^i G1 (n), beta G2
+using Groth16SRS = ps_groth16_srs;
+// The key of NewGroth16TrustedSetup (groth16.go:64-101) for delta = gamma = 1 from the string alone: no toxic waste.  The
+// caller frees the eight arrays of the result with ps_points_free, as with NewGroth16TrustedSetup.
+inline ps_groth16_crs NewGroth16SetupFromSRS(Context& c, const QAP& q, const Groth16SRS& srs) {
+    ps_groth16_crs out;
+    check(ps_groth16_setup_from_srs(c.get(), q.get(), &srs, &out));
+    return out;
+}
+// `in` with delta multiplied by d and gamma by g (ps_groth16_crs_contribute); xi, xi2, lxi, lxi2 of the result are views of
+// in's storage (reference counted): both keys are freed array by array, in either order
+inline ps_groth16_crs Groth16Contribute(Context& c, const ps_groth16_crs& in, const Scalar& d, const Scalar& g) {
+    ps_groth16_crs out;
+    check(ps_groth16_crs_contribute(c.get(), &in, d.data(), g.data(), &out));
+    return out;
+}
+// Was `after` made from `before` by folding in SOME shares?  rho_be32: nrho x 32 bytes drawn after both keys are fixed, at
+// least as many as the longest of nio_lp, xi_t, io_lp (ps_groth16_crs_check_update)
+inline bool Groth16CheckUpdate(Context& c, const ps_groth16_crs& before, const ps_groth16_crs& after, const uint8_t* rho_be32,
+                               size_t nrho) {
+    int ok = 0;
+    check(ps_groth16_crs_check_update(c.get(), &before, &after, rho_be32, nrho, &ok));
+    return ok != 0;
 }
 
 // func NewPHGR13TrustedSetup(qap QAP) PHGR13Setup (pinochio.go:93), toxic waste drawn by the caller;

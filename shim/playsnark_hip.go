@@ -356,6 +356,7 @@ type HipGroth16 struct {
 	vk                        C.ps_groth16_vk
 	xi, xi2, nioLP, xiT, ioLP *C.ps_points
 	lagrange                  []*C.ps_points // lxi, lxi2, lxi_t when the key came from NewHipGroth16FromToxicWaste
+	crs                       C.ps_groth16_crs // the whole key when it came from NewHipGroth16FromSRS / ContributeHIP
 	qap                       *HipQAP
 }
 
@@ -497,6 +498,97 @@ func Groth16VerifyBatchHIP(hs *HipGroth16, proofs []Groth16Proof, ios []Vector) 
 	var ok C.int
 	call(func() C.int {
 		return C.ps_groth16_verify_batch(hipCtx, &hs.vk, dio, u8(raw), C.size_t(len(proofs)), u8(rho), &ok)
+	})
+	return ok != 0
+}
+
+// ---------------------------------------------------------------------------------------
+// A key from a powers-of-tau string: NewGroth16TrustedSetup (groth16.go:64-101) keeps alpha, beta, delta, x, gamma "for
+// testing and learning purpose" (groth16.go:13-14).  A deployment derives the circuit's key from a universal string
+// {x^i G} nobody knows (delta = gamma = 1), every party folds a delta / gamma share of its own into it, and anybody checks
+// a fold.
+// ---------------------------------------------------------------------------------------
+
+// ColumnSumsHIP: out[i] = sum_j M[j][i] * pts[j] over the variables i, M = left, right, out for which = 0, 1, 2
+// (ps_qap_column_sums): fullLinearPoly's per-variable sums (groth16.go:254-264) over group elements.  The caller frees.
+func (q *HipQAP) ColumnSumsHIP(which int, pts *C.ps_points) *C.ps_points {
+	var out *C.ps_points
+	call(func() C.int { return C.ps_qap_column_sums(hipCtx, q.h, C.int(which), pts, &out) })
+	return out
+}
+
+// Groth16SRS is phase-1 output for a circuit of n gates: TauG1 = {x^i G1} (2n-1), TauG2 = {x^i G2} (n), AlphaTauG1 =
+// {alpha x^i G1} (n), BetaTauG1 = {beta x^i G1} (n), BetaG2 = beta G2.  UnmarshalBinary has put every point in the subgroup.
+type Groth16SRS struct {
+	TauG1, TauG2, AlphaTauG1, BetaTauG1 []Commit
+	BetaG2                              Commit
+}
+
+// hipGroth16FromCrs wraps a whole ps_groth16_crs: both forms of the arrays, the prover's and the verifier's fixed points.
+func hipGroth16FromCrs(crs C.ps_groth16_crs, q *HipQAP) *HipGroth16 {
+	hs := &HipGroth16{qap: q, xi: crs.xi, xi2: crs.xi2, nioLP: crs.nio_lp, xiT: crs.xi_t, ioLP: crs.io_lp, crs: crs}
+	hs.lagrange = []*C.ps_points{crs.lxi, crs.lxi2, crs.lxi_t}
+	hs.pk.alpha, hs.pk.beta, hs.pk.delta, hs.pk.beta2, hs.pk.delta2 = crs.alpha, crs.beta, crs.delta, crs.beta2, crs.delta2
+	hs.pk.xi, hs.pk.xi2, hs.pk.nio_lp, hs.pk.xi_t = crs.xi, crs.xi2, crs.nio_lp, crs.xi_t
+	hs.pk.lxi, hs.pk.lxi2, hs.pk.lxi_t = crs.lxi, crs.lxi2, crs.lxi_t
+	hs.vk.alpha, hs.vk.beta2, hs.vk.gamma, hs.vk.delta2 = crs.alpha, crs.beta2, crs.gamma, crs.delta2
+	hs.vk.io_lp = crs.io_lp
+	return hs
+}
+
+// NewHipGroth16FromSRS derives the circuit's key from the string alone (ps_groth16_setup_from_srs): the key
+// NewGroth16TrustedSetup makes for the same alpha, beta, x and delta = gamma = 1, in both forms.  A wrong array length
+// panics like BlindEval (algebra.go:350-352).
+func NewHipGroth16FromSRS(srs Groth16SRS, q *HipQAP) *HipGroth16 {
+	var s C.ps_groth16_srs
+	s.tau_g1 = uploadPoints(C.PS_G1, srs.TauG1)
+	s.tau_g2 = uploadPoints(C.PS_G2, srs.TauG2)
+	s.alpha_tau_g1 = uploadPoints(C.PS_G1, srs.AlphaTauG1)
+	s.beta_tau_g1 = uploadPoints(C.PS_G1, srs.BetaTauG1)
+	defer func() {
+		for _, p := range []*C.ps_points{s.tau_g1, s.tau_g2, s.alpha_tau_g1, s.beta_tau_g1} {
+			C.ps_points_free(p)
+		}
+	}()
+	copyTo(unsafe.Pointer(&s.beta_g2[0]), affineOf(C.PS_G2, srs.BetaG2))
+	var crs C.ps_groth16_crs
+	call(func() C.int { return C.ps_groth16_setup_from_srs(hipCtx, q.h, &s, &crs) })
+	return hipGroth16FromCrs(crs, q)
+}
+
+// ContributeHIP folds a share into the key: delta *= d, gamma *= g (ps_groth16_crs_contribute).  d and g are drawn by the
+// caller and must be forgotten afterwards.  The result shares Xi, Xi2 and their Lagrange forms with hs (reference
+// counted); both are Free()d as usual.  Only keys made by NewHipGroth16FromSRS or ContributeHIP carry what this needs.
+func (hs *HipGroth16) ContributeHIP(d, g Element) *HipGroth16 {
+	db, err := d.MarshalBinary()
+	if err != nil {
+		panic(err)
+	}
+	gb, err := g.MarshalBinary()
+	if err != nil {
+		panic(err)
+	}
+	var out C.ps_groth16_crs
+	call(func() C.int { return C.ps_groth16_crs_contribute(hipCtx, &hs.crs, u8(db), u8(gb), &out) })
+	return hipGroth16FromCrs(out, hs.qap)
+}
+
+// CheckUpdateHIP: was `after` made from `before` by folding in SOME shares (ps_groth16_crs_check_update)?  The weights of
+// the random linear combinations are drawn here, after both keys are in hand, 128 bits each.
+func CheckUpdateHIP(before, after *HipGroth16) bool {
+	n := 0
+	for _, p := range []*C.ps_points{before.nioLP, before.xiT, before.ioLP} {
+		if l := int(C.ps_points_len(p)); l > n {
+			n = l
+		}
+	}
+	rho := make([]byte, 32*n)
+	for i := 0; i < n; i++ {
+		random.Bytes(rho[32*i+16:32*i+32], random.New())
+	}
+	var ok C.int
+	call(func() C.int {
+		return C.ps_groth16_crs_check_update(hipCtx, &before.crs, &after.crs, u8(rho), C.size_t(n), &ok)
 	})
 	return ok != 0
 }
