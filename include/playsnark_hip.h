@@ -53,7 +53,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      later within 5: ps_groth16_prove_local, and ps_groth16_prove_multi reads the optional lxi / lxi2 / lxi_t of
  *      ps_groth16_device.pk.  No struct changed, so the number stays: an entry point added within a revision is detected by
  *      its symbol (dlsym), not by ps_abi_version().  Likewise ps_qap_column_sums, ps_groth16_setup_from_srs (with the new
- *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update. */
+ *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update; then ps_scalars_powers,
+ *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -424,9 +425,9 @@ typedef struct {                   /* phase-1 output, the layout public ceremoni
  * with z = prod_{j=1..n} (X - j) (one NTT over points: the correlation of lagrange.hpp); lxi_t its conversion on the nodes
  * n+1..2n-1.  Five conversions dominate the cost (seconds each at 2^16 gates).  An array of another length than the comment
  * above says: PS_ERR_LENGTH; n < 2: PS_ERR_ARG.  `out` is overwritten; the caller frees its eight arrays with ps_points_free.
- * The caller is responsible for the string being well formed (checking that is a pairing test per power, not done here)
- * and for its points lying in the subgroup of order r -- ps_points_check_subgroup on each array: the scalar multiplications
- * split their scalars with the curve's endomorphism, which acts as a scalar only there. */
+ * The caller is responsible for the string being well formed and for its points lying in the subgroup of order r --
+ * ps_groth16_srs_check (below) tests both: the scalar multiplications split their scalars with the curve's endomorphism, which
+ * acts as a scalar only there. */
 int ps_groth16_setup_from_srs(ps_ctx* ctx, const ps_qap* q, const ps_groth16_srs* srs, ps_groth16_crs* out);
 /* out = in with delta *= d and gamma *= g: nio_lp, xi_t and lxi_t scaled by 1/d, io_lp by 1/g (groth16.go:86-97), delta and
  * delta2 by d, gamma by g -- the key ps_groth16_setup makes for (delta d, gamma g), byte for byte.  d or g zero (mod r):
@@ -445,6 +446,48 @@ int ps_groth16_crs_contribute(ps_ctx* ctx, const ps_groth16_crs* in, const uint8
  * first.  Needs an empty MSM queue. */
 int ps_groth16_crs_check_update(ps_ctx* ctx, const ps_groth16_crs* before, const ps_groth16_crs* after, const uint8_t* rho_be32,
                                 size_t nrho, int* ok);
+
+/* ---- phase 1: making and checking the powers-of-tau string itself ----
+ * The string ps_groth16_setup_from_srs starts from is the work of a ceremony: it begins as the trivial string (tau = alpha =
+ * beta = 1: every point a generator), every party folds a share (t, a, b) of its own into it and publishes (t G2, a G2, b G2),
+ * and anybody checks every fold.  Nobody knows tau, alpha, beta of the result unless ALL parties collude.  Entry points added
+ * within revision 5 (found by symbol, no existing struct changed).
+ *
+ * out[i] = c s^i, i < n (s^0 = 1 also for s = 0): the exponents of a fold.  s or c not below r: PS_ERR_ENCODING; n = 0: an
+ * empty vector; n >= 2^32: PS_ERR_ARG.  Caller frees. */
+int ps_scalars_powers(ps_ctx* ctx, const uint8_t s_be32[32], const uint8_t c_be32[32], size_t n, ps_scalars** out);
+
+typedef struct { uint8_t t_g2[192], a_g2[192], b_g2[192]; } ps_groth16_srs_share; /* t G2, a G2, b G2 */
+/* out = in with tau *= t, alpha *= a, beta *= b:  tau_g1[i], tau_g2[i] scaled by t^i, alpha_tau_g1[i] by a t^i, beta_tau_g1[i] by
+ * b t^i, beta_g2 by b; share = (t G2, a G2, b G2), the contributor's public values.  Canonical affine output: the bytes
+ * ps_points_from_scalars gives for the same group elements.  Arrays of any lengths (a ceremony string is longer than any one
+ * circuit needs; ps_points_slice cuts it); the four arrays of `out` are as long as in's, new, and freed by the caller with
+ * ps_points_free.  out != in.  t, a or b zero (mod r): PS_ERR_ARG; not below r: PS_ERR_ENCODING.  The drawing of t, a and b, and
+ * their deletion, are the caller's; so is the subgroup membership of in's points, as in ps_groth16_setup_from_srs. */
+int ps_groth16_srs_contribute(ps_ctx* ctx, const ps_groth16_srs* in, const uint8_t t_be32[32], const uint8_t a_be32[32],
+                              const uint8_t b_be32[32], ps_groth16_srs* out, ps_groth16_srs_share* share);
+/* *ok = 1 iff the string is well formed -- {x^i G1}, {x^i G2}, {alpha x^i G1}, {beta x^i G1}, beta G2 for SOME non-zero x, alpha,
+ * beta.  With T1, T2, A, B the four arrays of m1, m2, ma, mb points:
+ *   T1[0] = G1, T2[0] = G2 (bytes);  T1[1], A[0], B[0], beta_g2 are not the identity;
+ *   e(sum rho_i X[i], T2[1]) = e(sum rho_i X[i+1], G2), i < m - 1, for X = T1, A, B;
+ *   e(T1[1], sum rho_i T2[i]) = e(G1, sum rho_i T2[i+1]), i < m2 - 1;     e(B[0], G2) = e(G1, beta_g2)
+ * -- every point of every array is in a tested pair (i, i+1); each equation is a pairing product of its own.  m1, m2 >= 2,
+ * ma, mb >= 1 (PS_ERR_ARG otherwise; an array of one point has no pair to test).  rho: nrho weights of 32 B, canonical
+ * (PS_ERR_ENCODING), drawn by the caller AFTER the string is fixed (128 random bits each are enough), nrho >= max(m) - 1
+ * (PS_ERR_LENGTH).  A string that is not well formed passes with probability <= 2^-bits(rho) per equation.  check_subgroup != 0:
+ * the four arrays go through ps_points_check_subgroup and beta_g2 is tested likewise; a point outside the subgroup gives
+ * *ok = 0 (0 only for a string the caller made itself).  A beta_g2 that is no canonical point on the curve: PS_ERR_ENCODING.
+ * Needs an empty MSM queue. */
+int ps_groth16_srs_check(ps_ctx* ctx, const ps_groth16_srs* srs, const uint8_t* rho_be32, size_t nrho, int check_subgroup, int* ok);
+/* *ok = 1 iff `after` passes ps_groth16_srs_check with the subgroup tests on, each of its arrays is as long as before's, and
+ *   e(after.T1[1], G2) = e(before.T1[1], share.t_g2);   e(after.A[0], G2) = e(before.A[0], share.a_g2);
+ *   e(after.B[0], G2) = e(before.B[0], share.b_g2);     e(G1, after.beta_g2) = e(before.B[0], share.b_g2)
+ * i.e. `after` is `before` with the (t, a, b) behind the share folded in.  `before` is taken as already checked.  The share is
+ * untrusted: an encoding that is no canonical point on the curve is PS_ERR_ENCODING, the identity or a point outside the
+ * subgroup gives *ok = 0.  rho as above.  A proof that the contributor KNOWS t, a and b (so that it could not derive its share
+ * from earlier ones) belongs to the ceremony protocol and is not part of this call.  Needs an empty MSM queue. */
+int ps_groth16_srs_check_update(ps_ctx* ctx, const ps_groth16_srs* before, const ps_groth16_srs* after, const ps_groth16_srs_share* share,
+                                const uint8_t* rho_be32, size_t nrho, int* ok);
 
 /* ---- verifiers (host-side ate pairing; the IO commitments go through the GPU MSM) ---- */
 typedef struct { /* the verifier's part of Groth16Setup (groth16.go:30-61) */

@@ -32,6 +32,7 @@ SYMBOLS = [
     "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_groth16_prove_local", "ps_phgr13_prove", "ps_phgr13_prove_shard", "ps_phgr13_prove_multi", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
     "ps_pairing_product_is_one", "ps_groth16_verify_batch",
     "ps_qap_column_sums", "ps_groth16_setup_from_srs", "ps_groth16_crs_contribute", "ps_groth16_crs_check_update",
+    "ps_scalars_powers", "ps_groth16_srs_contribute", "ps_groth16_srs_check", "ps_groth16_srs_check_update",
 ]
 
 
@@ -108,6 +109,10 @@ class Phgr13Proof(C.Structure):
 class Groth16Srs(C.Structure):  # phase-1 output (ps_groth16_srs): x^i G1 (2n-1), x^i G2 (n), alpha x^i G1 (n), beta x^i G1 (n), beta G2
     _fields_ = [("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p),
                 ("beta_g2", C.c_uint8 * 192)]
+
+
+class Groth16SrsShare(C.Structure):  # a phase-1 contributor's public values (ps_groth16_srs_share): t G2, a G2, b G2
+    _fields_ = [("t_g2", C.c_uint8 * 192), ("a_g2", C.c_uint8 * 192), ("b_g2", C.c_uint8 * 192)]
 
 
 def _load():
@@ -201,6 +206,12 @@ def _load():
     lib.ps_groth16_setup_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs)]
     lib.ps_groth16_crs_contribute.argtypes = [vp, C.POINTER(Groth16Crs), C.c_char_p, C.c_char_p, C.POINTER(Groth16Crs)]
     lib.ps_groth16_crs_check_update.argtypes = [vp, C.POINTER(Groth16Crs), C.POINTER(Groth16Crs), C.c_char_p, sz, C.POINTER(C.c_int)]
+    lib.ps_scalars_powers.argtypes = [vp, C.c_char_p, C.c_char_p, sz, pp]
+    lib.ps_groth16_srs_contribute.argtypes = [vp, C.POINTER(Groth16Srs), C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(Groth16Srs),
+                                              C.POINTER(Groth16SrsShare)]
+    lib.ps_groth16_srs_check.argtypes = [vp, C.POINTER(Groth16Srs), C.c_char_p, sz, i, C.POINTER(C.c_int)]
+    lib.ps_groth16_srs_check_update.argtypes = [vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Srs), C.POINTER(Groth16SrsShare), C.c_char_p, sz,
+                                                C.POINTER(C.c_int)]
     return lib
 
 

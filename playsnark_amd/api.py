@@ -292,6 +292,13 @@ class Poly:
         _check(lib.ps_scalars_slice(self._h, first, n, C.byref(h)))
         return Poly(self.ctx, h, owner=self)
 
+    @classmethod
+    def powers(cls, ctx: Context, s: int, n: int, c: int = 1) -> "Poly":
+        """[c, c s, c s^2, .., c s^(n-1)] computed on the device (ps_scalars_powers); s^0 = 1 also for s = 0.  s and c below r."""
+        h = C.c_void_p()
+        _check(lib.ps_scalars_powers(ctx._h, _be32(s), _be32(c), n, C.byref(h)))
+        return cls(ctx, h)
+
     def Mul(self, p2: "Poly") -> "Poly":
         """func (p Poly) Mul(p2 Poly) Poly (algebra.go:92-105)."""
         h = C.c_void_p()
@@ -576,16 +583,65 @@ def NewGroth16TrustedSetup(qap: "QAP", alpha: int, beta: int, delta: int, x: int
 class Groth16SRS:
     """Phase-1 output (a powers-of-tau string, ps_groth16_srs) for a circuit of n gates: TauG1 = {x^i G1} (2n-1 points), TauG2 =
     {x^i G2} (n), AlphaTauG1 = {alpha x^i G1} (n), BetaTauG1 = {beta x^i G1} (n), BetaG2 = beta G2 (192 bytes).  The caller
-    vouches for its shape and for its points lying in the subgroup (Points.in_subgroup)."""
+    vouches for its shape and for its points lying in the subgroup: Groth16SRSCheck tests both."""
 
     def __init__(self, TauG1: Points, TauG2: Points, AlphaTauG1: Points, BetaTauG1: Points, BetaG2: bytes):
         self.TauG1, self.TauG2, self.AlphaTauG1, self.BetaTauG1, self.BetaG2 = TauG1, TauG2, AlphaTauG1, BetaTauG1, BetaG2
+
+    @classmethod
+    def initial(cls, ctx: Context, m: int) -> "Groth16SRS":
+        """The string a ceremony starts from, tau = alpha = beta = 1, for m gates: 2m-1, m, m, m generators."""
+        ones = Poly.powers(ctx, 1, 2 * m - 1)
+        g1 = Points.from_scalars(ctx, G1, ones)
+        g2 = Points.from_scalars(ctx, G2, ones.slice(0, m))
+        return cls(g1, g2, g1.slice(0, m), g1.slice(0, m), g2.download(0, 1))
+
+    def truncate(self, n: int) -> "Groth16SRS":
+        """Views of the first 2n-1, n, n, n points: the shape NewGroth16SetupFromSRS wants for a circuit of n gates."""
+        return Groth16SRS(self.TauG1.slice(0, 2 * n - 1), self.TauG2.slice(0, n), self.AlphaTauG1.slice(0, n), self.BetaTauG1.slice(0, n),
+                          self.BetaG2)
 
     def _struct(self):
         s = _lib.Groth16Srs()
         s.tau_g1, s.tau_g2, s.alpha_tau_g1, s.beta_tau_g1 = self.TauG1._h, self.TauG2._h, self.AlphaTauG1._h, self.BetaTauG1._h
         C.memmove(s.beta_g2, self.BetaG2, 192)
         return s
+
+
+def Groth16SRSContribute(ctx: Context, srs: Groth16SRS, t: int, a: int, b: int):
+    """The string with tau multiplied by t, alpha by a and beta by b (ps_groth16_srs_contribute), and the contributor's public
+    share {"T2": t G2, "A2": a G2, "B2": b G2}.  t, a, b below r and non-zero; they are the caller's to draw and to delete."""
+    src = srs._struct()
+    out, share = _lib.Groth16Srs(), _lib.Groth16SrsShare()
+    _check(lib.ps_groth16_srs_contribute(ctx._h, C.byref(src), _be32(t), _be32(a), _be32(b), C.byref(out), C.byref(share)))
+    pts = [Points(ctx, C.c_void_p(getattr(out, f))) for f in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1")]
+    return Groth16SRS(*pts, bytes(out.beta_g2)), {"T2": bytes(share.t_g2), "A2": bytes(share.a_g2), "B2": bytes(share.b_g2)}
+
+
+def _rho_bytes(rhos: Sequence[int]) -> bytes:
+    return b"".join(int(v).to_bytes(32, "big") for v in rhos)
+
+
+def Groth16SRSCheck(ctx: Context, srs: Groth16SRS, rhos: Sequence[int], check_subgroup: bool = True) -> bool:
+    """Is the string well formed -- the powers of ONE tau in both groups, the same tau under alpha and beta, the same beta in G2
+    (ps_groth16_srs_check)?  rhos: weights below r drawn AFTER the string is fixed, at least (longest array - 1) of them
+    (LengthMismatch otherwise)."""
+    s = srs._struct()
+    ok = C.c_int(0)
+    _check(lib.ps_groth16_srs_check(ctx._h, C.byref(s), _rho_bytes(rhos), len(rhos), int(check_subgroup), C.byref(ok)))
+    return bool(ok.value)
+
+
+def Groth16SRSCheckUpdate(ctx: Context, before: Groth16SRS, after: Groth16SRS, share: dict, rhos: Sequence[int]) -> bool:
+    """Is `after` well formed and `before` with the (t, a, b) behind `share` folded in (ps_groth16_srs_check_update)?  `before`
+    is taken as checked; that the contributor knows t, a, b is for the ceremony protocol to establish."""
+    a, b = before._struct(), after._struct()
+    sh = _lib.Groth16SrsShare()
+    for name, key in (("t_g2", "T2"), ("a_g2", "A2"), ("b_g2", "B2")):
+        C.memmove(getattr(sh, name), share[key], 192)
+    ok = C.c_int(0)
+    _check(lib.ps_groth16_srs_check_update(ctx._h, C.byref(a), C.byref(b), C.byref(sh), _rho_bytes(rhos), len(rhos), C.byref(ok)))
+    return bool(ok.value)
 
 
 _CRS_ARRAYS = ("xi", "xi2", "io_lp", "nio_lp", "xi_t", "lxi", "lxi2", "lxi_t")

@@ -1981,3 +1981,4 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "pairing_dev.hpp"
 #include "verify_batch.inc"
 #include "srs_setup.inc"
+#include "srs_phase1.inc"

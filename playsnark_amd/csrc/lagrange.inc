@@ -111,45 +111,61 @@ extern "C" int ps_points_monomial_to_lagrange(ps_ctx* c, const ps_qap* q, const 
     return mono->group == PS_G1 ? monomial_to_lagrange_t<Fp>(c, q, mono, nodes == 1, out) : monomial_to_lagrange_t<Fp2>(c, q, mono, nodes == 1, out);
 }
 
-// Test hook (not in the header, like ps_debug_pair_add_probe): out[i] = k[i] * pts[i] by the scalar multiplication the conversion
-// above uses (ec_mul_glv: GLV split, fixed signed windows) -- so that its edge scalars (0, 1, lambda - 1, lambda, r - 1, digits
-// of -8 ...) are checked against the oracle one by one, not only through random twiddles (tests/test_prover_gpu.py).
+// out[i] = k[i] * pts[i], k: one Montgomery scalar per point, on the device (the caller orders their producer before c->stream's
+// next kernel).  The scalar multiplication the conversion above uses (ec_mul_glv: GLV split, fixed signed windows): the points
+// must lie in the subgroup of order r.  Canonical affine output; returns when the result is complete.
 template <class F>
-static int debug_points_scale_t(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, ps_points** out) {
+static int points_scale_each_t(ps_ctx* c, const ps_points* pts, const Fr* k_mont, ps_points** out) {
     typedef typename KernelField<F>::type KF;
     constexpr unsigned LN = FieldTraits<KF>::LANES;
     const size_t n = pts->n;
     hipStream_t st = c->stream;
     int rc = points_alloc(c, pts->group, n, out);
-    if (rc) return rc;
-    Xyzz<F>* buf = nullptr;
-    Fr* km = nullptr;
+    if (rc || n == 0) return rc;
+    char* buf = nullptr;  // n XYZZ points, then batch_to_affine's chain products
     auto bail = [&](const char* what, hipError_t err) {
         (void)hipStreamSynchronize(st);
         if (buf) (void)hipFree(buf);
-        if (km) (void)hipFree(km);
         ps_points_free(*out);
         *out = nullptr;
-        return fail(PS_ERR_HIP, std::string("ps_debug_points_scale: ") + what + ": " + hipGetErrorString(err));
+        return fail(PS_ERR_HIP, std::string("scaling a point array: ") + what + ": " + hipGetErrorString(err));
     };
     hipError_t e;
-    if ((e = hipMalloc((void**)&buf, sizeof(Xyzz<F>) * 2 * n)) != hipSuccess) return bail("hipMalloc", e);  // (batch_to_affine's chain products behind the n points)
-    if ((e = hipMalloc((void**)&km, sizeof(Fr) * n)) != hipSuccess) return bail("hipMalloc", e);
-    if (storage_wait_ready(pts->st, st) || storage_wait_ready(sc->st, st)) return bail("event wait", hipErrorUnknown);
-    hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(n)), dim3(256), 0, st, km, scalars_ptr(sc), (u64)n);
-    hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, buf);
-    hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, buf, (u32)n, (const Fr*)km, ~0ull);
-    batch_to_affine<F>(c, (char*)buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    if ((e = hipMalloc((void**)&buf, batch_affine_tmp_bytes(n, sizeof(Xyzz<F>)))) != hipSuccess) return bail("hipMalloc", e);
+    if (storage_wait_ready(pts->st, st)) return bail("event wait", hipErrorUnknown);
+    hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, (Xyzz<F>*)buf);
+    hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (Xyzz<F>*)buf, (u32)n, k_mont, ~0ull);
+    batch_to_affine<F>(c, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return bail("kernels", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return bail("run", e);
     (void)hipFree(buf);
-    (void)hipFree(km);
     return PS_OK;
+}
+static int points_scale_each(ps_ctx* c, const ps_points* pts, const Fr* k_mont, ps_points** out) {
+    return pts->group == PS_G1 ? points_scale_each_t<Fp>(c, pts, k_mont, out) : points_scale_each_t<Fp2>(c, pts, k_mont, out);
+}
+
+// Test hook (not in the header, like ps_debug_pair_add_probe): out[i] = k[i] * pts[i] for plain scalars -- so that the edge
+// scalars of ec_mul_glv (0, 1, lambda - 1, lambda, r - 1, digits of -8 ...) are checked against the oracle one by one, not only
+// through random twiddles (tests/test_prover_gpu.py).
+static int debug_points_scale(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, ps_points** out) {
+    const size_t n = pts->n;
+    Fr* km = nullptr;
+    hipError_t e = hipMalloc((void**)&km, sizeof(Fr) * n);
+    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_debug_points_scale: hipMalloc: ") + hipGetErrorString(e));
+    int rc = storage_wait_ready(sc->st, c->stream) ? fail(PS_ERR_HIP, "ps_debug_points_scale: event wait failed") : PS_OK;
+    if (!rc) {
+        hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(n)), dim3(256), 0, c->stream, km, scalars_ptr(sc), (u64)n);
+        rc = points_scale_each(c, pts, km, out);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(km);
+    return rc;
 }
 extern "C" int ps_debug_points_scale(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, ps_points** out) {
     if (!c || !pts || !sc || !out) return fail(PS_ERR_ARG, "ps_debug_points_scale: NULL argument");
     *out = nullptr;
     if (pts->n != sc->n || pts->n == 0) return fail(PS_ERR_LENGTH, "ps_debug_points_scale: one scalar per point, at least one");
     HIP_TRY(hipSetDevice(c->device));
-    return pts->group == PS_G1 ? debug_points_scale_t<Fp>(c, pts, sc, out) : debug_points_scale_t<Fp2>(c, pts, sc, out);
+    return debug_points_scale(c, pts, sc, out);
 }

@@ -289,6 +289,37 @@ inline bool Groth16CheckUpdate(Context& c, const ps_groth16_crs& before, const p
     return ok != 0;
 }
 
+// Phase 1, the making of the string itself.  [c, c s, .., c s^(n-1)] on the device (ps_scalars_powers); the caller frees it
+// with ps_scalars_free
+inline ps_scalars* Powers(Context& c, const Scalar& s, size_t n, const Scalar& coeff) {
+    ps_scalars* out = nullptr;
+    check(ps_scalars_powers(c.get(), s.data(), coeff.data(), n, &out));
+    return out;
+}
+using Groth16SRSShare = ps_groth16_srs_share;  // a contributor's public values: t G2, a G2, b G2
+// `in` with tau multiplied by t, alpha by a, beta by b (ps_groth16_srs_contribute), and the public share.  The caller frees the
+// four arrays of the result with ps_points_free; t, a, b are its to draw and to delete.
+inline Groth16SRS Groth16SRSContribute(Context& c, const Groth16SRS& in, const Scalar& t, const Scalar& a, const Scalar& b,
+                                       Groth16SRSShare* share) {
+    Groth16SRS out;
+    check(ps_groth16_srs_contribute(c.get(), &in, t.data(), a.data(), b.data(), &out, share));
+    return out;
+}
+// Is the string well formed?  rho_be32: nrho x 32 bytes drawn after the string is fixed, at least (longest array - 1) of them
+// (ps_groth16_srs_check)
+inline bool Groth16SRSCheck(Context& c, const Groth16SRS& srs, const uint8_t* rho_be32, size_t nrho, bool check_subgroup = true) {
+    int ok = 0;
+    check(ps_groth16_srs_check(c.get(), &srs, rho_be32, nrho, check_subgroup ? 1 : 0, &ok));
+    return ok != 0;
+}
+// Is `after` well formed and `before` with the (t, a, b) behind `share` folded in (ps_groth16_srs_check_update)?
+inline bool Groth16SRSCheckUpdate(Context& c, const Groth16SRS& before, const Groth16SRS& after, const Groth16SRSShare& share,
+                                  const uint8_t* rho_be32, size_t nrho) {
+    int ok = 0;
+    check(ps_groth16_srs_check_update(c.get(), &before, &after, &share, rho_be32, nrho, &ok));
+    return ok != 0;
+}
+
 // func NewPHGR13TrustedSetup(qap QAP) PHGR13Setup (pinochio.go:93), toxic waste drawn by the caller;
 // release the arrays with ps_phgr13_crs_free
 inline ps_phgr13_crs NewPHGR13TrustedSetup(Context& c, const QAP& q, const ps_phgr13_toxic& tw) {

@@ -594,6 +594,113 @@ func CheckUpdateHIP(before, after *HipGroth16) bool {
 }
 
 // ---------------------------------------------------------------------------------------
+// Phase 1: making and checking the string itself.  A ceremony starts from the trivial string (every point a generator),
+// every party folds a share (t, a, b) of its own into tau, alpha, beta and publishes (t G2, a G2, b G2), and anybody checks
+// every fold.  That a contributor KNOWS its t, a, b is for the ceremony protocol to establish, not for these calls.
+// ---------------------------------------------------------------------------------------
+
+// HipGroth16SRS is a phase-1 string resident on the device: folds and checks run on it without crossing the host.
+type HipGroth16SRS struct {
+	s C.ps_groth16_srs
+}
+
+// Groth16SRSShare holds a contributor's public values t G2, a G2, b G2.
+type Groth16SRSShare struct {
+	T2, A2, B2 Commit
+}
+
+// UploadGroth16SRS puts a string on the device.  Free() it when done.
+func UploadGroth16SRS(srs Groth16SRS) *HipGroth16SRS {
+	h := &HipGroth16SRS{}
+	h.s.tau_g1 = uploadPoints(C.PS_G1, srs.TauG1)
+	h.s.tau_g2 = uploadPoints(C.PS_G2, srs.TauG2)
+	h.s.alpha_tau_g1 = uploadPoints(C.PS_G1, srs.AlphaTauG1)
+	h.s.beta_tau_g1 = uploadPoints(C.PS_G1, srs.BetaTauG1)
+	copyTo(unsafe.Pointer(&h.s.beta_g2[0]), affineOf(C.PS_G2, srs.BetaG2))
+	return h
+}
+
+// Free releases the four arrays.
+func (h *HipGroth16SRS) Free() {
+	for _, p := range []*C.ps_points{h.s.tau_g1, h.s.tau_g2, h.s.alpha_tau_g1, h.s.beta_tau_g1} {
+		C.ps_points_free(p)
+	}
+	h.s = C.ps_groth16_srs{}
+}
+
+// PowersHIP returns [c, c s, .., c s^(n-1)] computed on the device (ps_scalars_powers).
+func PowersHIP(s, c Element, n int) Poly {
+	var h *C.ps_scalars
+	call(func() C.int { return C.ps_scalars_powers(hipCtx, u8(mustMarshalElement(s)), u8(mustMarshalElement(c)), C.size_t(n), &h) })
+	defer C.ps_scalars_free(h)
+	return downloadPoly(h)
+}
+
+func mustMarshalElement(e Element) []byte {
+	b, err := e.MarshalBinary()
+	if err != nil {
+		panic(err)
+	}
+	return b
+}
+
+// Groth16SRSContribute folds a share into the string: tau *= t, alpha *= a, beta *= b (ps_groth16_srs_contribute).  t, a
+// and b are drawn by the caller and must be forgotten afterwards.  The result is a new string; both are Free()d.
+func Groth16SRSContribute(in *HipGroth16SRS, t, a, b Element) (*HipGroth16SRS, Groth16SRSShare) {
+	out := &HipGroth16SRS{}
+	var sh C.ps_groth16_srs_share
+	call(func() C.int {
+		return C.ps_groth16_srs_contribute(hipCtx, &in.s, u8(mustMarshalElement(t)), u8(mustMarshalElement(a)),
+			u8(mustMarshalElement(b)), &out.s, &sh)
+	})
+	g2 := func(p *C.uint8_t) Commit { return pointFrom(C.PS_G2, bytesOf(unsafe.Pointer(p), g2Wire), zeroG2) }
+	return out, Groth16SRSShare{T2: g2(&sh.t_g2[0]), A2: g2(&sh.a_g2[0]), B2: g2(&sh.b_g2[0])}
+}
+
+// srsWeights draws one 128-bit weight per neighbouring pair of the longest array, after the string is in hand.
+func srsWeights(srs *HipGroth16SRS) ([]byte, int) {
+	n := 0
+	for _, p := range []*C.ps_points{srs.s.tau_g1, srs.s.tau_g2, srs.s.alpha_tau_g1, srs.s.beta_tau_g1} {
+		if l := int(C.ps_points_len(p)); l > n {
+			n = l
+		}
+	}
+	rho := make([]byte, 32*n)
+	for i := 0; i < n; i++ {
+		random.Bytes(rho[32*i+16:32*i+32], random.New())
+	}
+	return rho, n
+}
+
+// Groth16SRSCheck: is the string well formed -- the powers of one tau in both groups, the same tau under alpha and beta,
+// the same beta in G2 (ps_groth16_srs_check)?  checkSubgroup = false only for a string this process made itself.
+func Groth16SRSCheck(srs *HipGroth16SRS, checkSubgroup bool) bool {
+	rho, n := srsWeights(srs)
+	sub := C.int(0)
+	if checkSubgroup {
+		sub = 1
+	}
+	var ok C.int
+	call(func() C.int { return C.ps_groth16_srs_check(hipCtx, &srs.s, u8(rho), C.size_t(n), sub, &ok) })
+	return ok != 0
+}
+
+// Groth16SRSCheckUpdate: is `after` well formed and `before` with the (t, a, b) behind `share` folded in
+// (ps_groth16_srs_check_update)?  `before` is taken as checked.
+func Groth16SRSCheckUpdate(before, after *HipGroth16SRS, share Groth16SRSShare) bool {
+	var sh C.ps_groth16_srs_share
+	copyTo(unsafe.Pointer(&sh.t_g2[0]), affineOf(C.PS_G2, share.T2))
+	copyTo(unsafe.Pointer(&sh.a_g2[0]), affineOf(C.PS_G2, share.A2))
+	copyTo(unsafe.Pointer(&sh.b_g2[0]), affineOf(C.PS_G2, share.B2))
+	rho, n := srsWeights(after)
+	var ok C.int
+	call(func() C.int {
+		return C.ps_groth16_srs_check_update(hipCtx, &before.s, &after.s, &sh, u8(rho), C.size_t(n), &ok)
+	})
+	return ok != 0
+}
+
+// ---------------------------------------------------------------------------------------
 // Several GPUs from ONE process (a cgo caller cannot wrap a function call in one process per GPU, which is how
 // bench.py and playsnark_amd/dist.py scale): ps_msm_multi_device and ps_groth16_prove_multi run one context per
 // device side by side and fold the per-device partial sums on the host (SURVEY.md 8e, DESIGN.md section 7).
