@@ -535,6 +535,38 @@ int ps_pairing_product_is_one(ps_ctx* ctx, const ps_points* g1, const ps_points*
 int ps_groth16_verify_batch(ps_ctx* ctx, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs, size_t nproofs,
                             const uint8_t* rho_be32, int* ok);
 
+/* WHICH proofs of a batch are invalid.  Arguments, validation and error codes are exactly those of
+ * ps_groth16_verify_batch (lengths; canonical, non-zero rho; encoding, curve and subgroup of every point, ps_last_error()
+ * naming the proof of a bad encoding -- a malformed or off-subgroup proof fails the CALL with PS_ERR_ENCODING, there is no
+ * per-proof "malformed" verdict; an empty MSM queue), except the cap: nproofs <= 2^20 (PS_ERR_ARG beyond).
+ * valid[i] = 1 / 0 for proof i, *ninvalid = the number of zeros.  nproofs = 0: *ninvalid = 0 and nothing is written.  On an
+ * error *ninvalid = 0 and the contents of valid are unspecified.
+ * How: the batch equation restricted to a set S of proofs,
+ *     check(S): final_exp(prod_{i in S} miller(rho_i A_i, B_i) * miller(-(sum_S rho_i) alpha, beta2) * miller(-X_S, gamma)
+ *                         * miller(-sum_S rho_i C_i, delta2)) == 1,   X_S = sum_j (sum_S rho_i io_ij) IoLP_j,
+ * is multiplicative over disjoint unions.  The whole batch is checked exactly as ps_groth16_verify_batch checks it; if it
+ * is rejected, the sets of a binary tree over the proofs are checked from the root down, both halves of every failing set,
+ * from partial results kept on the device (no step passes over the proofs of a set again).
+ * Soundness: check({i}) is proof i's own equation (Groth16Verify, groth16.go:214-233) raised to rho_i != 0, and GT has prime
+ * order, so a verdict "invalid" is always exact; a verdict "valid" is wrong only if a set that passed hid a cancellation:
+ * probability <= nproofs / 2^bits(rho) per passed check, over the choice of rho (drawn after the proofs are fixed).
+ * Cost: an accepted batch costs what ps_groth16_verify_batch costs (one check, nothing else is launched); b invalid proofs
+ * among N cost at most 1 + 2 b ceil(log2 N) checks, each three host Miller loops and one final exponentiation, the sets of a
+ * level side by side on at most 16 host threads (profiles/verify_locate.txt).
+ * Device memory, kept by the context: 1 344 B per proof for the levels of the product tree; for a rejected batch also
+ * 448 B per proof for the sums of rho_i C_i and 64 B per proof and per (public input + 1) for the scalar sums; a batch that
+ * cannot get them fails with PS_ERR_HIP and a message that says so. */
+typedef struct {
+    uint32_t checks;   /* sets whose equation was evaluated, the whole batch included */
+    uint32_t levels;   /* depth reached below the root (0: batch accepted, or nproofs <= 1) */
+    uint32_t invalid;  /* proofs reported invalid */
+    uint32_t reserved;
+} ps_verify_locate_info;
+int ps_groth16_verify_batch_locate(ps_ctx* ctx, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs,
+                                   size_t nproofs, const uint8_t* rho_be32, uint8_t* valid /* nproofs bytes: 1 / 0 */,
+                                   size_t* ninvalid);
+int ps_groth16_verify_batch_locate_info(ps_ctx* ctx, ps_verify_locate_info* out); /* of the last locate call on ctx */
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ SYMBOLS = [
     "ps_qap_create", "ps_qap_free", "ps_qap_quotient", "ps_qap_is_valid", "ps_qap_interpolate", "ps_poly_mul",
     "ps_points_lincomb", "ps_msm_multi_device", "ps_groth16_prove_multi", "ps_points_monomial_to_lagrange",
     "ps_groth16_setup", "ps_phgr13_setup", "ps_phgr13_crs_free", "ps_groth16_prove", "ps_groth16_prove_shard", "ps_groth16_prove_local", "ps_phgr13_prove", "ps_phgr13_prove_shard", "ps_phgr13_prove_multi", "ps_groth16_verify", "ps_phgr13_verify", "ps_pairing_equal", "ps_prove_last_phase_ms",
-    "ps_pairing_product_is_one", "ps_groth16_verify_batch",
+    "ps_pairing_product_is_one", "ps_groth16_verify_batch", "ps_groth16_verify_batch_locate", "ps_groth16_verify_batch_locate_info",
     "ps_qap_column_sums", "ps_groth16_setup_from_srs", "ps_groth16_crs_contribute", "ps_groth16_crs_check_update",
     "ps_scalars_powers", "ps_groth16_srs_contribute", "ps_groth16_srs_check", "ps_groth16_srs_check_update",
 ]
@@ -42,6 +42,10 @@ PS_MSM_QUEUE = 4  # pending sums per context (include/playsnark_hip.h)
 class MsmInfo(C.Structure):
     _fields_ = [("window_bits", C.c_int), ("windows", C.c_int), ("entries", C.c_uint64),
                 ("buckets", C.c_uint64), ("slice", C.c_int), ("window_table", C.c_int)]
+
+
+class VerifyLocateInfo(C.Structure):  # ps_verify_locate_info
+    _fields_ = [("checks", C.c_uint32), ("levels", C.c_uint32), ("invalid", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Csr(C.Structure):
@@ -202,6 +206,8 @@ def _load():
     lib.ps_pairing_equal.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
     lib.ps_pairing_product_is_one.argtypes = [vp, vp, vp, i, C.POINTER(C.c_int)]
     lib.ps_groth16_verify_batch.argtypes = [vp, C.POINTER(Groth16Vk), vp, C.c_char_p, sz, C.c_char_p, C.POINTER(C.c_int)]
+    lib.ps_groth16_verify_batch_locate.argtypes = [vp, C.POINTER(Groth16Vk), vp, C.c_char_p, sz, C.c_char_p, C.c_char_p, C.POINTER(sz)]
+    lib.ps_groth16_verify_batch_locate_info.argtypes = [vp, C.POINTER(VerifyLocateInfo)]
     lib.ps_qap_column_sums.argtypes = [vp, vp, i, vp, pp]
     lib.ps_groth16_setup_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs)]
     lib.ps_groth16_crs_contribute.argtypes = [vp, C.POINTER(Groth16Crs), C.c_char_p, C.c_char_p, C.POINTER(Groth16Crs)]

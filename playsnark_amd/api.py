@@ -896,6 +896,39 @@ def Groth16VerifyBatch(ctx: Context, Alpha: bytes, Beta2: bytes, Gamma: bytes, D
             if not Groth16Verify(ctx, Alpha, Beta2, Gamma, Delta2, IoLP, p, io.slice(i * diff, diff))]
 
 
+def Groth16VerifyBatchLocate(ctx: Context, Alpha: bytes, Beta2: bytes, Gamma: bytes, Delta2: bytes, IoLP: Points, proofs: Sequence[Groth16Proof],
+                             ios: Sequence[Poly], rhos: Sequence[int]):
+    """The invalid proofs of a batch (ps_groth16_verify_batch_locate): the batch check of Groth16VerifyBatch, then, if it
+    fails, a bisection over partial results kept on the device -- at most 1 + 2 b ceil(log2 N) checks for b invalid proofs
+    among N, where locate=True of Groth16VerifyBatch verifies all N one by one.  Arguments as Groth16VerifyBatch.  Returns
+    (the bad indices in ascending order, info) with info = {"checks", "levels", "invalid"} of the call.  A verdict
+    "invalid" is exact; "valid" is relative to the weights, like the batch verdict itself."""
+    vk = _lib.Groth16Vk()
+    for name, src in (("alpha", Alpha), ("beta2", Beta2), ("gamma", Gamma), ("delta2", Delta2)):
+        C.memmove(getattr(vk, name), src, len(src))
+    vk.io_lp = IoLP._h
+    n = len(proofs)
+    if isinstance(ios, Poly):
+        io = ios
+    else:
+        if len(ios) != n:
+            raise LengthMismatch(f"{len(ios)} public-input vectors for {n} proofs")
+        io = Poly.upload(ctx, b"".join(v.download_bytes() for v in ios))
+    raw = b"".join(bytes(p.A) + bytes(p.B) + bytes(p.C) for p in proofs)
+    if len(rhos) != n:
+        raise LengthMismatch(f"{len(rhos)} weights for {n} proofs")
+    rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
+    valid = C.create_string_buffer(max(n, 1))
+    ninvalid = C.c_size_t(0)
+    _check(lib.ps_groth16_verify_batch_locate(ctx._h, C.byref(vk), io._h, raw, n, rho, valid, C.byref(ninvalid)))
+    raw_info = _lib.VerifyLocateInfo()
+    _check(lib.ps_groth16_verify_batch_locate_info(ctx._h, C.byref(raw_info)))
+    flags = valid.raw
+    bad = [i for i in range(n) if flags[i] == 0]
+    assert len(bad) == ninvalid.value
+    return bad, {"checks": raw_info.checks, "levels": raw_info.levels, "invalid": raw_info.invalid}
+
+
 def PHGR13Verify(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, p: "PHGR13Proof", io: Poly) -> bool:
     """func PHGR13Verify(vk PHGR13VerifKey, qap QAP, p PHGR13Proof, io Vector) bool (pinochio.go:281).
     vk_points: av, aw, ay, gamma, bgamma, bgamma2, yts as affine bytes."""

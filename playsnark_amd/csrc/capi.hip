@@ -14,6 +14,7 @@
 #include <cstring>
 #include <future>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "msm.hpp"
@@ -91,6 +92,11 @@ struct ps_ctx {
     DevBuf staging;                  // byte staging for uploads / downloads
     DevBuf vb_f12, vb_xyzz, vb_rho, vb_cols;  // the batch verifier's workspaces (verify_batch.inc): Miller values, rho A, rho, column sums
     float vb_ms[6] = {0, 0, 0, 0, 0, 0};  // stages of the last timed ps_groth16_verify_batch (ps_debug_verify_batch_stage_ms)
+    // ps_groth16_verify_batch_locate (verify_locate.inc): every level of the product tree, of the C tree and of the scalar tree,
+    // IoLP in XYZZ form, and the workspace of a round of the descent
+    DevBuf lc_f12, lc_pts, lc_rows, lc_iolp, lc_work;
+    ps_verify_locate_info lc_info{0, 0, 0, 0};  // of the last locate call (ps_groth16_verify_batch_locate_info)
+    float lc_ms[3] = {0, 0, 0};                 // ... and its descent's wall clock (ps_debug_verify_locate_ms)
     u32 simds = 0;                   // SIMDs of the device (how far k_miller_batch spreads a small batch), 0: not asked yet
     // ps_msm_be32 / ps_msm_i64 (seam S1: one upload per BlindEval call): the converted scalars of the call live in a vector
     // the context keeps, so a call does not pay a hipMalloc and a hipFree (which synchronises the device) of 32 bytes per
@@ -285,7 +291,8 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     if (c->tail) (void)hipStreamSynchronize(c->tail);
     for (DevBuf* b : {&c->counts, &c->offs, &c->bsum, &c->keys, &c->ranks, &c->sorted, &c->buckets, &c->parts,
                       &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->fb_table[0], &c->fb_table[1],
-                      &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols})
+                      &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols,
+                      &c->lc_f12, &c->lc_pts, &c->lc_rows, &c->lc_iolp, &c->lc_work})
         b->release();
     quotient_cache_free(c->qcache);
     if (c->up_scalars) ps_scalars_free(c->up_scalars);
@@ -1979,6 +1986,8 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "lagrange.inc"
 #include "pairing.inc"
 #include "pairing_dev.hpp"
+#include "locate_dev.hpp"
 #include "verify_batch.inc"
+#include "verify_locate.inc"
 #include "srs_setup.inc"
 #include "srs_phase1.inc"

@@ -5,6 +5,7 @@
 // The N Miller loops with distinct G2 arguments and their product run on the device (k_miller_batch, k_f12_product); the
 // three loops whose G2 argument is a key point, and the ONE final exponentiation, run on the host as in pairing.inc.
 // Staging memory is context buffers (DevBuf), not the stream-ordered pool: see batch_to_affine in capi.hip.
+// The body of ps_groth16_verify_batch is verify_batch_impl, which ps_groth16_verify_batch_locate (verify_locate.inc) calls too.
 
 constexpr size_t PS_VERIFY_BATCH_MAX = (size_t)1 << 24;
 
@@ -189,38 +190,51 @@ static size_t first_bad_encoding(const std::vector<uint8_t>& raw, size_t n, size
     return n;
 }
 
-extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs, size_t nproofs,
-                                       const uint8_t* rho_be32, int* ok) {
-    if (!c || !vk || !io || !ok || !vk->io_lp || (nproofs && (!proofs || !rho_be32))) return fail(PS_ERR_ARG, "ps_groth16_verify_batch: NULL argument");
-    *ok = 0;
+// What a REJECTED batch hands to the descent of ps_groth16_verify_batch_locate (verify_locate.inc) instead of freeing it:
+// the C_i and rho on the device (owned by the holder from then on; rho in Montgomery form stays in c->vb_rho until the
+// next call), and the key's points in the host field.
+struct VbKeep {
+    ps_points* c_pts = nullptr;
+    ps_scalars* rho = nullptr;
+    Affine<Fq> alpha;
+    Affine<Fq2> g2[3];  // beta2, gamma, delta2
+};
+// verify_locate.inc: k_miller_batch and the product tree with every level kept (c->lc_f12); *res is the root
+static int locate_miller_levels(ps_ctx* c, const Affine<Fp>* g1, const Affine<Fp2>* g2, size_t n, const pairing_dev::Fp12** res, VbClock* clk);
+
+// The batch check behind ps_groth16_verify_batch (fn = its name, max_n = 2^24) and ps_groth16_verify_batch_locate (its own
+// name and cap; keep != nullptr: the levels of the product tree are retained and a rejected batch fills *keep).  The
+// caller has checked its pointers and set *ok = 0.
+static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, const char* max_what, const ps_groth16_vk* vk, const ps_scalars* io,
+                             const uint8_t* proofs, size_t nproofs, const uint8_t* rho_be32, int* ok, VbKeep* keep) {
     VbClock clk(c);
-    if (c->q_len) return fail(PS_ERR_ARG, "ps_groth16_verify_batch: sums are pending on this context (ps_msm_finish them first)");
-    if (nproofs > PS_VERIFY_BATCH_MAX) return fail(PS_ERR_ARG, "ps_groth16_verify_batch: more than 2^24 proofs in one batch");
+    if (c->q_len) return fail(PS_ERR_ARG, fn + ": sums are pending on this context (ps_msm_finish them first)");
+    if (nproofs > max_n) return fail(PS_ERR_ARG, fn + ": more than " + max_what + " proofs in one batch");
     const size_t N = nproofs, diff = vk->io_lp->n;
     if (io->n != N * diff)
-        return fail(PS_ERR_LENGTH, "ps_groth16_verify_batch: " + std::to_string(io->n) + " public inputs for " + std::to_string(N) + " proofs of " +
+        return fail(PS_ERR_LENGTH, fn + ": " + std::to_string(io->n) + " public inputs for " + std::to_string(N) + " proofs of " +
                                        std::to_string(diff) + " each");
     if (N == 0) { *ok = 1; return PS_OK; }
     // weights: canonical, non-zero; their sum for the alpha term
     u32 rho_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (size_t i = 0; i < N; i++) {
         u32 w[8];
-        if (!be32_to_words(w, rho_be32 + 32 * i)) return fail(PS_ERR_ENCODING, "ps_groth16_verify_batch: rho[" + std::to_string(i) + "] is not below r");
+        if (!be32_to_words(w, rho_be32 + 32 * i)) return fail(PS_ERR_ENCODING, fn + ": rho[" + std::to_string(i) + "] is not below r");
         u32 any = 0;
         for (int k = 0; k < 8; k++) any |= w[k];
-        if (!any) return fail(PS_ERR_ARG, "ps_groth16_verify_batch: rho[" + std::to_string(i) + "] is zero (the proof would not be checked)");
+        if (!any) return fail(PS_ERR_ARG, fn + ": rho[" + std::to_string(i) + "] is zero (the proof would not be checked)");
         words_add_mod_r(rho_sum, w);
     }
     HIP_TRY(hipSetDevice(c->device));
     // the key: as in ps_groth16_verify
-    int rc = vk_array_in_subgroup(c, vk->io_lp, "ps_groth16_verify_batch");
+    int rc = vk_array_in_subgroup(c, vk->io_lp, fn.c_str());
     if (rc) return rc;
     Affine<Fp> alpha;
     Affine<Fp2> beta2, gamma, delta2;
     if (!read_g1(alpha, vk->alpha) || !read_g2(beta2, vk->beta2) || !read_g2(gamma, vk->gamma) || !read_g2(delta2, vk->delta2))
-        return fail(PS_ERR_ENCODING, "ps_groth16_verify_batch: bad point encoding in the verification key");
+        return fail(PS_ERR_ENCODING, fn + ": bad point encoding in the verification key");
     if (!all_in_subgroup({&alpha}, {&beta2, &gamma, &delta2}))
-        return fail(PS_ERR_ENCODING, "ps_groth16_verify_batch: verification-key point outside the order-r subgroup");
+        return fail(PS_ERR_ENCODING, fn + ": verification-key point outside the order-r subgroup");
     // the proofs: three arrays through the validating upload, then [r]P on the device
     std::vector<uint8_t> raw[3];
     const size_t wbs[3] = {96, 192, 96}, offs[3] = {0, 96, 288};
@@ -242,7 +256,7 @@ extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const
         rc = ps_points_upload(c, groups[k], raw[k].data(), N, PS_FMT_AFFINE, &arr[k]);
         if (rc == PS_ERR_ENCODING) {
             const size_t bad = groups[k] == PS_G1 ? first_bad_encoding<Fp>(raw[k], N, 96) : first_bad_encoding<Fp2>(raw[k], N, 192);
-            return done(fail(PS_ERR_ENCODING, std::string("ps_groth16_verify_batch: ") + names[k] + " of proof " + std::to_string(bad) +
+            return done(fail(PS_ERR_ENCODING, fn + ": " + names[k] + " of proof " + std::to_string(bad) +
                                                   " is not a canonical point on the curve"));
         }
         if (rc) return done(rc);
@@ -250,7 +264,7 @@ extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const
     for (int k = 0; k < 3; k++) {
         int in = 0;
         if ((rc = ps_points_check_subgroup(c, arr[k], &in))) return done(rc);
-        if (!in) return done(fail(PS_ERR_ENCODING, std::string("ps_groth16_verify_batch: a proof's ") + names[k] + " is outside the order-r subgroup"));
+        if (!in) return done(fail(PS_ERR_ENCODING, fn + ": a proof's " + names[k] + " is outside the order-r subgroup"));
     }
     clk.mark(0);
     // rho on the device: plain words for the sum over C, Montgomery form for the scaling of A and the column sums
@@ -262,18 +276,20 @@ extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const
     if ((rc = points_scale_g1(c, arr[0], rho_m, &ra))) return done(rc);
     clk.mark(1);
     const pairing_dev::Fp12* fdev = nullptr;
-    if ((rc = miller_product_launch(c, (const Affine<Fp>*)points_ptr(ra), (const Affine<Fp2>*)points_ptr(arr[1]), N, &fdev, &clk))) return done(rc);
+    rc = keep ? locate_miller_levels(c, (const Affine<Fp>*)points_ptr(ra), (const Affine<Fp2>*)points_ptr(arr[1]), N, &fdev, &clk)
+              : miller_product_launch(c, (const Affine<Fp>*)points_ptr(ra), (const Affine<Fp2>*)points_ptr(arr[1]), N, &fdev, &clk);
+    if (rc) return done(rc);
     // (the loops are only enqueued: the column sums and the two sums below queue up behind them while they run, and the
     // product is fetched after the sums)
     // X = sum_j (sum_i rho_i io_ij) IoLP_j and sum_i rho_i C_i: two sums instead of N
     uint8_t xb[96], cb[96];
     if (diff) {
-        if (storage_wait_ready(io->st, c->stream)) return done(fail(PS_ERR_HIP, "ps_groth16_verify_batch: event wait failed"));
+        if (storage_wait_ready(io->st, c->stream)) return done(fail(PS_ERR_HIP, fn + ": event wait failed"));
         const u32* tw = nullptr;
         if ((rc = weighted_columns(c, rho_m, scalars_ptr(io), N, diff, &tw))) return done(rc);
         if ((rc = scalars_alloc(c, diff, &t))) return done(rc);
         if (hipMemcpyAsync(t->st->p, tw, 32 * diff, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || storage_mark_ready(t->st, c->stream))
-            return done(fail(PS_ERR_HIP, "ps_groth16_verify_batch: copy of the column sums failed"));
+            return done(fail(PS_ERR_HIP, fn + ": copy of the column sums failed"));
         if ((rc = ps_msm(c, vk->io_lp, t, xb))) return done(rc);
     } else {
         write_identity(PS_G1, xb);
@@ -283,7 +299,7 @@ extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const
     pairing::Fp12 f;
     if ((rc = miller_product_fetch(c, fdev, &f))) return done(rc);
     Affine<Fp> x, sc;
-    if (!read_g1(x, xb) || !read_g1(sc, cb)) return done(fail(PS_ERR_ENCODING, "ps_groth16_verify_batch: bad point from a sum"));
+    if (!read_g1(x, xb) || !read_g1(sc, cb)) return done(fail(PS_ERR_ENCODING, fn + ": bad point from a sum"));
     // the host's share: (-(sum rho) alpha, beta2), (-X, gamma), (-sum rho_i C_i, delta2), one final exponentiation
     typedef Affine<Fq> H1;
     H1 sa;
@@ -303,5 +319,20 @@ extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const
     for (auto& l : loops) f = pairing::f12_mul(f, l.get());
     *ok = pairing::f12_eq(pairing::final_exp(f), pairing::f12_one()) ? 1 : 0;
     clk.mark(5);
+    if (keep && !*ok) {
+        keep->c_pts = arr[2];
+        keep->rho = rho;
+        arr[2] = nullptr;
+        rho = nullptr;
+        keep->alpha = affine_to_host<Fp>(alpha);
+        for (int k = 0; k < 3; k++) keep->g2[k] = tail[k].second;
+    }
     return done(PS_OK);
+}
+
+extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs, size_t nproofs,
+                                       const uint8_t* rho_be32, int* ok) {
+    if (!c || !vk || !io || !ok || !vk->io_lp || (nproofs && (!proofs || !rho_be32))) return fail(PS_ERR_ARG, "ps_groth16_verify_batch: NULL argument");
+    *ok = 0;
+    return verify_batch_impl(c, "ps_groth16_verify_batch", PS_VERIFY_BATCH_MAX, "2^24", vk, io, proofs, nproofs, rho_be32, ok, nullptr);
 }

@@ -251,6 +251,19 @@ inline bool Groth16VerifyBatch(Context& c, const ps_groth16_vk& vk, const Poly& 
     check(ps_groth16_verify_batch(c.get(), &vk, io.get(), proofs, nproofs, rho_be32, &ok));
     return ok != 0;
 }
+// The invalid proofs of a batch, by bisection over partial results kept on the device (ps_groth16_verify_batch_locate):
+// their indices in ascending order, empty for an accepted batch; *info (optional): checks, depth, count of the call
+inline std::vector<size_t> Groth16VerifyBatchLocate(Context& c, const ps_groth16_vk& vk, const Poly& io, const uint8_t* proofs, size_t nproofs,
+                                                    const uint8_t* rho_be32, ps_verify_locate_info* info = nullptr) {
+    std::vector<uint8_t> valid(nproofs ? nproofs : 1, 1);
+    size_t ninvalid = 0;
+    check(ps_groth16_verify_batch_locate(c.get(), &vk, io.get(), proofs, nproofs, rho_be32, valid.data(), &ninvalid));
+    if (info) check(ps_groth16_verify_batch_locate_info(c.get(), info));
+    std::vector<size_t> bad;
+    for (size_t i = 0; i < nproofs; i++)
+        if (!valid[i]) bad.push_back(i);
+    return bad;
+}
 // func PHGR13Verify(vk PHGR13VerifKey, qap QAP, p PHGR13Proof, io Vector) bool (pinochio.go:281)
 inline bool PHGR13Verify(Context& c, const ps_phgr13_vk& vk, const ps_phgr13_proof& p, const Poly& io) {
     int ok = 0;

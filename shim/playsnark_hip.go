@@ -502,6 +502,50 @@ func Groth16VerifyBatchHIP(hs *HipGroth16, proofs []Groth16Proof, ios []Vector) 
 	return ok != 0
 }
 
+// Groth16VerifyBatchLocateHIP names the invalid proofs of a batch (ps_groth16_verify_batch_locate): the batch check of
+// Groth16VerifyBatchHIP first, then, if it fails, a bisection over partial results kept on the device -- at most
+// 1 + 2 b ceil(log2 N) checks for b invalid proofs among N.  The weights are drawn here, as in Groth16VerifyBatchHIP.
+// Returns the indices of the invalid proofs in ascending order (nil for an accepted batch) and the number of checks.
+func Groth16VerifyBatchLocateHIP(hs *HipGroth16, proofs []Groth16Proof, ios []Vector) ([]int, int) {
+	if len(proofs) != len(ios) {
+		panic("Groth16VerifyBatchLocateHIP: one public-input vector per proof")
+	}
+	if len(proofs) == 0 {
+		return nil, 0
+	}
+	var all Vector
+	raw := make([]byte, 0, 384*len(proofs))
+	rho := make([]byte, 32*len(proofs))
+	for i, p := range proofs {
+		all = append(all, ios[i]...)
+		raw = append(raw, affineOf(C.PS_G1, p.A)...)
+		raw = append(raw, affineOf(C.PS_G2, p.B)...)
+		raw = append(raw, affineOf(C.PS_G1, p.C)...)
+		for zero := true; zero; {
+			random.Bytes(rho[32*i+16:32*i+32], random.New())
+			for _, b := range rho[32*i+16 : 32*i+32] {
+				zero = zero && b == 0
+			}
+		}
+	}
+	dio := uploadSolution(all)
+	defer C.ps_scalars_free(dio)
+	valid := make([]byte, len(proofs))
+	var ninvalid C.size_t
+	var info C.ps_verify_locate_info
+	call(func() C.int {
+		return C.ps_groth16_verify_batch_locate(hipCtx, &hs.vk, dio, u8(raw), C.size_t(len(proofs)), u8(rho), u8(valid), &ninvalid)
+	})
+	call(func() C.int { return C.ps_groth16_verify_batch_locate_info(hipCtx, &info) })
+	var bad []int
+	for i, v := range valid {
+		if v == 0 {
+			bad = append(bad, i)
+		}
+	}
+	return bad, int(info.checks)
+}
+
 // ---------------------------------------------------------------------------------------
 // A key from a powers-of-tau string: NewGroth16TrustedSetup (groth16.go:64-101) keeps alpha, beta, delta, x, gamma "for
 // testing and learning purpose" (groth16.go:13-14).  A deployment derives the circuit's key from a universal string
