@@ -21,6 +21,7 @@
 #include "quotient.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
+#include "share_ranges.hpp"
 
 namespace ps {
 #include "hostfield.inc"
@@ -1983,6 +1984,7 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 }
 #endif
 #include "prove.inc"
+#include "prove_shares.inc"
 #include "lagrange.inc"
 #include "pairing.inc"
 #include "pairing_dev.hpp"

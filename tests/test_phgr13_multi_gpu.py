@@ -151,6 +151,61 @@ def test_shards_fold_to_the_proof(ps_api, ctx, pr, n, world, lagrange):
         ps_api.PHGR13ProveShard(ek, q, dsol, world, world)
 
 
+@pytest.fixture(scope="module")
+def whole41(ps_api, ctx, pr):
+    """n = 41 on the session context: circuit, QAP, the raw key with lgsi, the solution and the oracle's proof."""
+    from oracle import restate as rs
+
+    rng = pr.SplitMix64(SEED + 7150)
+    c, sol = _circuit(rs, 41)
+    setup = rs.phgr13_setup(c, *[rng.fr() for _ in range(8)])
+    q = _qap(ps_api, ctx, c, _csr(c))
+    raw = _with_lgsi(ps_api, ctx, q, {f: getattr(setup.EK, f) for f in FIELDS})
+    return q, raw, sol, rs.phgr13_prove(setup.EK, c, sol, fast=True)
+
+
+@pytest.mark.parametrize("lagrange", [False, True], ids=["monomial", "lgsi"])
+@pytest.mark.parametrize("n", [3, 41])
+def test_the_unsharded_prover_is_rank_0_of_1(ps_api, ctx, pr, whole41, n, lagrange):
+    """ps_phgr13_prove and ps_phgr13_prove_shard(rank 0, world 1) give identical bytes (the oracle's), element by element,
+    not folded: with two values of h and two non-IO variables (n = 3) and with 40 (n = 41)."""
+    from oracle import restate as rs
+
+    if n == 41:
+        q, raw, sol, want = whole41
+    else:
+        rng = pr.SplitMix64(SEED + 7160)
+        c, sol = _circuit(rs, n)
+        setup = rs.phgr13_setup(c, *[rng.fr() for _ in range(8)])
+        want = rs.phgr13_prove(setup.EK, c, sol, fast=False)
+        q = _qap(ps_api, ctx, c, _csr(c))
+        raw = _with_lgsi(ps_api, ctx, q, {f: getattr(setup.EK, f) for f in FIELDS})
+    ek = _whole_key(ps_api, ctx, raw if lagrange else {f: raw[f] for f in FIELDS})
+    dsol = ps_api.Poly.upload(ctx, _sol_bytes(sol))
+    single = ps_api.PHGR13Prove(ek, q, dsol)
+    shard = ps_api.PHGR13ProveShard(ek, q, dsol, 0, 1)
+    _same(ps_api, single, want)
+    _same(ps_api, shard, want)
+
+
+def test_unsharded_apocalypse_then_a_proof_on_the_same_context(ps_api, ctx, pr, whole41):
+    """ps_phgr13_prove with a witness that violates a gate is "apocalypse"; the proof right after it on the same context is
+    the oracle's, and no sum is left pending (ps_msm refuses a context with pending sums)."""
+    q, raw, sol, want = whole41
+    ek = _whole_key(ps_api, ctx, raw)
+    bad = list(sol)
+    bad[5] = (bad[5] + 1) % pr.R
+    with pytest.raises(ps_api.Apocalypse):
+        ps_api.PHGR13Prove(ek, q, ps_api.Poly.upload(ctx, _sol_bytes(bad)))
+    dsol = ps_api.Poly.upload(ctx, _sol_bytes(sol))
+    _same(ps_api, ps_api.PHGR13Prove(ek, q, dsol), want)
+    with pytest.raises(ps_api.PlaysnarkError, match="nothing pending"):
+        ps_api.msm_finish(ctx, ps_api.G1)
+    rng = pr.SplitMix64(SEED + 7170)
+    h = ps_api.Poly.upload(ctx, [rng.fr() for _ in range(len(ek.gsi))])
+    assert len(h.BlindEval(ek.gsi)) == 96
+
+
 def test_refusals_and_recovery(ps_api, ctx, pool, pr):
     """Wrong ranges (LengthMismatch, naming the device), lgsi on some devices only and a G2 array where a G1 one belongs
     (PS_ERR_ARG), an unsatisfied witness ("apocalypse") from both entries -- and right after each, a correct proof on the

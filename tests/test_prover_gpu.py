@@ -575,6 +575,73 @@ def test_groth16_prove_over_rank_local_keys(ps_api, ctx, co, pr, ndev):
         cx.close()
 
 
+def test_groth16_multi_monomial_first_error_and_recovery(ps_api, ctx, co, pr):
+    """The monomial route of ps_groth16_prove_multi, three devices at n = 41, when two of them fail at run time and not in the
+    argument checks: the caller sees one error, its code and its text, and the next proof on the same contexts is the oracle's.
+    (i) Devices 1 and 2 hold a witness that violates a gate: the quotient stage (h on device 2) says "apocalypse".
+    (ii) Devices 1 and 2 cannot launch their sums, their contexts' queues being full of the caller's own pending sums
+    (PS_MSM_QUEUE of them, so the prover launches nothing there): the error is ps_msm_launch's, the caller's sums are still
+    pending afterwards, in order and with their values, and nothing of the prover's is.
+    (iii) Devices 0 and 2 fail differently, device 2 first in time: the error is device 0's."""
+    from oracle import restate as rs
+    from playsnark_amd import _lib
+
+    rng = pr.SplitMix64(SEED + 6100)
+    c, sol = rs.synthetic_circuit(41)
+    c = rs.SparseR1CS(c.nbVars, c.nbVars - 3, c.left, c.right, c.out)
+    r, s = rng.fr(), rng.fr()
+    tr = rs.groth16_setup(c, *[rng.fr() for _ in range(5)])
+    want = rs.groth16_prove(tr, c, sol, r, s)
+    ndev = 3
+    ctxs = [ctx] + [ps_api.Context(0) for _ in range(ndev - 1)]
+    devices = []
+    for d, cx in enumerate(ctxs):
+        q = _upload_circuit(ps_api, cx, c)
+        devices.append((_local_groth16_key(ps_api, cx, tr, c.nbGates, c.nbIO, d, ndev), q, ps_api.Poly.upload(cx, sol)))
+
+    def proves():
+        proof = ps_api.Groth16ProveMulti(devices, r, s)
+        assert (proof.A, proof.B, proof.C) == (want.A, want.B, want.C)
+
+    proves()
+    bad = list(sol)
+    bad[5] = (bad[5] + 1) % pr.R
+    with pytest.raises(ps_api.Apocalypse, match="^apocalypse$"):
+        ps_api.Groth16ProveMulti([devices[0]] + [(k, q, ps_api.Poly.upload(q.ctx, bad)) for k, q, _ in devices[1:]], r, s)
+    proves()
+
+    held = []
+    for cx, (key, _, _) in zip(ctxs[1:], devices[1:]):
+        sc = ps_api.Poly.upload(cx, [rng.fr() for _ in range(len(key.Xi))])
+        held.append((cx, sc, sc.BlindEval(key.Xi)))
+        for _ in range(_lib.PS_MSM_QUEUE):
+            ps_api.msm_launch(cx, key.Xi, sc)
+    with pytest.raises(ps_api.PlaysnarkError, match="ps_msm_launch: PS_MSM_QUEUE sums are already pending on this context$") as e:
+        ps_api.Groth16ProveMulti(devices, r, s)
+    assert e.value.code == _lib.PS_ERR_ARG
+    for cx, sc, value in held:
+        assert [ps_api.msm_finish(cx, ps_api.G1) for _ in range(_lib.PS_MSM_QUEUE)] == [value] * _lib.PS_MSM_QUEUE
+        with pytest.raises(ps_api.PlaysnarkError, match="nothing pending"):
+            ps_api.msm_finish(cx, ps_api.G1)
+    proves()
+
+    # (iii) two devices, two different faults: device 2's queue is full again (it fails before it launches anything), and device
+    # 0's key has a malformed Alpha, which only the addition of the fixed points reads -- the last thing device 0 does, behind
+    # its five sums.  The caller sees device 0's error, the lowest-numbered failing device's, not the first in time.
+    cx, sc, value = held[1]
+    for _ in range(_lib.PS_MSM_QUEUE):
+        ps_api.msm_launch(cx, devices[2][0].Xi, sc)
+    k0 = devices[0][0]
+    bad_key = ps_api.Groth16Setup(b"\xff" * 96, k0.Beta, k0.Delta, k0.Beta2, k0.Delta2, k0.Xi, k0.Xi2, k0.NioLP, k0.XiT)
+    with pytest.raises(ps_api.PlaysnarkError, match="ps_points_lincomb: bad point encoding$") as e:
+        ps_api.Groth16ProveMulti([(bad_key,) + devices[0][1:]] + devices[1:], r, s)
+    assert e.value.code == _lib.PS_ERR_ENCODING
+    assert [ps_api.msm_finish(cx, ps_api.G1) for _ in range(_lib.PS_MSM_QUEUE)] == [value] * _lib.PS_MSM_QUEUE
+    proves()
+    for cx in ctxs[1:]:
+        cx.close()
+
+
 def test_msm_over_shards_on_several_contexts(ps_api, ctx, co, pr):
     """ps_msm_multi_device: index-range shards on different contexts (devices) of one process, summed side by side."""
     from playsnark_amd.dist import shard_range
