@@ -54,7 +54,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_groth16_device.pk.  No struct changed, so the number stays: an entry point added within a revision is detected by
  *      its symbol (dlsym), not by ps_abi_version().  Likewise ps_qap_column_sums, ps_groth16_setup_from_srs (with the new
  *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update; then ps_scalars_powers,
- *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update. */
+ *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
+ *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -101,9 +102,10 @@ int ps_ctx_set_tables(ps_ctx* ctx, int enable);
 /* Memory policy of those tables.  A prover builds a table only when it fits: `bytes` >= 0 caps ONE table (0: none fit),
  * negative (the default) = what hipMemGetInfo reports as free, less a sixteenth of the device (at least 2 GiB) kept for
  * the sums' own workspaces.  A table that does not fit -- or whose allocation fails -- is not an error: the sums over that
- * array take the plain plan, which needs no memory beyond the array (ps_msm_info.window_table tells which ran), and the
- * array is not asked again until ps_points_precompute(p, -1) clears the mark.  An explicit ps_points_precompute still
- * fails with PS_ERR_HIP when the allocation fails. */
+ * array take the plain plan, which needs no memory beyond the array (ps_msm_info.window_table tells which ran).  The array
+ * is marked with what the asking context had to offer, and it IS asked again: by a later request with a larger budget, or
+ * once a quarter more device memory is free than at the time; ps_points_precompute(p, -1) clears the mark at once.  An
+ * explicit ps_points_precompute still fails with PS_ERR_HIP when the allocation fails. */
 int ps_ctx_set_table_budget(ps_ctx* ctx, long long bytes);
 /* *ok = 1 iff [r]P = O for every point of the array (GPU, ~400 group operations per point). */
 int ps_points_check_subgroup(ps_ctx* ctx, const ps_points* p, int* ok);
@@ -488,6 +490,49 @@ int ps_groth16_srs_check(ps_ctx* ctx, const ps_groth16_srs* srs, const uint8_t* 
  * from earlier ones) belongs to the ceremony protocol and is not part of this call.  Needs an empty MSM queue. */
 int ps_groth16_srs_check_update(ps_ctx* ctx, const ps_groth16_srs* before, const ps_groth16_srs* after, const ps_groth16_srs_share* share,
                                 const uint8_t* rho_be32, size_t nrho, int* ok);
+
+/* ---- the last link: is a key what its string makes of it? ----
+ * Every other step of the chain -- ps_groth16_srs_contribute -> ps_groth16_srs_check / _check_update -> ps_groth16_setup_from_srs
+ * -> ps_groth16_crs_contribute -> ps_groth16_crs_check_update -> prove -> verify -- has a cheap public check; that a circuit's key
+ * IS what ps_groth16_setup_from_srs makes from this string could only be known by deriving it again (five conversions over group
+ * elements) and comparing bytes.  But every key element is a fixed linear function of the string's points: a random linear
+ * combination of a key array equals ONE sum over the monomial string, with coefficients from an interpolation over scalars.
+ * Entry points added within revision 5 (found by symbol, no existing struct changed).
+ *
+ * *ok = 1 iff `lagr` is the Lagrange form of `mono` as ps_points_monomial_to_lagrange makes it (nodes = 0: the domain 1..n,
+ * cnt = n points; nodes = 1: the nodes n+1..2n-1, cnt = n-1), either group:
+ *   sum_j rho_j lagr[j] = sum_i c_i mono[i],   c = the coefficients of the polynomial with the values rho on those nodes
+ * -- one interpolation of cnt scalars, two sums, the results compared as canonical affine bytes.  An array of another length
+ * than cnt: PS_ERR_LENGTH; arrays of different groups, or sums pending on the context: PS_ERR_ARG.  rho: nrho >= cnt weights of
+ * 32 B (PS_ERR_LENGTH), canonical (PS_ERR_ENCODING), drawn by the caller AFTER both arrays are fixed (128 random bits each are
+ * enough); a wrong array passes with probability <= 2^-bits(rho). */
+int ps_points_lagrange_check(ps_ctx* ctx, const ps_qap* q, const ps_points* mono, const ps_points* lagr, int nodes,
+                             const uint8_t* rho_be32, size_t nrho, int* ok);
+/* *ok = 1 iff `key` is ps_groth16_setup_from_srs(q, srs) with SOME non-zero (delta, gamma) folded in -- the fresh key
+ * (delta = gamma = 1) and a ceremony's final key alike.  With T1, T2, A, B the string's arrays, diff = n_vars - n_io and
+ * z = prod_{j=1..n} (X - j):
+ *   alpha = A[0], beta = B[0], beta2 = srs.beta_g2 (bytes);  delta, delta2, gamma are not the identity and lie in the subgroup;
+ *   e(delta, G2) = e(G1, delta2);
+ *   xi = T1[:n], xi2 = T2[:n] (bytes, compared on the device: no array crosses PCIe);
+ *   lxi against xi, lxi2 against xi2 (nodes = 0) and lxi_t against xi_t (nodes = 1): the equation of ps_points_lagrange_check;
+ *     the three are optional (NULL: skipped, a monomial-only key has none);
+ *   e(sum_{i<n-1} rho_i xi_t[i], delta2) = e(sum_{m<2n-1} (rho * z)_m T1[m], G2),   rho * z the polynomial product;
+ *   for S = the IO variables (i < diff) and S = the rest, rho_S = rho[:n_vars] with the entries outside S zeroed, and cU, cV, cW
+ *   the interpolants on 1..n of L rho_S, R rho_S, O rho_S (ps_qap_interpolate with rho_S for the solution),
+ *   E_S = <cU, B> + <cV, A> + <cW, T1[:n]>:
+ *     e(sum_{i<diff} rho_i io_lp[i], gamma) = e(E_io, G2),     e(sum_{i>=diff} rho_i nio_lp[i-diff], delta2) = e(E_nio, G2).
+ * Each array enters exactly one equation that is linear in rho, so a key that differs from the derived one in any point passes
+ * with probability <= 2^-bits(rho) per equation.  About sixteen sums, eight scalar interpolations and four pairing equalities
+ * (each a product of its own, on host threads beside the device's work) where the derivation runs five conversions over group
+ * elements: 28 ms against 4.05 s at 2^16 gates, 105 ms with the subgroup tests (profiles/crs_check_from_srs.txt).
+ * The string's lengths as for ps_groth16_setup_from_srs (PS_ERR_LENGTH; n < 2: PS_ERR_ARG); the string itself is taken as
+ * checked (ps_groth16_srs_check).  rho: nrho >= max(n_vars, n) weights of 32 B (PS_ERR_LENGTH), canonical (PS_ERR_ENCODING),
+ * drawn by the caller AFTER string and key are fixed.  A key array of another length than this circuit's gives *ok = 0, not an
+ * error; a key without xi, xi2, io_lp, nio_lp or xi_t: PS_ERR_ARG.  check_subgroup != 0: the key's arrays go through
+ * ps_points_check_subgroup first, a point outside the subgroup gives *ok = 0 (0 only for a key the caller made itself).  A
+ * delta, delta2 or gamma that is no canonical point on the curve: PS_ERR_ENCODING.  Needs an empty MSM queue. */
+int ps_groth16_crs_check_from_srs(ps_ctx* ctx, const ps_qap* q, const ps_groth16_srs* srs, const ps_groth16_crs* key,
+                                  const uint8_t* rho_be32, size_t nrho, int check_subgroup, int* ok);
 
 /* ---- verifiers (host-side ate pairing; the IO commitments go through the GPU MSM) ---- */
 typedef struct { /* the verifier's part of Groth16Setup (groth16.go:30-61) */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "ps_pairing_product_is_one", "ps_groth16_verify_batch", "ps_groth16_verify_batch_locate", "ps_groth16_verify_batch_locate_info",
     "ps_qap_column_sums", "ps_groth16_setup_from_srs", "ps_groth16_crs_contribute", "ps_groth16_crs_check_update",
     "ps_scalars_powers", "ps_groth16_srs_contribute", "ps_groth16_srs_check", "ps_groth16_srs_check_update",
+    "ps_points_lagrange_check", "ps_groth16_crs_check_from_srs",
 ]
 
 
@@ -218,6 +219,8 @@ def _load():
     lib.ps_groth16_srs_check.argtypes = [vp, C.POINTER(Groth16Srs), C.c_char_p, sz, i, C.POINTER(C.c_int)]
     lib.ps_groth16_srs_check_update.argtypes = [vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Srs), C.POINTER(Groth16SrsShare), C.c_char_p, sz,
                                                 C.POINTER(C.c_int)]
+    lib.ps_points_lagrange_check.argtypes = [vp, vp, vp, vp, i, C.c_char_p, sz, C.POINTER(C.c_int)]
+    lib.ps_groth16_crs_check_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs), C.c_char_p, sz, i, C.POINTER(C.c_int)]
     return lib
 
 

@@ -210,6 +210,15 @@ class Points:
         _check(lib.ps_points_monomial_to_lagrange(qap.ctx._h, qap._h, self._h, nodes, C.byref(h)))
         return Points(qap.ctx, h)
 
+    def lagrange_check(self, qap: "QAP", lagr: "Points", rhos: Sequence[int], nodes: int = 0) -> bool:
+        """Is `lagr` the Lagrange form of this monomial-form array, as to_lagrange(qap, nodes) makes it -- without making it
+        (ps_points_lagrange_check: one interpolation over scalars and two sums)?  rhos: weights below r drawn AFTER both arrays
+        are fixed, at least as many as the arrays are long (LengthMismatch otherwise, and for an array of another length than
+        nbGates, or nbGates - 1 with nodes = 1)."""
+        ok = C.c_int(0)
+        _check(lib.ps_points_lagrange_check(qap.ctx._h, qap._h, self._h, lagr._h, nodes, _rho_bytes(rhos), len(rhos), C.byref(ok)))
+        return bool(ok.value)
+
     def precompute(self, window_bits: int = 0) -> "Points":
         """Build the window table 2^(c w) P of this resident array once (ps_points_precompute): later sums over it,
         or over slices of it, share one bucket set.  Returns self."""
@@ -695,6 +704,20 @@ def Groth16CheckUpdate(ctx: Context, before, after, rhos: Sequence[int]) -> bool
     rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
     ok = C.c_int(0)
     _check(lib.ps_groth16_crs_check_update(ctx._h, C.byref(a), C.byref(b), rho, len(rhos), C.byref(ok)))
+    return bool(ok.value)
+
+
+def Groth16CheckFromSRS(ctx: Context, qap: "QAP", srs: Groth16SRS, key_pair, rhos: Sequence[int], check_subgroup: bool = True) -> bool:
+    """Is the key `key_pair` = (tr, vk) what NewGroth16SetupFromSRS(qap, srs) makes, with SOME shares folded in (none, one
+    Groth16Contribute or several) -- without deriving it again (ps_groth16_crs_check_from_srs: sums over the string with
+    interpolated weights and four pairing equalities in place of five conversions over group elements)?  The Lagrange-form
+    arrays are checked when the key has them.  rhos: weights below r drawn AFTER string and key are fixed, at least
+    max(nbVars, nbGates) of them (LengthMismatch otherwise, and for a string of the wrong shape).  check_subgroup = False only
+    for a key this process made itself."""
+    s, k = srs._struct(), _crs_from_pair(*key_pair)
+    ok = C.c_int(0)
+    _check(lib.ps_groth16_crs_check_from_srs(ctx._h, qap._h, C.byref(s), C.byref(k), _rho_bytes(rhos), len(rhos), int(check_subgroup),
+                                             C.byref(ok)))
     return bool(ok.value)
 
 

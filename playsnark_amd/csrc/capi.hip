@@ -1993,3 +1993,4 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "verify_locate.inc"
 #include "srs_setup.inc"
 #include "srs_phase1.inc"
+#include "crs_check.inc"

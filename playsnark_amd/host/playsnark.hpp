@@ -74,6 +74,14 @@ class Points {
         check(ps_points_monomial_to_lagrange(ctx_->get(), qap.get(), h_, nodes, &h));
         return Points(*ctx_, h);
     }
+    // Is `lagr` what ToLagrange(qap, nodes) makes of this array, without making it?  rho_be32: nrho x 32 bytes drawn after both
+    // arrays are fixed, at least as many as the arrays are long (ps_points_lagrange_check)
+    template <class Q>
+    bool LagrangeCheck(const Q& qap, const Points& lagr, int nodes, const uint8_t* rho_be32, size_t nrho) const {
+        int ok = 0;
+        check(ps_points_lagrange_check(ctx_->get(), qap.get(), h_, lagr.h_, nodes, rho_be32, nrho, &ok));
+        return ok != 0;
+    }
     Bytes Download() const {
         Bytes out(size() * (group() == PS_G1 ? 96 : 192));
         if (!out.empty()) check(ps_points_download(ctx_->get(), h_, 0, size(), out.data()));
@@ -299,6 +307,14 @@ inline bool Groth16CheckUpdate(Context& c, const ps_groth16_crs& before, const p
                                size_t nrho) {
     int ok = 0;
     check(ps_groth16_crs_check_update(c.get(), &before, &after, rho_be32, nrho, &ok));
+    return ok != 0;
+}
+// Is `key` what NewGroth16SetupFromSRS(q, srs) makes, with SOME shares folded in -- without deriving it again?  rho_be32: nrho x
+// 32 bytes drawn after string and key are fixed, at least max(n_vars, n_gates) of them (ps_groth16_crs_check_from_srs)
+inline bool Groth16CheckFromSRS(Context& c, const QAP& q, const Groth16SRS& srs, const ps_groth16_crs& key, const uint8_t* rho_be32,
+                                size_t nrho, bool check_subgroup = true) {
+    int ok = 0;
+    check(ps_groth16_crs_check_from_srs(c.get(), q.get(), &srs, &key, rho_be32, nrho, check_subgroup ? 1 : 0, &ok));
     return ok != 0;
 }
 

@@ -744,6 +744,61 @@ func Groth16SRSCheckUpdate(before, after *HipGroth16SRS, share Groth16SRSShare) 
 	return ok != 0
 }
 
+// drawWeights returns n weights of 128 random bits each, as n x 32 big-endian bytes.
+func drawWeights(n int) []byte {
+	rho := make([]byte, 32*n)
+	for i := 0; i < n; i++ {
+		random.Bytes(rho[32*i+16:32*i+32], random.New())
+	}
+	return rho
+}
+
+// CheckFromSRSHIP: is `key` what NewHipGroth16FromSRS(srs, q) makes, with SOME shares folded in (none, one ContributeHIP or
+// several) -- without deriving it again (ps_groth16_crs_check_from_srs)?  The last link of the ceremony chain: sums over the
+// string with interpolated weights and four pairing equalities in place of five conversions over group elements.  The
+// weights are drawn here, after string and key are in hand.  checkSubgroup = false only for a key this process made itself.
+func CheckFromSRSHIP(srs *HipGroth16SRS, key *HipGroth16, checkSubgroup bool) bool {
+	q := key.qap
+	n := q.nbVars
+	if q.nbGates > n {
+		n = q.nbGates
+	}
+	rho := drawWeights(n)
+	sub := C.int(0)
+	if checkSubgroup {
+		sub = 1
+	}
+	var ok C.int
+	call(func() C.int {
+		return C.ps_groth16_crs_check_from_srs(hipCtx, q.h, &srs.s, &key.crs, u8(rho), C.size_t(n), sub, &ok)
+	})
+	return ok != 0
+}
+
+// LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
+// them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
+func (hs *HipGroth16) LagrangeCheckHIP() bool {
+	if hs.pk.lxi == nil || hs.pk.lxi2 == nil || hs.pk.lxi_t == nil {
+		return false
+	}
+	n := hs.qap.nbGates
+	rho := drawWeights(n)
+	pairs := []struct {
+		mono, lagr *C.ps_points
+		nodes      C.int
+	}{{hs.xi, hs.pk.lxi, 0}, {hs.xi2, hs.pk.lxi2, 0}, {hs.xiT, hs.pk.lxi_t, 1}}
+	for _, p := range pairs {
+		var ok C.int
+		call(func() C.int {
+			return C.ps_points_lagrange_check(hipCtx, hs.qap.h, p.mono, p.lagr, p.nodes, u8(rho), C.size_t(n), &ok)
+		})
+		if ok == 0 {
+			return false
+		}
+	}
+	return true
+}
+
 // ---------------------------------------------------------------------------------------
 // Several GPUs from ONE process (a cgo caller cannot wrap a function call in one process per GPU, which is how
 // bench.py and playsnark_amd/dist.py scale): ps_msm_multi_device and ps_groth16_prove_multi run one context per
