@@ -55,7 +55,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      its symbol (dlsym), not by ps_abi_version().  Likewise ps_qap_column_sums, ps_groth16_setup_from_srs (with the new
  *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update; then ps_scalars_powers,
  *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
- *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs. */
+ *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
+ *      ps_csr_fr) and ps_qap_wide_entries. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -209,8 +210,9 @@ int ps_ctx_set_timing(ps_ctx* ctx, int enable);
 int ps_msm_last_stage_ms(ps_ctx* ctx, float ms[PS_MSM_STAGES]);
 
 /* ---- QAP quotient: QAP.Quotient (qap.go:151-162) + computeAggregatePoly (qap.go:164-175) ----
- * The R1CS matrices (r1cs.go:78-101: rows = gates, columns = variables) are given in CSR with
- * int64 coefficients (the reference's Value = int, algebra.go:11).  The QAP domain is the
+ * The R1CS matrices (r1cs.go:78-101: rows = gates, columns = variables) are given in CSR, with
+ * int64 coefficients (the reference's Value = int, algebra.go:11; ps_csr) or with field elements
+ * (ps_csr_fr, below).  The QAP domain is the
  * reference's {1..n} (qap.go:42-55, algebra.go:256-258). */
 typedef struct {
     const uint32_t* row_ptr; /* n+1 */
@@ -220,6 +222,22 @@ typedef struct {
 int ps_qap_create(ps_ctx* ctx, size_t n_gates, size_t n_vars, size_t n_io, const ps_csr* L, const ps_csr* R,
                   const ps_csr* O, ps_qap** out);
 void ps_qap_free(ps_qap* q);
+/* The same, with coefficients that are field elements -- a hash's round constants, MDS entries, weights 2^k for k >= 64, or
+ * r - 1 written out instead of -1: 32-byte canonical big-endian values, the format of ps_scalars_upload.  Checks, codes and
+ * texts are ps_qap_create's; in addition a coefficient not below r is PS_ERR_ENCODING.  An explicit zero is allowed.  Both
+ * entries make the same ps_qap from the same circuit: every result is the same bytes.  Added within revision 5 (found by
+ * symbol). */
+typedef struct {
+    const uint32_t* row_ptr; /* n+1 */
+    const uint32_t* col;     /* nnz */
+    const uint8_t* val_be32; /* nnz x 32 B */
+} ps_csr_fr;
+int ps_qap_create_fr(ps_ctx* ctx, size_t n_gates, size_t n_vars, size_t n_io, const ps_csr_fr* L, const ps_csr_fr* R,
+                     const ps_csr_fr* O, ps_qap** out);
+/* out[0..2]: the entries of L, R, O that are WIDE.  A canonical value v counts with the signed magnitude min(v, r - v)
+ * (negative above (r - 1) / 2), and is wide iff that magnitude is >= 2^64.  Always 0 for a ps_qap made by ps_qap_create.
+ * Only ps_qap_column_sums depends on it. */
+int ps_qap_wide_entries(const ps_qap* q, size_t out[3]);
 /* sol: n_vars scalars.  Outputs (any may be NULL): A, B, C aggregate polynomials (n coefficients
  * each) and h (n-1 coefficients), all device-resident.  PS_ERR_NOT_DIVISIBLE <=> "apocalypse". */
 int ps_qap_quotient(ps_ctx* ctx, const ps_qap* q, const ps_scalars* sol, ps_scalars** A, ps_scalars** B,
@@ -407,10 +425,11 @@ int ps_points_monomial_to_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points
  *
  * Column sums of an R1CS matrix over points: out[i] = sum_j M[j][i] p[j], i < n_vars; M = L, R, O for which = 0, 1, 2; p has
  * n_gates points (PS_ERR_LENGTH otherwise), either group.  The per-variable sums of fullLinearPoly (groth16.go:254-264) when
- * only {l_j(x) G} is known, not x: the sparse matrix applied to a vector of points.  The coefficients are the int64 of
- * ps_csr, so a column costs at most 64 doublings plus one addition per set coefficient bit, not a 255-bit multiplication per
- * non-zero.  Identity points, repeated points and terms that cancel are handled; a variable that occurs in no gate gives the
- * identity.  Canonical affine output (the bytes ps_points_from_scalars gives for the same group element); caller frees. */
+ * only {l_j(x) G} is known, not x: the sparse matrix applied to a vector of points.  A coefficient enters as the signed
+ * magnitude min(v, r - v), and a column costs one doubling per bit of its own largest magnitude plus one addition per set
+ * coefficient bit: at most 64 doublings while the matrix has no wide entry (ps_qap_wide_entries; every ps_csr matrix), at
+ * most 254 for a column that holds one, and additions only for a column of +-1 in either case.  Identity points, repeated
+ * points and terms that cancel are handled; a variable that occurs in no gate gives the identity.  Canonical affine output (the bytes ps_points_from_scalars gives for the same group element); caller frees. */
 int ps_qap_column_sums(ps_ctx* ctx, const ps_qap* q, int which, const ps_points* p, ps_points** out);
 
 typedef struct {                   /* phase-1 output, the layout public ceremonies publish; n = n_gates */

@@ -34,6 +34,7 @@ SYMBOLS = [
     "ps_qap_column_sums", "ps_groth16_setup_from_srs", "ps_groth16_crs_contribute", "ps_groth16_crs_check_update",
     "ps_scalars_powers", "ps_groth16_srs_contribute", "ps_groth16_srs_check", "ps_groth16_srs_check_update",
     "ps_points_lagrange_check", "ps_groth16_crs_check_from_srs",
+    "ps_qap_create_fr", "ps_qap_wide_entries",
 ]
 
 
@@ -51,6 +52,10 @@ class VerifyLocateInfo(C.Structure):  # ps_verify_locate_info
 
 class Csr(C.Structure):
     _fields_ = [("row_ptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p)]
+
+
+class CsrFr(C.Structure):  # ps_csr_fr: val_be32 = nnz x 32 B, canonical big-endian Fr elements
+    _fields_ = [("row_ptr", C.c_void_p), ("col", C.c_void_p), ("val_be32", C.c_void_p)]
 
 
 class Groth16Pk(C.Structure):
@@ -179,6 +184,8 @@ def _load():
     lib.ps_qap_is_valid.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     lib.ps_msm_last_stage_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ps_qap_create.argtypes = [vp, sz, sz, sz, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), pp]
+    lib.ps_qap_create_fr.argtypes = [vp, sz, sz, sz, C.POINTER(CsrFr), C.POINTER(CsrFr), C.POINTER(CsrFr), pp]
+    lib.ps_qap_wide_entries.argtypes = [vp, C.POINTER(sz)]
     lib.ps_qap_free.argtypes = [vp]
     lib.ps_qap_free.restype = None
     lib.ps_qap_quotient.argtypes = [vp, vp, vp, pp, pp, pp, pp]

@@ -14,6 +14,7 @@ No arithmetic happens in this file: everything is a call into libplaysnark_hip.s
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from typing import Iterable, Optional, Sequence
 
 from . import _lib
@@ -406,21 +407,97 @@ def points_sum(group: int, raw: bytes) -> bytes:
 # -----------------------------------------------------------------------------------------
 # QAP / provers
 # -----------------------------------------------------------------------------------------
-def _csr(rows: Sequence[Sequence[tuple]]):
-    """rows[g] = [(col, int_value), ...] -> (Csr struct, keep-alive arrays)."""
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def _coef(v) -> int:
+    """A coefficient as a Python integer; a float or any other non-integer is a TypeError (never rounded, never narrowed)."""
+    if isinstance(v, int):
+        return v
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise TypeError("R1CS coefficients are integers, got %s" % type(v).__name__) from None
+
+
+def _fits_i64(vals) -> bool:
+    return all(_I64_MIN <= v <= _I64_MAX for v in vals)
+
+
+def _flat(rows: Sequence[Sequence[tuple]]):
+    """rows[g] = [(col, int_value), ...] -> (row_ptr, cols, vals) as Python lists; zero coefficients are dropped"""
     row_ptr = [0]
     cols, vals = [], []
     for r in rows:
         for col, v in r:
+            v = _coef(v)
             if v != 0:
                 cols.append(col)
                 vals.append(v)
         row_ptr.append(len(cols))
+    return row_ptr, cols, vals
+
+
+def _pack(row_ptr, cols, vals, fr: bool):
+    """(Csr or CsrFr struct, keep-alive arrays): int64 values, or 32-byte canonical big-endian values mod r"""
     a = (C.c_uint32 * len(row_ptr))(*row_ptr)
     b = (C.c_uint32 * max(len(cols), 1))(*cols)
-    c = (C.c_int64 * max(len(vals), 1))(*vals)
-    s = _lib.Csr(C.cast(a, C.c_void_p), C.cast(b, C.c_void_p), C.cast(c, C.c_void_p))
+    if fr:
+        c = C.create_string_buffer(b"".join((v % R_ORDER).to_bytes(32, "big") for v in vals), max(32 * len(vals), 32))
+    else:
+        c = (C.c_int64 * max(len(vals), 1))(*vals)
+    s = (_lib.CsrFr if fr else _lib.Csr)(C.cast(a, C.c_void_p), C.cast(b, C.c_void_p), C.cast(c, C.c_void_p))
     return s, (a, b, c)
+
+
+def _csr(rows: Sequence[Sequence[tuple]], fr: Optional[bool] = None):
+    """rows[g] = [(col, int_value), ...] -> (Csr struct, keep-alive arrays); a CsrFr struct of the values mod r when fr, or
+    (fr = None) when some value is no int64."""
+    row_ptr, cols, vals = _flat(rows)
+    return _pack(row_ptr, cols, vals, (not _fits_i64(vals)) if fr is None else fr)
+
+
+def _csr3(mats):
+    """The three matrices for one call: int64 structs (ps_qap_create) if every coefficient of all three is an int64, else
+    all three as field elements (ps_qap_create_fr).  -> (fr, structs, keep-alive)"""
+    flat = [_flat(rows) for rows in mats]
+    fr = not all(_fits_i64(f[2]) for f in flat)
+    packed = [_pack(*f, fr) for f in flat]
+    return fr, [p[0] for p in packed], [p[1] for p in packed]
+
+
+def _val_is_fr(val) -> bool:
+    """Is a val array of QAP.from_csr field elements (bytes, or uint8 of shape (nnz, 32)) rather than int64?"""
+    mv = memoryview(val)
+    if mv.format in ("e", "f", "d", "g"):
+        raise TypeError("R1CS coefficients are integers, got an array of floats")
+    return mv.itemsize == 1
+
+
+def _csr_arrays(triples, n_gates: int):
+    """QAP.from_csr's three (row_ptr, col, val) triples -> (fr, structs, keep-alive): copies of the buffers, val as int64 or
+    (fr) as 32-byte field elements"""
+    kinds = {_val_is_fr(val) for _, _, val in triples}
+    if len(kinds) != 1:
+        raise TypeError("the three val arrays must all be int64 or all be 32-byte field elements")
+    fr = kinds.pop()
+    structs, keep = [], []
+    for row_ptr, col, val in triples:
+        arrs = []
+        for a, ct in ((row_ptr, C.c_uint32), (col, C.c_uint32), (val, C.c_uint8 if fr else C.c_int64)):
+            raw = memoryview(a).tobytes()
+            if len(raw) % C.sizeof(ct):
+                raise ValueError("CSR array of the wrong element type")
+            buf = (ct * max(len(raw) // C.sizeof(ct), 1))()
+            C.memmove(buf, raw, len(raw))
+            arrs.append((buf, len(raw) // C.sizeof(ct)))
+        if arrs[0][1] != n_gates + 1:
+            raise LengthMismatch("row_ptr arrays of different lengths")
+        if fr and arrs[2][1] != 32 * arrs[1][1]:
+            raise LengthMismatch("val holds %d bytes, 32 per column index are %d" % (arrs[2][1], 32 * arrs[1][1]))
+        keep.append([a for a, _ in arrs])
+        structs.append((_lib.CsrFr if fr else _lib.Csr)(*[C.cast(a, C.c_void_p) for a, _ in arrs]))
+    return fr, structs, keep
 
 
 def dense_to_rows(m: Sequence[Sequence[int]]):
@@ -434,41 +511,25 @@ class QAP:
     def __init__(self, ctx: Context, nbVars: int, nbIO: int, left_rows, right_rows, out_rows):
         self.ctx = ctx
         self.nbVars, self.nbIO, self.nbGates = nbVars, nbIO, len(left_rows)
-        keep = []
-        structs = []
-        for rows in (left_rows, right_rows, out_rows):
-            s, k = _csr(rows)
-            structs.append(s)
-            keep.append(k)
+        fr, structs, keep = _csr3((left_rows, right_rows, out_rows))
         h = C.c_void_p()
-        _check(lib.ps_qap_create(ctx._h, self.nbGates, nbVars, nbIO, C.byref(structs[0]), C.byref(structs[1]),
-                                 C.byref(structs[2]), C.byref(h)))
+        _check((lib.ps_qap_create_fr if fr else lib.ps_qap_create)(ctx._h, self.nbGates, nbVars, nbIO, C.byref(structs[0]),
+                                                                   C.byref(structs[1]), C.byref(structs[2]), C.byref(h)))
         self._h = h
 
     @classmethod
     def from_csr(cls, ctx: Context, nbVars: int, nbIO: int, left, right, out) -> "QAP":
         """The three matrices as (row_ptr, col, val) triples of array-likes exposing the buffer protocol
-        (numpy uint32 / uint32 / int64): no per-row Python lists, for circuits of millions of gates."""
+        (numpy uint32 / uint32 / int64): no per-row Python lists, for circuits of millions of gates.  val may instead hold
+        field elements -- an (nnz, 32) uint8 array or a bytes of 32 * nnz, canonical big-endian values -- in all three
+        triples (ps_qap_create_fr); an array of floats is a TypeError."""
         self = cls.__new__(cls)
         self.ctx, self.nbVars, self.nbIO = ctx, nbVars, nbIO
         self.nbGates = len(left[0]) - 1
-        structs, keep = [], []
-        for row_ptr, col, val in (left, right, out):
-            arrs = []
-            for a, ct in ((row_ptr, C.c_uint32), (col, C.c_uint32), (val, C.c_int64)):
-                mv = memoryview(a).cast("B")
-                if mv.nbytes % C.sizeof(ct):
-                    raise ValueError("CSR array of the wrong element type")
-                buf = (ct * max(mv.nbytes // C.sizeof(ct), 1))()
-                C.memmove(buf, mv.tobytes(), mv.nbytes)
-                arrs.append(buf)
-            if len(arrs[0]) != self.nbGates + 1:
-                raise LengthMismatch("row_ptr arrays of different lengths")
-            keep.append(arrs)
-            structs.append(_lib.Csr(*[C.cast(a, C.c_void_p) for a in arrs]))
+        fr, structs, keep = _csr_arrays((left, right, out), self.nbGates)
         h = C.c_void_p()
-        _check(lib.ps_qap_create(ctx._h, self.nbGates, nbVars, nbIO, C.byref(structs[0]), C.byref(structs[1]),
-                                 C.byref(structs[2]), C.byref(h)))
+        _check((lib.ps_qap_create_fr if fr else lib.ps_qap_create)(ctx._h, self.nbGates, nbVars, nbIO, C.byref(structs[0]),
+                                                                   C.byref(structs[1]), C.byref(structs[2]), C.byref(h)))
         self._h = h
         return self
 
@@ -517,6 +578,13 @@ class QAP:
         h = C.c_void_p()
         _check(lib.ps_qap_column_sums(self.ctx._h, self._h, which, points._h, C.byref(h)))
         return Points(self.ctx, h)
+
+    def wide_entries(self) -> tuple:
+        """(left, right, out): how many entries of each matrix have a signed magnitude min(v, r - v) of 2^64 or more
+        (ps_qap_wide_entries).  (0, 0, 0) for every circuit with int64 coefficients."""
+        out = (C.c_size_t * 3)()
+        _check(lib.ps_qap_wide_entries(self._h, out))
+        return tuple(int(v) for v in out)
 
     def free(self):
         if getattr(self, "_h", None):

@@ -12,6 +12,11 @@ struct DevCsr {
     size_t nnz = 0;
     u32* long_rows = nullptr;  // rows with more than SPMV_LONG_ROW non-zeros
     u32 n_long = 0;
+    // The long rows of a TRANSPOSED matrix once more, split for the column sums over points (srs_setup.inc): those without a
+    // wide entry (coef_width.hpp), on the device, and on the host (row, first entry, entries) those that hold one
+    u32* long_narrow = nullptr;
+    u32 n_long_narrow = 0;
+    std::vector<u32> long_wide_h;
 };
 
 static void spmv_launch(hipStream_t st, const DevCsr& m, const Fr* x, Fr* y, u32 rows) {
@@ -36,6 +41,7 @@ struct ps_qap {
     // prover can cut the list to its range of rows
     u32* long_any = nullptr;
     std::vector<u32> long_any_h;
+    size_t wide[3] = {0, 0, 0};  // per matrix: entries whose signed magnitude needs more than 64 bits (coef_width.hpp)
     std::vector<void*> owned;
 };
 
@@ -61,38 +67,63 @@ extern "C" void ps_qap_free(ps_qap* q) {
     delete q;
 }
 
-extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps_csr* L, const ps_csr* R, const ps_csr* O,
-                             ps_qap** out) {
-    if (!c || !L || !R || !O || !out) return fail(PS_ERR_ARG, "ps_qap_create: NULL argument");
+static Fr fr_mont_from_be32(const uint8_t* be);
+
+// One matrix as either entry point gives it: int64 coefficients (ps_csr) or canonical big-endian field elements (ps_csr_fr)
+struct CsrSource {
+    const uint32_t* row_ptr;
+    const uint32_t* col;
+    const int64_t* val;       // ps_qap_create
+    const uint8_t* val_be32;  // ps_qap_create_fr
+    bool fr;
+};
+
+// ps_qap_create and ps_qap_create_fr: the argument checks (same order, codes and texts for both), the host preparation
+// and the upload.  Only the coefficient source differs.
+static int qap_create_from(ps_ctx* c, size_t n, size_t m, size_t nio, const CsrSource* src, ps_qap** out) {
     if (n == 0 || m == 0 || nio > m) return fail(PS_ERR_ARG, "ps_qap_create: bad dimensions");
     if (n >= (1ull << 27)) return fail(PS_ERR_ARG, "ps_qap_create: more than 2^27 gates is not supported");
     HIP_TRY(hipSetDevice(c->device));
     ps_qap* q = new ps_qap();
     q->device = c->device;
     q->n = n; q->m = m; q->nio = nio;
-    const ps_csr* src[3] = {L, R, O};
     int rc = PS_OK;
     for (int k = 0; k < 3; k++)
-        if (!src[k]->row_ptr) { delete q; return fail(PS_ERR_ARG, "ps_qap_create: NULL row_ptr"); }
+        if (!src[k].row_ptr) { delete q; return fail(PS_ERR_ARG, "ps_qap_create: NULL row_ptr"); }
     // Host preparation of the three matrices and of the factorial tables on four threads: coefficient
-    // conversion Value.ToFieldElement (curve.go:17-19) to Montgomery form, the transpose (counting sort
-    // by column; rows = variables, for the setups' per-variable sums) and the long-row lists.
+    // conversion (Value.ToFieldElement, curve.go:17-19, or the canonical bytes) to Montgomery form, the transpose
+    // (counting sort by column; rows = variables, for the setups' per-variable sums) and the long-row lists.
     struct HostCsr {
-        bool bad_col = false;
+        bool bad_col = false, bad_val = false, no_val = false;
+        size_t wide = 0;
         std::vector<Fr> vals, tv;
-        std::vector<u32> tp, tc, lr, lrT;
+        std::vector<u32> tp, tc, lr, lrT, lrT_narrow, lrT_wide;
     };
-    auto prepare = [n, m](const ps_csr* s) {
+    auto prepare = [n, m](const CsrSource* s) {
         HostCsr h;
         const size_t nnz = s->row_ptr[n];
         for (size_t e = 0; e < nnz; e++)
             if (s->col[e] >= m) { h.bad_col = true; return h; }
         h.vals.resize(nnz);
-        for (size_t e = 0; e < nnz; e++) {
-            int64_t v = s->val[e];
-            u64 mag = v < 0 ? (u64)0 - (u64)v : (u64)v;
-            Fr a = fr_from_u64(mag);
-            h.vals[e] = v < 0 ? fr_neg(a) : a;
+        std::vector<u32> wide_in_col(m, 0);
+        if (s->fr) {
+            if (nnz && !s->val_be32) { h.no_val = true; return h; }
+            for (size_t e = 0; e < nnz; e++) {
+                const uint8_t* be = s->val_be32 + 32 * e;
+                if (!coef_be32_is_canonical(be)) { h.bad_val = true; return h; }
+                u32 v[8], mag[8];
+                limbs_from_be<8>(v, be);
+                (void)coef_signed_magnitude(mag, v);
+                if (coef_is_wide(mag)) { h.wide++; wide_in_col[s->col[e]]++; }
+                h.vals[e] = fr_mont_from_be32(be);
+            }
+        } else {
+            for (size_t e = 0; e < nnz; e++) {
+                int64_t v = s->val[e];
+                u64 mag = v < 0 ? (u64)0 - (u64)v : (u64)v;
+                Fr a = fr_from_u64(mag);
+                h.vals[e] = v < 0 ? fr_neg(a) : a;
+            }
         }
         h.tp.assign(m + 1, 0); h.tc.resize(nnz); h.tv.resize(nnz);
         for (size_t e = 0; e < nnz; e++) h.tp[s->col[e] + 1]++;
@@ -105,13 +136,17 @@ extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps
                 h.tv[pos] = h.vals[e];
             }
         for (size_t r = 0; r < m; r++)
-            if (h.tp[r + 1] - h.tp[r] > SPMV_LONG_ROW) h.lrT.push_back((u32)r);
+            if (h.tp[r + 1] - h.tp[r] > SPMV_LONG_ROW) {
+                h.lrT.push_back((u32)r);
+                if (wide_in_col[r]) h.lrT_wide.insert(h.lrT_wide.end(), {(u32)r, h.tp[r], h.tp[r + 1] - h.tp[r]});
+                else h.lrT_narrow.push_back((u32)r);
+            }
         for (size_t r = 0; r < n; r++)
             if (s->row_ptr[r + 1] - s->row_ptr[r] > SPMV_LONG_ROW) h.lr.push_back((u32)r);
         return h;
     };
     std::future<HostCsr> prep[3];
-    for (int k = 0; k < 3; k++) prep[k] = std::async(std::launch::async, prepare, src[k]);
+    for (int k = 0; k < 3; k++) prep[k] = std::async(std::launch::async, prepare, &src[k]);
     std::future<FactTables> facts = std::async(std::launch::async, fact_tables, qap_np(n));
     auto upload = [&](auto** dst, const auto& v) -> int {
         typedef typename std::remove_reference<decltype(v[0])>::type T;
@@ -125,8 +160,11 @@ extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps
         HostCsr h = prep[k].get();  // always collected, also after an error
         if (rc) continue;
         if (h.bad_col) { rc = fail(PS_ERR_ARG, "ps_qap_create: column index out of range"); continue; }
-        const ps_csr* s = src[k];
+        if (h.no_val) { rc = fail(PS_ERR_ARG, "ps_qap_create_fr: NULL val_be32"); continue; }
+        if (h.bad_val) { rc = fail(PS_ERR_ENCODING, "ps_qap_create_fr: coefficient not below r"); continue; }
+        const CsrSource* s = &src[k];
         const size_t nnz = s->row_ptr[n];
+        q->wide[k] = h.wide;
         DevCsr& d = q->mat[k];
         DevCsr& t = q->matT[k];
         d.nnz = t.nnz = nnz;
@@ -143,6 +181,9 @@ extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps
         if ((rc = upload(&t.val, h.tv))) continue;
         if (d.n_long && (rc = upload(&d.long_rows, h.lr))) continue;
         if (t.n_long && (rc = upload(&t.long_rows, h.lrT))) continue;
+        t.n_long_narrow = (u32)h.lrT_narrow.size();
+        if (t.n_long_narrow && (rc = upload(&t.long_narrow, h.lrT_narrow))) continue;
+        t.long_wide_h = h.lrT_wide;
         q->long_any_h.insert(q->long_any_h.end(), h.lr.begin(), h.lr.end());
     }
     if (rc == PS_OK && !q->long_any_h.empty()) {
@@ -168,6 +209,31 @@ extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps
         return rc;
     }
     *out = q;
+    return PS_OK;
+}
+
+extern "C" int ps_qap_create(ps_ctx* c, size_t n, size_t m, size_t nio, const ps_csr* L, const ps_csr* R, const ps_csr* O,
+                             ps_qap** out) {
+    if (!c || !L || !R || !O || !out) return fail(PS_ERR_ARG, "ps_qap_create: NULL argument");
+    const CsrSource src[3] = {{L->row_ptr, L->col, L->val, nullptr, false},
+                                {R->row_ptr, R->col, R->val, nullptr, false},
+                                {O->row_ptr, O->col, O->val, nullptr, false}};
+    return qap_create_from(c, n, m, nio, src, out);
+}
+
+// The same circuit with coefficients given as field elements: 32-byte canonical big-endian values (ps_scalars_upload's format)
+extern "C" int ps_qap_create_fr(ps_ctx* c, size_t n, size_t m, size_t nio, const ps_csr_fr* L, const ps_csr_fr* R, const ps_csr_fr* O,
+                                ps_qap** out) {
+    if (!c || !L || !R || !O || !out) return fail(PS_ERR_ARG, "ps_qap_create: NULL argument");
+    const ps_csr_fr* in[3] = {L, R, O};
+    CsrSource src[3];
+    for (int k = 0; k < 3; k++) src[k] = {in[k]->row_ptr, in[k]->col, nullptr, in[k]->val_be32, true};
+    return qap_create_from(c, n, m, nio, src, out);
+}
+
+extern "C" int ps_qap_wide_entries(const ps_qap* q, size_t out[3]) {
+    if (!q || !out) return fail(PS_ERR_ARG, "ps_qap_wide_entries: NULL argument");
+    for (int k = 0; k < 3; k++) out[k] = q->wide[k];
     return PS_OK;
 }
 

@@ -26,23 +26,60 @@ static int column_sums_t(ps_ctx* c, const ps_qap* q, int which, const ps_points*
         if (code) { ps_points_free(*out); *out = nullptr; }
         return code;
     };
+    const bool wide = q->wide[which] != 0;  // (ec_spmv.hpp: four magnitude words per entry instead of one)
     hipError_t e;
     if ((e = hipMalloc((void**)&buf, batch_affine_tmp_bytes(m, sizeof(Xyzz<F>)))) != hipSuccess ||
-        (e = hipMalloc((void**)&mag, sizeof(u64) * std::max<size_t>(nnz, 1))) != hipSuccess ||
+        (e = hipMalloc((void**)&mag, sizeof(u64) * (wide ? 4 : 1) * std::max<size_t>(nnz, 1))) != hipSuccess ||
         (e = hipMalloc((void**)&cs, sizeof(u32) * std::max<size_t>(nnz, 1))) != hipSuccess)
         return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMalloc: ") + hipGetErrorString(e)));
     if (storage_wait_ready(p->st, st)) return done(fail(PS_ERR_HIP, "ps_qap_column_sums: event wait failed"));
     const Affine<F>* pts = (const Affine<F>*)points_ptr(p);
-    if (nnz) hipLaunchKernelGGL(k_colsum_coef, dim3(nblk(nnz)), dim3(256), 0, st, (const Fr*)t.val, (const u32*)t.col, (u32)nnz, mag, cs);
-    hipLaunchKernelGGL(k_colsum_rows<KF>, dim3(nblocks(m * LN)), dim3(256), 0, st, (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, pts, (u32)m,
-                       (Xyzz<F>*)buf);
-    if (t.n_long)
-        hipLaunchKernelGGL(k_colsum_long<KF>, dim3(t.n_long), dim3(COLSUM_LONG_THREADS), sizeof(Xyzz<F>) * (COLSUM_LONG_THREADS / LN), st,
-                           (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, pts, (const u32*)t.long_rows, (Xyzz<F>*)buf);
+    if (!wide) {
+        if (nnz) hipLaunchKernelGGL(k_colsum_coef, dim3(nblk(nnz)), dim3(256), 0, st, (const Fr*)t.val, (const u32*)t.col, (u32)nnz, mag, cs);
+        hipLaunchKernelGGL(k_colsum_rows<KF>, dim3(nblocks(m * LN)), dim3(256), 0, st, (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, pts, (u32)m,
+                           (Xyzz<F>*)buf);
+        if (t.n_long)
+            hipLaunchKernelGGL(k_colsum_long<KF>, dim3(t.n_long), dim3(COLSUM_LONG_THREADS), sizeof(Xyzz<F>) * (COLSUM_LONG_THREADS / LN), st,
+                               (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, pts, (const u32*)t.long_rows, (Xyzz<F>*)buf);
+    } else {
+        hipLaunchKernelGGL(k_colsum_coef_wide, dim3(nblk(nnz)), dim3(256), 0, st, (const Fr*)t.val, (const u32*)t.col, (u32)nnz, mag, cs);
+        hipLaunchKernelGGL(k_colsum_rows_wide<KF>, dim3(nblocks(m * LN)), dim3(256), 0, st, (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs,
+                           (u32)nnz, pts, (u32)m, (Xyzz<F>*)buf);
+        if (t.n_long_narrow)  // long rows without a wide entry: one workgroup each, at most 64 planes
+            hipLaunchKernelGGL(k_colsum_long_wide<KF>, dim3(t.n_long_narrow), dim3(COLSUM_LONG_THREADS), sizeof(Xyzz<F>) * (COLSUM_LONG_THREADS / LN), st,
+                               (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, (u32)nnz, pts, (const u32*)t.long_narrow, (Xyzz<F>*)buf);
+        for (size_t k = 0; k < t.long_wide_h.size(); k += 3)  // long rows with one: the identity here, their sum below
+            if ((e = hipMemsetAsync(buf + sizeof(Xyzz<F>) * t.long_wide_h[k], 0, sizeof(Xyzz<F>), st)) != hipSuccess)
+                return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemsetAsync: ") + hipGetErrorString(e)));
+    }
     batch_to_affine<F>(c, buf, m, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: kernels: ") + hipGetErrorString(e)));
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: run: ") + hipGetErrorString(e)));
-    return done(PS_OK);
+    // A long row that holds a wide entry is a multi-scalar multiplication, sum_e v_e P[col_e], of thousands of full-width
+    // terms (every round constant of a hash multiplies `const`).  k_colsum_long_wide took 1.33 s for the 65 528 wide entries of
+    // R's `const` column of a 2^16-gate MiMC circuit, 2 000 x all other work of the three column sums; the library's own sum
+    // takes 3.3 ms for it, gather and conversion included (profiles/column_sums_wide.txt).  So: the row's points gathered
+    // (k_gather_words), its coefficients as the scalars, ps_msm -- bit-exact on identities, repeated and opposite points.
+    if (wide)
+        for (size_t k = 0; k < t.long_wide_h.size() && rc == PS_OK; k += 3) {
+            const u32 row = t.long_wide_h[k], first = t.long_wide_h[k + 1], len = t.long_wide_h[k + 2];
+            constexpr u32 W = sizeof(Affine<F>) / 4;
+            ps_points* gp = nullptr;
+            ps_scalars* sc = nullptr;
+            uint8_t wire[192];
+            if ((rc = points_alloc(c, p->group, len, &gp)) == PS_OK) {
+                hipLaunchKernelGGL(k_gather_words, dim3(nblocks((size_t)len * W)), dim3(256), 0, st, (const u32*)pts, (const u32*)t.col + first, len,
+                                   (u64)W, (u64)0, W, (u32*)gp->st->p);
+                if ((rc = scalars_from_mont(c, t.val + first, len, &sc)) == PS_OK) rc = ps_msm(c, gp, sc, wire);
+            }
+            Affine<F> sum;
+            if (rc == PS_OK && !read_affine(sum, wire)) rc = fail(PS_ERR_HIP, "ps_qap_column_sums: the sum of a long row is no point");
+            if (rc == PS_OK && (e = hipMemcpy((char*)(*out)->st->p + sizeof(Affine<F>) * row, &sum, sizeof sum, hipMemcpyHostToDevice)) != hipSuccess)
+                rc = fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemcpy: ") + hipGetErrorString(e));
+            ps_scalars_free(sc);
+            ps_points_free(gp);
+        }
+    return done(rc);
 }
 
 extern "C" int ps_qap_column_sums(ps_ctx* c, const ps_qap* q, int which, const ps_points* p, ps_points** out) {

@@ -151,6 +151,26 @@ class QAP {
         ps_csr o{out.row_ptr.data(), out.col.data(), out.val.data()};
         check(ps_qap_create(c.get(), left.row_ptr.size() - 1, nbVars, nbIO, &l, &r, &o, &h_));
     }
+    // The same circuit with coefficients that are field elements (ps_qap_create_fr): val holds one canonical big-endian
+    // Scalar per entry.  A coefficient not below r throws (PS_ERR_ENCODING).
+    struct CsrFr {
+        std::vector<uint32_t> row_ptr, col;
+        std::vector<Scalar> val;
+    };
+    QAP(Context& c, size_t nbVars, size_t nbIO, const CsrFr& left, const CsrFr& right, const CsrFr& out) : ctx_(&c) {
+        static_assert(sizeof(Scalar) == 32, "a Scalar is 32 bytes, so a vector of them is the val_be32 array");
+        auto bytes = [](const CsrFr& m) { return m.val.empty() ? nullptr : m.val[0].data(); };
+        ps_csr_fr l{left.row_ptr.data(), left.col.data(), bytes(left)};
+        ps_csr_fr r{right.row_ptr.data(), right.col.data(), bytes(right)};
+        ps_csr_fr o{out.row_ptr.data(), out.col.data(), bytes(out)};
+        check(ps_qap_create_fr(c.get(), left.row_ptr.size() - 1, nbVars, nbIO, &l, &r, &o, &h_));
+    }
+    // entries of left, right, out whose signed magnitude min(v, r - v) needs more than 64 bits (ps_qap_wide_entries)
+    std::array<size_t, 3> wide_entries() const {
+        std::array<size_t, 3> out{};
+        check(ps_qap_wide_entries(h_, out.data()));
+        return out;
+    }
     ~QAP() { ps_qap_free(h_); }
     QAP(const QAP&) = delete;
     QAP& operator=(const QAP&) = delete;

@@ -322,6 +322,75 @@ func NewHipQAP(circuit R1CS) *HipQAP {
 	return q
 }
 
+// FrCsr is one R1CS matrix (rows = gates) whose coefficients are field elements: Val[k] is the canonical 32-byte big-endian
+// value of entry k (the format of kyber's Scalar.MarshalBinary).  The reference's Value is an int (algebra.go:11); a front end
+// that emits round constants, MDS entries or weights 2^k for k >= 64 needs this form.
+type FrCsr struct {
+	RowPtr []uint32 // nbGates + 1
+	Col    []uint32 // nnz
+	Val    [][32]byte
+}
+
+type cCsrFr struct {
+	csr         C.ps_csr_fr
+	rp, col, va unsafe.Pointer
+}
+
+func newCsrFr(m FrCsr) *cCsrFr {
+	nnz := len(m.Col)
+	if len(m.Val) != nnz {
+		panic(fmt.Sprintf("FrCsr: %d column indices and %d values", nnz, len(m.Val)))
+	}
+	c := &cCsrFr{
+		rp:  C.malloc(C.size_t(4 * len(m.RowPtr))),
+		col: C.malloc(C.size_t(4*nnz + 4)),
+		va:  C.malloc(C.size_t(32*nnz + 32)),
+	}
+	rp := (*[1 << 30]C.uint32_t)(c.rp)[:len(m.RowPtr):len(m.RowPtr)]
+	col := (*[1 << 30]C.uint32_t)(c.col)[: nnz+1 : nnz+1]
+	va := (*[1 << 30]byte)(c.va)[: 32*nnz+32 : 32*nnz+32]
+	for g, v := range m.RowPtr {
+		rp[g] = C.uint32_t(v)
+	}
+	for k := 0; k < nnz; k++ {
+		col[k] = C.uint32_t(m.Col[k])
+		copy(va[32*k:32*k+32], m.Val[k][:])
+	}
+	c.csr.row_ptr = (*C.uint32_t)(c.rp)
+	c.csr.col = (*C.uint32_t)(c.col)
+	c.csr.val_be32 = (*C.uint8_t)(c.va)
+	return c
+}
+
+func (c *cCsrFr) free() {
+	C.free(c.rp)
+	C.free(c.col)
+	C.free(c.va)
+}
+
+// NewHipQAPFr is NewHipQAP for matrices with field coefficients (ps_qap_create_fr).  A coefficient not below r panics
+// (PS_ERR_ENCODING), as does a column index out of range.
+func NewHipQAPFr(nbVars, nbIO int, left, right, out FrCsr) *HipQAP {
+	if len(left.RowPtr) == 0 || len(right.RowPtr) != len(left.RowPtr) || len(out.RowPtr) != len(left.RowPtr) {
+		panic("NewHipQAPFr: the three matrices need the same, non-zero number of gates")
+	}
+	l, r, o := newCsrFr(left), newCsrFr(right), newCsrFr(out)
+	defer l.free()
+	defer r.free()
+	defer o.free()
+	q := &HipQAP{nbVars: nbVars, nbIO: nbIO, nbGates: len(left.RowPtr) - 1}
+	call(func() C.int { return C.ps_qap_create_fr(hipCtx, C.size_t(q.nbGates), C.size_t(q.nbVars), C.size_t(q.nbIO), &l.csr, &r.csr, &o.csr, &q.h) })
+	return q
+}
+
+// WideEntries: how many entries of left, right and out have a signed magnitude min(v, r - v) of 2^64 or more
+// (ps_qap_wide_entries); 0, 0, 0 for every circuit made by NewHipQAP.
+func (q *HipQAP) WideEntries() [3]int {
+	var w [3]C.size_t
+	call(func() C.int { return C.ps_qap_wide_entries(q.h, &w[0]) })
+	return [3]int{int(w[0]), int(w[1]), int(w[2])}
+}
+
 func (q *HipQAP) Free() { C.ps_qap_free(q.h) }
 
 // QuotientHIP replaces `func (q QAP) Quotient(sol Vector) Poly` (qap.go:151-162): panics "apocalypse"
