@@ -56,7 +56,7 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update; then ps_scalars_powers,
  *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
  *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
- *      ps_csr_fr) and ps_qap_wide_entries. */
+ *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -170,6 +170,16 @@ int ps_msm_finish(ps_ctx* ctx, uint8_t* out);
  * length (PS_ERR_LENGTH otherwise, algebra.go:350-352). */
 #define PS_MSM_MULTI_MAX 16
 int ps_msm_multi(ps_ctx* ctx, const ps_points* const* points, size_t k, const ps_scalars* scalars, uint8_t* const* out);
+/* The dual: k scalar vectors over ONE point array, one sort / accumulation / tail over k * W bucket sets and a fold per
+ * member on the device.
+ * out[k] = sum_i scalars[k*n + i] * points[i],  n = ps_points_len(points),  ps_scalars_len(scalars) == k*n (PS_ERR_LENGTH
+ * otherwise).  out: k * 96 (G1) / k * 192 (G2) bytes, the encoding ps_msm writes.  Byte-identical to k calls of ps_msm over
+ * slices of `scalars`.  k == 0 or n == 0: PS_OK, identities.  (algebra.go:348-359, k times over one blindedPoint.)
+ * A window table on `points` is ignored (same bytes with and without); ps_msm_set_window is honoured.  Needs an empty MSM
+ * queue (PS_ERR_ARG otherwise).  A batch too large for one pass runs as several, invisibly; ps_msm_batch_set_chunk bounds
+ * the members of a pass (0 = automatic).  A batch of which not even one member fits a pass is summed by ps_msm per member. */
+int ps_msm_batch(ps_ctx* ctx, const ps_points* points, const ps_scalars* scalars, size_t k, uint8_t* out);
+int ps_msm_batch_set_chunk(ps_ctx* ctx, int members /* sums per pass; 0 = automatic */);
 /* Host-side conversion of ONE point between PS_FMT_AFFINE and PS_FMT_COMPRESSED (what the shim
  * needs to feed proof elements back to kyber's UnmarshalBinary).  Validates the encoding. */
 int ps_point_convert(int group, int in_fmt, int out_fmt, const uint8_t* in, uint8_t* out);
@@ -282,6 +292,22 @@ typedef struct { /* the prover's part of Groth16Setup (groth16.go:30-61) */
 int ps_groth16_prove(ps_ctx* ctx, const ps_groth16_pk* pk, const ps_qap* q, const ps_scalars* sol,
                      const uint8_t r_be32[32], const uint8_t s_be32[32], uint8_t A[96], uint8_t B[192],
                      uint8_t C[96]);
+
+/* k proofs under one key: sols holds k solution vectors of q's m variables back to back; r_be32 / s_be32 k*32 bytes; A, C
+ * k*96, B k*192.  Proof j is byte-identical to ps_groth16_prove(ctx, pk, q, sols[j*m .. (j+1)*m), r_j, s_j, ..).
+ * (groth16.go:122-211, k times.)  One pass of wire values and gate checks over all witnesses, the h values witness by
+ * witness without a host synchronisation between them, then three ps_msm_batch sums.
+ * Needs a Lagrange-form key (lxi, lxi2, lxi_t): PS_ERR_ARG otherwise, naming ps_points_monomial_to_lagrange.
+ * valid == NULL: a witness that violates a gate fails the call with PS_ERR_NOT_DIVISIBLE ("apocalypse", qap.go:158-160; the
+ * message names the first such index).  valid != NULL: PS_OK, valid[j] = 0 and the 384 bytes of proof j are zero, every
+ * other proof as above.  k == 0: PS_OK.  Needs an empty MSM queue; ps_msm_batch_set_chunk bounds the members per pass.
+ * Measured against a loop of ps_groth16_prove on the same key (profiles/prove_batch.txt): a call costs ~13 ms whatever k is (each
+ * of the three sums ends in a serial fold of ~250 doublings per member, 3.3-3.9 ms), so the batch is slower than the loop
+ * below ~32 proofs (k = 1: 0.06-0.14x, k = 8: 0.35-0.54x) and wins beyond: 1.9x at 2^10 constraints and k = 64, 3.0x at
+ * k = 256, 2.0-2.2x at 2^12.  At 2^14 constraints it only draws level (0.97x at 64, 1.15x at 256) and at 2^16 it loses at
+ * every k measured (0.55x): there the single prover's window tables and its three sums in flight are worth more. */
+int ps_groth16_prove_batch(ps_ctx* ctx, const ps_groth16_pk* pk, const ps_qap* q, const ps_scalars* sols, size_t k,
+                           const uint8_t* r_be32, const uint8_t* s_be32, uint8_t* A, uint8_t* B, uint8_t* C, int* valid);
 
 /* One rank's share of Groth16Prove when the sums are sharded over `world` GPUs (one process each): rank g
  * takes its index range of every CRS array, the LAST rank also the fixed points; A_part / B_part / C_part of all

@@ -35,6 +35,7 @@ SYMBOLS = [
     "ps_scalars_powers", "ps_groth16_srs_contribute", "ps_groth16_srs_check", "ps_groth16_srs_check_update",
     "ps_points_lagrange_check", "ps_groth16_crs_check_from_srs",
     "ps_qap_create_fr", "ps_qap_wide_entries",
+    "ps_msm_batch", "ps_msm_batch_set_chunk", "ps_groth16_prove_batch",
 ]
 
 
@@ -172,6 +173,8 @@ def _load():
     lib.ps_msm_launch.argtypes = [vp, vp, vp]
     lib.ps_msm_finish.argtypes = [vp, C.c_char_p]
     lib.ps_msm_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.POINTER(vp)]
+    lib.ps_msm_batch.argtypes = [vp, vp, vp, sz, C.c_char_p]
+    lib.ps_msm_batch_set_chunk.argtypes = [vp, i]
     lib.ps_points_sum.argtypes = [i, C.c_char_p, sz, C.c_char_p]
     lib.ps_point_convert.argtypes = [i, i, i, C.c_char_p, C.c_char_p]
     lib.ps_msm_last_info.argtypes = [vp, C.POINTER(MsmInfo)]
@@ -197,6 +200,8 @@ def _load():
     lib.ps_groth16_prove_multi.argtypes = [C.POINTER(Groth16Device), sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
     lib.ps_groth16_prove.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, C.c_char_p, C.c_char_p, C.c_char_p,
                                      C.c_char_p, C.c_char_p]
+    lib.ps_groth16_prove_batch.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                           C.POINTER(C.c_int)]
     lib.ps_groth16_prove_shard.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, C.c_char_p, C.c_char_p, i, i, C.c_char_p,
                                            C.c_char_p, C.c_char_p]
     lib.ps_groth16_prove_local.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, C.c_char_p, C.c_char_p, i, i, C.c_char_p,

@@ -92,6 +92,10 @@ class Context:
     def set_slice(self, entries: int):
         _check(lib.ps_msm_set_slice(self._h, entries))
 
+    def set_batch_chunk(self, members: int):
+        """Members per pass of msm_batch / Groth16ProveBatch (ps_msm_batch_set_chunk); 0: automatic."""
+        _check(lib.ps_msm_batch_set_chunk(self._h, members))
+
     def set_tail(self, mode: int):
         """0 automatic, 1 chains (the long sums' tail), 2 trees of lane-cooperative additions (the short sums' tail)."""
         _check(lib.ps_msm_set_tail(self._h, mode))
@@ -370,6 +374,15 @@ def msm_multi(ctx: Context, points: list, scalars: Poly) -> list:
     oa = (C.c_void_p * max(k, 1))(*[C.cast(o, C.c_void_p) for o in outs])
     _check(lib.ps_msm_multi(ctx._h, pa, k, scalars._h, oa))
     return [o.raw for o in outs]
+
+
+def msm_batch(ctx: Context, points: Points, scalars: Poly, k: int) -> list:
+    """[scalars[j*n:(j+1)*n].BlindEval(points) for j in range(k)], n = len(points), as ONE bucket problem on the device
+    (ps_msm_batch): k scalar vectors back to back over one point array -- the dual of msm_multi."""
+    nb = _WIRE[points.group]
+    out = C.create_string_buffer(max(k, 1) * nb)
+    _check(lib.ps_msm_batch(ctx._h, points._h, scalars._h, k, out))
+    return [out.raw[j * nb : (j + 1) * nb] for j in range(k)]
 
 
 def point_convert(group: int, raw: bytes, in_fmt: int, out_fmt: int) -> bytes:
@@ -805,6 +818,24 @@ def Groth16Prove(tr: Groth16Setup, q: QAP, sol: Poly, r: int, s: int) -> Groth16
     pk = tr._struct()
     _check(lib.ps_groth16_prove(q.ctx._h, C.byref(pk), q._h, sol._h, _be32(r), _be32(s), A, B, Cc))
     return Groth16Proof(r, s, A.raw, B.raw, Cc.raw)
+
+
+def Groth16ProveBatch(tr: Groth16Setup, q: QAP, sols: Poly, rs: Sequence[int], ss: Sequence[int], valid: bool = False):
+    """[Groth16Prove(tr, q, sols[j*m:(j+1)*m], rs[j], ss[j]) for j in range(len(rs))] in one call (ps_groth16_prove_batch): the
+    witnesses of ONE circuit back to back in `sols`, one key, which must carry its Lagrange form (with_lagrange).
+    valid=False: a list of Groth16Proof; a witness that violates a gate raises Apocalypse.  valid=True: (proofs, flags) with
+    flags[j] == 0 and proof j all zero bytes for such a witness, every other proof as usual."""
+    k = len(rs)
+    if len(ss) != k:
+        raise ValueError("Groth16ProveBatch: as many s as r")
+    A, B, Cc = C.create_string_buffer(max(96 * k, 1)), C.create_string_buffer(max(192 * k, 1)), C.create_string_buffer(max(96 * k, 1))
+    flags = (C.c_int * max(k, 1))() if valid else None
+    pk = tr._struct()
+    _check(lib.ps_groth16_prove_batch(q.ctx._h, C.byref(pk), q._h, sols._h, k, b"".join(_be32(r) for r in rs),
+                                      b"".join(_be32(s) for s in ss), A, B, Cc, flags))
+    proofs = [Groth16Proof(rs[j], ss[j], A.raw[96 * j : 96 * j + 96], B.raw[192 * j : 192 * j + 192], Cc.raw[96 * j : 96 * j + 96])
+              for j in range(k)]
+    return (proofs, list(flags)[:k]) if valid else proofs
 
 
 def Groth16ProveLocal(tr_local: Groth16Setup, q: QAP, sol: Poly, r: int, s: int, rank: int, world: int):

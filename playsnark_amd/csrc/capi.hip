@@ -18,9 +18,12 @@
 #include <vector>
 
 #include "msm.hpp"
+#include "msm_batch.hpp"
+#include "msm_batch_plan.hpp"
 #include "quotient.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
+#include "prove_batch.hpp"
 #include "share_ranges.hpp"
 
 namespace ps {
@@ -89,6 +92,14 @@ struct ps_ctx {
     bool tail_used = false;
     // MSM workspace
     DevBuf counts, offs, bsum, keys, ranks, vals, sorted, buckets, parts, segs, wins, heavy, hparts, coarse;
+    DevBuf mb_fold, mb_out;  // ps_msm_batch: the members' folded sums (XYZZ + the chain products of k_batch_to_affine), then affine + wire bytes
+    int batch_chunk = 0;     // ps_msm_batch_set_chunk: members per pass, 0 = automatic
+    hipEvent_t mb_ev[2] = {nullptr, nullptr};  // timed contexts: around the fold, the normalisation and the encoding of a batch's last pass
+    // ps_groth16_prove_batch (prove_batch.inc): the witnesses in Montgomery form [k][m], the wire values [3][k][n], and r_j, s_j,
+    // r_j s_j with the gate flags behind them; stage events of the last timed call
+    DevBuf pb_x, pb_y, pb_small;
+    hipEvent_t pb_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool pb_timed = false;
     DevBuf affine_tmp;  // XYZZ points + chain products of k_batch_to_affine (fixed-base multiplications, window tables)
     DevBuf staging;                  // byte staging for uploads / downloads
     DevBuf vb_f12, vb_xyzz, vb_rho, vb_cols;  // the batch verifier's workspaces (verify_batch.inc): Miller values, rho A, rho, column sums
@@ -291,7 +302,7 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->tail) (void)hipStreamSynchronize(c->tail);
     for (DevBuf* b : {&c->counts, &c->offs, &c->bsum, &c->keys, &c->ranks, &c->sorted, &c->buckets, &c->parts,
-                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->fb_table[0], &c->fb_table[1],
+                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->mb_fold, &c->mb_out, &c->pb_x, &c->pb_y, &c->pb_small, &c->fb_table[0], &c->fb_table[1],
                       &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols,
                       &c->lc_f12, &c->lc_pts, &c->lc_rows, &c->lc_iolp, &c->lc_work})
         b->release();
@@ -313,6 +324,8 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_multi) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->mb_ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->pb_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_acc) if (e) (void)hipEventDestroy(e);
     if (c->ev_sorted) (void)hipEventDestroy(c->ev_sorted);
     if (c->d_flag) (void)hipFree(c->d_flag);
@@ -1160,9 +1173,12 @@ static bool table_ref(const ps_points* pts, size_t n, int wbits, int W, TableRef
 // alternates two workspaces so that the latency-bound tail of one sum -- fix-up and reduction, ~1.3 ms
 // of short dependency chains on a mostly idle chip -- runs under the next sum's accumulation).
 // wait_acc: event the accumulation waits for; acc_done: recorded right after it.
+// dev_sets (ps_msm_batch only; NULL for every other caller, whose launches it does not touch): the set sums stay on the
+// device -- *dev_sets points at the pl.sets weighted sums in `wins`, nothing is copied to the pinned slot, and the number
+// of sets is not bound by that slot.  `n` is then the length of the virtual scalar array (members x points).
 template <class F>
 static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, const MsmPlan& pl, bool timed, int slot,
-                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false) {
+                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr) {
     typedef typename KernelField<F>::type KF;      // Fp -> Fp, Fp2 -> lane-split Fp2s
     constexpr unsigned LN = FieldTraits<KF>::LANES;  // lanes per logical thread
     const u64 total = (u64)pl.W * n;
@@ -1209,7 +1225,7 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     const u32 heavy_npb = 256 / QTraits<KF>::GL;  // a job is at least one block's worth of slices (heavy_chunk_of)
     const size_t max_jobs = (size_t)nthreads_acc / heavy_npb + max_heavy + 1;
     if ((rc = wc->hparts.ensure(sizeof(Xyzz<F>) * max_jobs))) return rc;
-    if (sizeof(Xyzz<F>) * (pl.sets > 1 ? (size_t)pl.sets : (size_t)nres) + 16 > PS_PINNED_SLOT) return fail(PS_ERR_ARG, "too many windows");
+    if (!dev_sets && sizeof(Xyzz<F>) * (pl.sets > 1 ? (size_t)pl.sets : (size_t)nres) + 16 > PS_PINNED_SLOT) return fail(PS_ERR_ARG, "too many windows");
     hipStream_t st = wc->stream;
     int evi = 4;  // ev[3] = after the scatter (msm_sort); ev[4] = the accumulation may start
     if (wc->tail_used) HIP_TRY(hipStreamWaitEvent(st, wc->ev_tail_done, 0));  // buffers of the previous sum
@@ -1329,7 +1345,7 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
                                    (const Xyzz<F>*)pieces, rp.nblk, (Xyzz<F>*)wc->wins.p);
             }
         }
-        if (pl.sets > 1)  // per-set weights on the device; the set sums follow the partial results in `wins`
+        if (pl.sets > 1 || dev_sets)  // per-set weights on the device; the set sums follow the partial results in `wins`
             hipLaunchKernelGGL(k_reduce_weights<KF>, dim3((unsigned)pl.sets), dim3(RED_SUM_LANES * LN), RED_SUM_LANES * sizeof(Xyzz<F>), st,
                                (const Xyzz<F>*)wc->wins.p, rp.njobs, (rp.small && !pl.qtail) ? 1 : 0, pl.qtail ? 0 : RED_SEG_LOG,
                                (Xyzz<F>*)wc->wins.p + nres);
@@ -1337,6 +1353,8 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     PS_STAGE_MARK();  // 7: after reduction
     HIP_TRY(hipGetLastError());
     // one set: its partial results (the host applies the weights); several: the set sums
+    if (dev_sets) *dev_sets = (Xyzz<F>*)wc->wins.p + nres;
+    else
     HIP_TRY(hipMemcpyAsync((char*)c->h_pinned + (size_t)slot * PS_PINNED_SLOT, (const Xyzz<F>*)wc->wins.p + (pl.sets > 1 ? nres : 0),
                            sizeof(Xyzz<F>) * (pl.sets > 1 ? (size_t)pl.sets : (size_t)nres) + (pl.qtail ? 4 : 0), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(wc->ev_tail_done, st));
@@ -1356,6 +1374,9 @@ static bool table_usable(const ps_ctx* c, const ps_points* pts, size_t n, int ma
 // trees of lane-cooperative additions (qtail.hpp) wherever that costs little lane-time.  Short sums (fewer than
 // PS_QTAIL_MAX_ENTRIES digits) also get slices as short as keeps one wave per SIMD busy and a tree fix-up.
 // forced: 0 automatic, 1 the chains of round 2 throughout, 2 the trees wherever they apply.
+// A pass of ps_msm_batch (Kc members of n scalars each, Kc * W bucket sets) is planned by the same rules as ONE plain sum of
+// Kc * n scalars: msm_plan_tail and msm_plan_lpb are called with n := Kc * n and G = Kc * W * NB, the window c alone comes
+// from one member's n (msm_batch_plan, msm_batch.inc).
 #ifndef PS_QTAIL_MAX_ENTRIES
 #define PS_QTAIL_MAX_ENTRIES (1ull << 21)
 #endif
@@ -1983,8 +2004,10 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
     return PS_OK;
 }
 #endif
+#include "msm_batch.inc"
 #include "prove.inc"
 #include "prove_shares.inc"
+#include "prove_batch.inc"
 #include "lagrange.inc"
 #include "pairing.inc"
 #include "pairing_dev.hpp"

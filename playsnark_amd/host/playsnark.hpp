@@ -12,6 +12,7 @@
 // The reference panics; here the same conditions throw LengthMismatch (message of
 // algebra.go:351) and Apocalypse ("apocalypse", qap.go:159).  No arithmetic in this file.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -209,6 +210,33 @@ inline Groth16Proof Groth16Prove(Context& c, const ps_groth16_pk& tr, const QAP&
     return p;
 }
 
+// Groth16Prove for every witness of `sols` (rs.size() solution vectors of q's variables back to back) under one Lagrange-form
+// key, in one call (ps_groth16_prove_batch); proof j is byte for byte Groth16Prove of witness j with (rs[j], ss[j]).
+// valid == nullptr: a witness that violates a gate throws Apocalypse; otherwise (*valid)[j] == 0 and proof j is all zero bytes
+inline std::vector<Groth16Proof> Groth16ProveBatch(Context& c, const ps_groth16_pk& tr, const QAP& q, const Poly& sols,
+                                                   const std::vector<Scalar>& rs, const std::vector<Scalar>& ss,
+                                                   std::vector<int>* valid = nullptr) {
+    const size_t k = rs.size();
+    if (ss.size() != k) throw std::invalid_argument("Groth16ProveBatch: as many s as r");
+    std::vector<uint8_t> r(32 * k + 1), s(32 * k + 1), A(96 * k + 1), B(192 * k + 1), C(96 * k + 1);
+    for (size_t j = 0; j < k; j++) {
+        std::copy(rs[j].begin(), rs[j].end(), r.begin() + 32 * j);
+        std::copy(ss[j].begin(), ss[j].end(), s.begin() + 32 * j);
+    }
+    if (valid) valid->assign(k, 0);
+    check(ps_groth16_prove_batch(c.get(), &tr, q.get(), sols.get(), k, r.data(), s.data(), A.data(), B.data(), C.data(),
+                                 valid && k ? valid->data() : nullptr));
+    std::vector<Groth16Proof> out(k);
+    for (size_t j = 0; j < k; j++) {
+        out[j].R = rs[j];
+        out[j].S = ss[j];
+        std::copy(A.begin() + 96 * j, A.begin() + 96 * (j + 1), out[j].A.begin());
+        std::copy(B.begin() + 192 * j, B.begin() + 192 * (j + 1), out[j].B.begin());
+        std::copy(C.begin() + 96 * j, C.begin() + 96 * (j + 1), out[j].C.begin());
+    }
+    return out;
+}
+
 // One rank's share of Groth16Prove when the sums are split over `world` GPUs; the ranks' A, B, C add up
 // (ps_points_sum after an all_gather) to the proof
 inline Groth16Proof Groth16ProveShard(Context& c, const ps_groth16_pk& tr, const QAP& q, const Poly& sol, const Scalar& r,
@@ -389,5 +417,18 @@ inline std::vector<Bytes> SolCommits(Context& c, const std::vector<const Points*
     check(ps_msm_multi(c.get(), pts.data(), pts.size(), sol.get(), dst.data()));
     return out;
 }
+
+// k scalar vectors (back to back in `scalars`) over ONE point array, as one bucket problem on the device (ps_msm_batch): the dual
+// of SolCommits.  out[j] = the sum of member j, 96 / 192 bytes
+inline std::vector<Bytes> BlindEvalBatch(Context& c, const Points& points, const Poly& scalars, size_t k) {
+    const size_t wb = points.group() == PS_G1 ? 96 : 192;
+    std::vector<uint8_t> flat(wb * k + 1);
+    check(ps_msm_batch(c.get(), points.get(), scalars.get(), k, flat.data()));
+    std::vector<Bytes> out;
+    for (size_t j = 0; j < k; j++) out.emplace_back(flat.begin() + wb * j, flat.begin() + wb * (j + 1));
+    return out;
+}
+// members per pass of BlindEvalBatch / Groth16ProveBatch (ps_msm_batch_set_chunk); 0: automatic
+inline void SetBatchChunk(Context& c, int members) { check(ps_msm_batch_set_chunk(c.get(), members)); }
 
 }  // namespace playsnark

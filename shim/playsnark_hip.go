@@ -526,6 +526,80 @@ func Groth16ProveHIP(hs *HipGroth16, sol Vector) Groth16Proof {
 	}
 }
 
+// Groth16ProveBatchHIP is Groth16ProveHIP for many witnesses of ONE circuit under one key, in one call
+// (ps_groth16_prove_batch): one pass of wire values and gate checks over all witnesses, then three batched sums.  The
+// route is the Lagrange-form one, so a key that came from the reference's setup is converted first (ToLagrange, once per
+// key).  Proof j is the proof Groth16ProveHIP would make of sols[j] with the same (r, s), which are drawn here per proof.
+// A witness that violates a gate panics with the reference's "apocalypse" (qap.go:158-160).
+func Groth16ProveBatchHIP(hs *HipGroth16, sols []Vector) []Groth16Proof {
+	k := len(sols)
+	if k == 0 {
+		return nil
+	}
+	hs.ToLagrange()
+	flat := make(Vector, 0, k*len(sols[0]))
+	for _, s := range sols {
+		if len(s) != len(sols[0]) {
+			panic("Groth16ProveBatchHIP: the witnesses of one circuit have one length")
+		}
+		flat = append(flat, s...)
+	}
+	rs, ss := make([]Element, k), make([]Element, k)
+	rb, sb := make([]byte, 0, 32*k), make([]byte, 0, 32*k)
+	for j := 0; j < k; j++ {
+		rs[j] = NewElement().Pick(random.New())
+		ss[j] = NewElement().Pick(random.New())
+		b, _ := rs[j].MarshalBinary()
+		rb = append(rb, b...)
+		b, _ = ss[j].MarshalBinary()
+		sb = append(sb, b...)
+	}
+	dsols := uploadSolution(flat)
+	defer C.ps_scalars_free(dsols)
+	A := make([]byte, g1Wire*k)
+	B := make([]byte, g2Wire*k)
+	Cc := make([]byte, g1Wire*k)
+	call(func() C.int {
+		return C.ps_groth16_prove_batch(hipCtx, &hs.pk, hs.qap.h, dsols, C.size_t(k), u8(rb), u8(sb), u8(A), u8(B), u8(Cc), nil)
+	})
+	out := make([]Groth16Proof, k)
+	for j := range out {
+		out[j] = Groth16Proof{
+			tp: groth16ToxicProof{R: rs[j], S: ss[j]},
+			A:  pointFrom(C.PS_G1, A[g1Wire*j:g1Wire*(j+1)], zeroG1),
+			B:  pointFrom(C.PS_G2, B[g2Wire*j:g2Wire*(j+1)], zeroG2),
+			C:  pointFrom(C.PS_G1, Cc[g1Wire*j:g1Wire*(j+1)], zeroG1),
+		}
+	}
+	return out
+}
+
+// BlindEvalBatchHIP is BlindEvalHIP for k polynomials over ONE array of blinded points, as one bucket problem on the
+// device (ps_msm_batch): out[j] = polys[j].BlindEval(zero, crs).
+func BlindEvalBatchHIP(polys []Poly, zero Commit, crs *C.ps_points) []Commit {
+	k := len(polys)
+	n := int(C.ps_points_len(crs))
+	sc := make([]byte, 0, 32*k*n)
+	for _, p := range polys {
+		if len(p) != n { // the reference's own panic and message, algebra.go:350-352
+			panic(fmt.Sprintf("mismatch of length between poly %d and blinded eval points %d", len(p), n))
+		}
+		sc = append(sc, marshalScalars(p)...)
+	}
+	group := C.ps_points_group(crs)
+	var h *C.ps_scalars
+	call(func() C.int { return C.ps_scalars_upload(hipCtx, u8(sc), C.size_t(k*n), &h) })
+	defer C.ps_scalars_free(h)
+	w := wireLen(group)
+	raw := make([]byte, w*k)
+	call(func() C.int { return C.ps_msm_batch(hipCtx, crs, h, C.size_t(k), u8(raw)) })
+	out := make([]Commit, k)
+	for j := range out {
+		out[j] = pointFrom(group, raw[w*j:w*(j+1)], zero)
+	}
+	return out
+}
+
 // Groth16VerifyHIP replaces `func Groth16Verify(tr Groth16Setup, q QAP, p Groth16Proof, io Vector) bool`
 // (groth16.go:214-233): pairings on the host inside the library, the IO sum on the GPU.  A proof point
 // that is not a canonical encoding of a subgroup element never gets here: UnmarshalBinary refused it.
