@@ -46,6 +46,8 @@ static int fail(int code, const std::string& msg) {
             return fail(PS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
     } while (0)
 
+#include "scope.hpp"  // Scope, KeepError: what a call makes along the way, released on every way out
+
 extern "C" const char* ps_last_error(void) { return g_last_error.c_str(); }
 extern "C" const char* ps_version(void) { return "playsnark_hip 0.4 (gfx950), ABI 4"; }
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
@@ -365,15 +367,17 @@ static int scalars_alloc(ps_ctx* c, size_t n, ps_scalars** out) {
 
 extern "C" int ps_scalars_from_device_be32(ps_ctx* c, const void* d_be32, size_t n, ps_scalars** out) {
     if (!c || !out || (n && !d_be32)) return fail(PS_ERR_ARG, "ps_scalars_from_device_be32: NULL argument");
+    *out = nullptr;
     if (n >= (1ull << 31)) return fail(PS_ERR_ARG, "vector too long");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = scalars_alloc(c, n, out);
+    Scope scope;
+    int rc = scalars_alloc(c, n, scope.result(out));
     if (rc) return rc;
     if (n) hipLaunchKernelGGL(k_scalars_from_be32, dim3(nblocks(n)), dim3(256), 0, c->stream, (const uint8_t*)d_be32,
                               (u32)n, (u32*)(*out)->st->p);
     HIP_TRY(hipGetLastError());
     if (storage_mark_ready((*out)->st, c->stream)) return fail(PS_ERR_HIP, "ps_scalars_from_device_be32: event record failed");
-    return PS_OK;
+    return scope.finish(PS_OK);
 }
 
 extern "C" int ps_scalars_upload(ps_ctx* c, const uint8_t* be32, size_t n, ps_scalars** out) {
@@ -390,53 +394,42 @@ extern "C" int ps_scalars_upload(ps_ctx* c, const uint8_t* be32, size_t n, ps_sc
     return PS_OK;
 }
 
-// The context's own vector for the scalars of ONE ps_msm_be32 / ps_msm_i64 call: grown when a call needs more, never shrunk,
-// resized in place (the handle is the context's alone and no sum is pending on it between calls).
-static int upload_vector(ps_ctx* c, size_t n, ps_scalars** out) {
-    if (!c->up_scalars || c->up_cap < n) {
-        if (c->up_scalars) { ps_scalars_free(c->up_scalars); c->up_scalars = nullptr; c->up_cap = 0; }
+// A vector the context owns and reuses, as (handle, capacity): grown when a call needs more, never shrunk, resized in place.  The
+// caller must NOT free it; views made of it (ps_scalars_slice) are freed as usual.  c->up_scalars serves ONE ps_msm_be32 /
+// ps_msm_i64 call, c->pv_scalars[0..3] the provers: no sum is pending on a context between such calls, so the memory is free
+// to reuse.
+static int reused_vector(ps_ctx* c, ps_scalars*& v, size_t& have, size_t n, ps_scalars** out) {
+    if (!v || have < n) {
+        if (v) { ps_scalars_free(v); v = nullptr; have = 0; }
         const size_t cap = n + n / 8 + 64;
-        int rc = scalars_alloc(c, cap, &c->up_scalars);
+        int rc = scalars_alloc(c, cap, &v);
         if (rc) return rc;
-        c->up_cap = cap;
+        have = cap;
     }
-    ps_scalars* s = c->up_scalars;
-    s->n = n;
-    s->first = 0;
-    s->max_bits = 255;
-    s->neg_small = false;
-    *out = s;
+    v->n = n;
+    v->first = 0;
+    v->max_bits = 255;
+    v->neg_small = false;
+    *out = v;
     return PS_OK;
 }
-
-// The same for the provers' vectors (slot 0..3): handles owned by the context -- the caller must NOT free them; views made of them
-// (ps_scalars_slice) are freed as usual.  No sum is pending on a context between proofs, so the memory is free to reuse.
-static int prover_vector(ps_ctx* c, int slot, size_t n, ps_scalars** out) {
-    if (!c->pv_scalars[slot] || c->pv_cap[slot] < n) {
-        if (c->pv_scalars[slot]) { ps_scalars_free(c->pv_scalars[slot]); c->pv_scalars[slot] = nullptr; c->pv_cap[slot] = 0; }
-        const size_t cap = n + n / 8 + 64;
-        int rc = scalars_alloc(c, cap, &c->pv_scalars[slot]);
-        if (rc) return rc;
-        c->pv_cap[slot] = cap;
-    }
-    ps_scalars* s = c->pv_scalars[slot];
-    s->n = n;
-    s->first = 0;
-    s->max_bits = 255;
-    s->neg_small = false;
-    *out = s;
-    return PS_OK;
-}
+static int upload_vector(ps_ctx* c, size_t n, ps_scalars** out) { return reused_vector(c, c->up_scalars, c->up_cap, n, out); }
+static int prover_vector(ps_ctx* c, int slot, size_t n, ps_scalars** out) { return reused_vector(c, c->pv_scalars[slot], c->pv_cap[slot], n, out); }
 
 extern "C" int ps_scalars_upload_i64(ps_ctx* c, const int64_t* v, size_t n, ps_scalars** out) {
     if (!c || !out || (n && !v)) return fail(PS_ERR_ARG, "ps_scalars_upload_i64: NULL argument");
+    *out = nullptr;
     if (n >= (1ull << 31)) return fail(PS_ERR_ARG, "vector too long");
     HIP_TRY(hipSetDevice(c->device));
     int rc = c->staging.ensure(8 * n + 32);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(c->staging.p, v, 8 * n, hipMemcpyHostToDevice, c->stream));
-    rc = scalars_alloc(c, n, out);
+    Scope scope(c->stream);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->staging.p, v, 8 * n, hipMemcpyHostToDevice, c->stream));
+        scope.in_flight();  // the caller's buffer is not read past return
+    }
+    rc = scalars_alloc(c, n, scope.result(out));
     if (rc) return rc;
     if (n) hipLaunchKernelGGL(k_scalars_from_i64, dim3(nblocks(n)), dim3(256), 0, c->stream, (const int64_t*)c->staging.p,
                               (u32)n, (u32*)(*out)->st->p);
@@ -446,7 +439,7 @@ extern "C" int ps_scalars_upload_i64(ps_ctx* c, const int64_t* v, size_t n, ps_s
     (*out)->max_bits = 64;  // witnesses need only ceil(64/c) windows; negatives are folded onto -P (k_digits_grouped)
     (*out)->neg_small = any_neg;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return PS_OK;
+    return scope.finish(PS_OK);
 }
 
 extern "C" int ps_scalars_download(ps_ctx* c, const ps_scalars* s, size_t first, size_t n, uint8_t* out) {
@@ -504,6 +497,7 @@ static int points_alloc(ps_ctx* c, int group, size_t n, ps_points** out) {
 
 extern "C" int ps_points_upload(ps_ctx* c, int group, const uint8_t* pts, size_t n, int fmt, ps_points** out) {
     if (!c || !out || (n && !pts)) return fail(PS_ERR_ARG, "ps_points_upload: NULL argument");
+    *out = nullptr;
     if (group != PS_G1 && group != PS_G2) return fail(PS_ERR_ARG, "ps_points_upload: bad group");
     if (fmt != PS_FMT_AFFINE && fmt != PS_FMT_COMPRESSED) return fail(PS_ERR_ARG, "ps_points_upload: bad format");
     if (n >= (1ull << 31)) return fail(PS_ERR_ARG, "vector too long");
@@ -512,8 +506,12 @@ extern "C" int ps_points_upload(ps_ctx* c, int group, const uint8_t* pts, size_t
     int rc = c->staging.ensure(wb * n + 32);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(c->staging.p, pts, wb * n, hipMemcpyHostToDevice, c->stream));
-    rc = points_alloc(c, group, n, out);
+    Scope scope(c->stream);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->staging.p, pts, wb * n, hipMemcpyHostToDevice, c->stream));
+        scope.in_flight();  // the caller's buffer is not read past return
+    }
+    rc = points_alloc(c, group, n, scope.result(out));
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->d_flag, 0, 4, c->stream));
     if (n && fmt == PS_FMT_COMPRESSED) {  // GPU batch decompression: one Fp / Fp2 square root per point
@@ -535,12 +533,8 @@ extern "C" int ps_points_upload(ps_ctx* c, int group, const uint8_t* pts, size_t
     u32 nbad = 0;
     HIP_TRY(hipMemcpyAsync(&nbad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (nbad) {
-        ps_points_free(*out);
-        *out = nullptr;
-        return fail(PS_ERR_ENCODING, std::to_string(nbad) + " point(s) not canonical / not on the curve");
-    }
-    return PS_OK;
+    if (nbad) return fail(PS_ERR_ENCODING, std::to_string(nbad) + " point(s) not canonical / not on the curve");
+    return scope.finish(PS_OK);
 }
 
 // XYZZ -> affine for n points on c->stream (k_batch_to_affine): `tmp` holds the XYZZ points followed by the chain products.
@@ -628,16 +622,13 @@ extern "C" int ps_points_from_scalars(ps_ctx* c, int group, const ps_scalars* k,
     if (!c || !k || !out) return fail(PS_ERR_ARG, "ps_points_from_scalars: NULL argument");
     if (group != PS_G1 && group != PS_G2) return fail(PS_ERR_ARG, "bad group");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = points_alloc(c, group, k->n, out);
+    Scope scope;
+    int rc = points_alloc(c, group, k->n, scope.result(out));
     if (rc) return rc;
     if (storage_wait_ready(k->st, c->stream)) return fail(PS_ERR_HIP, "ps_points_from_scalars: event wait failed");
     rc = group == PS_G1 ? fixed_base<Fp>(c, 0, k, *out) : fixed_base<Fp2>(c, 1, k, *out);
     if (!rc && storage_mark_ready((*out)->st, c->stream)) rc = fail(PS_ERR_HIP, "ps_points_from_scalars: event record failed");
-    if (rc) {
-        ps_points_free(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return scope.finish(rc);
 }
 
 extern "C" int ps_points_download(ps_ctx* c, const ps_points* p, size_t first, size_t n, uint8_t* out) {
@@ -1770,15 +1761,15 @@ extern "C" int ps_msm_be32(ps_ctx* c, const ps_points* pts, const uint8_t* be32,
     ps_scalars* s = nullptr;
     if ((rc = upload_vector(c, n, &s))) return rc;
     // (no sum is pending and every earlier call returned after its result: the staging buffer and the vector are free)
+    Scope scope(c->stream);
     if (n) {
         HIP_TRY(hipMemcpyAsync(c->staging.p, be32, 32 * n, hipMemcpyHostToDevice, c->stream));
+        scope.in_flight();  // the caller's buffer is not read past return, error or not (ps_msm returns a result with the stream idle)
         hipLaunchKernelGGL(k_scalars_from_be32, dim3(nblocks(n)), dim3(256), 0, c->stream, (const uint8_t*)c->staging.p, (u32)n, (u32*)s->st->p);
         HIP_TRY(hipGetLastError());
     }
     if (storage_mark_ready(s->st, c->stream)) return fail(PS_ERR_HIP, "ps_msm_be32: event record failed");
-    rc = ps_msm(c, pts, s, out);
-    if (rc) (void)hipStreamSynchronize(c->stream);  // the caller's buffer is not read past return, error or not
-    return rc;
+    return scope.finish(ps_msm(c, pts, s, out));
 }
 extern "C" int ps_msm_i64(ps_ctx* c, const ps_points* pts, const int64_t* v, size_t n, uint8_t* out) {
     if (!c || !pts || !out || (n && !v)) return fail(PS_ERR_ARG, "ps_msm_i64: NULL argument");
@@ -1789,8 +1780,10 @@ extern "C" int ps_msm_i64(ps_ctx* c, const ps_points* pts, const int64_t* v, siz
     if (rc) return rc;
     ps_scalars* s = nullptr;
     if ((rc = upload_vector(c, n, &s))) return rc;
+    Scope scope(c->stream);
     if (n) {
         HIP_TRY(hipMemcpyAsync(c->staging.p, v, 8 * n, hipMemcpyHostToDevice, c->stream));
+        scope.in_flight();
         hipLaunchKernelGGL(k_scalars_from_i64, dim3(nblocks(n)), dim3(256), 0, c->stream, (const int64_t*)c->staging.p, (u32)n, (u32*)s->st->p);
         HIP_TRY(hipGetLastError());
     }
@@ -1799,9 +1792,7 @@ extern "C" int ps_msm_i64(ps_ctx* c, const ps_points* pts, const int64_t* v, siz
     s->max_bits = 64;
     s->neg_small = any_neg;
     if (storage_mark_ready(s->st, c->stream)) return fail(PS_ERR_HIP, "ps_msm_i64: event record failed");
-    rc = ps_msm(c, pts, s, out);
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return scope.finish(ps_msm(c, pts, s, out));
 }
 extern "C" int ps_msm_last_info(ps_ctx* c, ps_msm_info* out) {
     if (!c || !out) return fail(PS_ERR_ARG, "NULL argument");
@@ -1951,13 +1942,12 @@ extern "C" int ps_debug_pair_add_probe(ps_ctx* c, const ps_points* pts, const ps
     HIP_TRY(hipMemcpy(&E, (const u32*)c->offs.p + pl.G, 4, hipMemcpyDeviceToHost));
     const u32 T = E / 32;
     if (!T) return fail(PS_ERR_ARG, "ps_debug_pair_add_probe: fewer than 32 entries");
+    Scope scope(c->stream);
     Fp* prefix = nullptr;
     Affine<Fp>* out = nullptr;
-    HIP_TRY(hipMalloc((void**)&prefix, sizeof(Fp) * 16 * (size_t)T));
-    if (hipMalloc((void**)&out, sizeof(Affine<Fp>) * 16 * (size_t)T) != hipSuccess) { (void)hipFree(prefix); return fail(PS_ERR_HIP, "hipMalloc"); }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    if (scope.device(&prefix, 16 * (size_t)T) != hipSuccess || scope.device(&out, 16 * (size_t)T) != hipSuccess) return fail(PS_ERR_HIP, "hipMalloc");
+    const hipEvent_t e0 = c->ev[0], e1 = c->ev[1];  // the context's timing pair, as ps_microbench_mad uses it (no sum is pending)
+    c->ev_valid = false;
     const u32 idx_mask = (1u << ENTRY_W_SHIFT) - 1u, pstride = (u32)table_row_bytes(PS_G1);
     auto launch = [&]() {
         if (real_inv) hipLaunchKernelGGL(k_pair_add_probe<true>, dim3(nblocks(T)), dim3(256), 0, c->stream, tref.base, (const u32*)c->sorted.p,
@@ -1980,8 +1970,6 @@ extern "C" int ps_debug_pair_add_probe(ps_ctx* c, const ps_points* pts, const ps
         HIP_TRY(hipMemcpy(&a, out + (size_t)i * T, sizeof a, hipMemcpyDeviceToHost));
         write_affine(sample_sums + 96 * i, xyzz_from_affine<Fp>(a.x, a.y));
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(prefix); (void)hipFree(out);
     return PS_OK;
 }
 

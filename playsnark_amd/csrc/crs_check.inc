@@ -6,7 +6,6 @@
 // instead of a conversion over group elements (lagrange.inc, seconds).  Everything is the existing machinery -- the row SpMV
 // and the interpolations of the quotient, ps_poly_mul, the sums, the host pairing of pairing.inc -- but the comparison of two
 // resident arrays, which has a kernel here so that no array crosses PCIe.
-#include <deque>
 
 // *flag = 1 when the two word arrays differ anywhere (stored points are canonical: equal points <=> equal words).  Grid-stride
 // over 16-byte words; every thread that sees a difference stores the same 1.
@@ -32,20 +31,6 @@ static int points_differ_launch(ps_ctx* c, const ps_points* a, const ps_points* 
                        (const uint4*)((const char*)points_ptr(b) + first * pb), nq, c->d_flag);
     return PS_OK;
 }
-
-// Handles made during a check, freed together on every way out (deques: a slot keeps its address when later ones are added)
-struct CheckScope {
-    std::deque<ps_scalars*> sc;
-    std::deque<ps_points*> pt;
-    ps_scalars** scalars() { sc.push_back(nullptr); return &sc.back(); }
-    ps_points** points() { pt.push_back(nullptr); return &pt.back(); }
-    ~CheckScope() {
-        std::string keep = g_last_error;
-        for (ps_scalars* s : sc) ps_scalars_free(s);
-        for (ps_points* p : pt) ps_points_free(p);
-        g_last_error = keep;
-    }
-};
 
 // The coefficients c of the polynomial that takes the values w[0..cnt) on the nodes 1..n (nodes = 0, cnt = n) or n+1..2n-1
 // (nodes = 1, cnt = n - 1): sum_j w_j l_j(X) = sum_i c_i X^i, so sum_j w_j {l_j(x) P} = sum_i c_i {x^i P} whatever x and P are.
@@ -76,10 +61,9 @@ static int sums_run(ps_ctx* c, const std::vector<SumJob>& jobs) {
         if (!rc) rc = ps_msm_finish(c, jobs[done++].out);
     }
     if (rc) {
-        std::string keep = g_last_error;
+        KeepError keep;
         uint8_t sink[192];
         while (c->q_len) (void)ps_msm_finish(c, sink);
-        g_last_error = keep;
     }
     return rc;
 }
@@ -109,7 +93,7 @@ extern "C" int ps_points_lagrange_check(ps_ctx* c, const ps_qap* q, const ps_poi
         if (p->n != cnt)  // the arrays are polynomial bases of exactly that degree bound (algebra.go:350-352's rule)
             return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(cnt) + " and blinded eval points " + std::to_string(p->n));
     HIP_TRY(hipSetDevice(c->device));
-    CheckScope keep;
+    Scope keep;
     ps_scalars** rho = keep.scalars();
     int rc = check_weights(c, who, rho_be32, nrho, cnt, rho);
     if (rc) return rc;
@@ -156,7 +140,7 @@ extern "C" int ps_groth16_crs_check_from_srs(ps_ctx* c, const ps_qap* q, const p
             return fail(PS_ERR_LENGTH, std::string("mismatch of length between ") + l.name + " " + std::to_string(l.p->n) + " and the " + std::to_string(l.want) +
                                            " powers a circuit of " + std::to_string(n) + " gates needs");
     HIP_TRY(hipSetDevice(c->device));
-    CheckScope keep;
+    Scope keep;
     const size_t nw = std::max(m, n);
     ps_scalars** rho = keep.scalars();
     int rc = check_weights(c, who, rho_be32, nrho, nw, rho);

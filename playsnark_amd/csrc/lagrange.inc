@@ -19,6 +19,9 @@ static void ec_ntt(const NttTables& tb, hipStream_t st, Xyzz<F>* buf, u32 total,
     }
 }
 
+// "<who>: <what>: <the HIP error>" as PS_ERR_HIP
+static int fail_hip(const char* who, const char* what, hipError_t err) { return fail(PS_ERR_HIP, std::string(who) + ": " + what + ": " + hipGetErrorString(err)); }
+
 template <class F>
 static int monomial_to_lagrange_t(ps_ctx* c, const ps_qap* q, const ps_points* mono, bool shifted, ps_points** out) {
     typedef typename KernelField<F>::type KF;
@@ -33,44 +36,33 @@ static int monomial_to_lagrange_t(ps_ctx* c, const ps_qap* q, const ps_points* m
     NttTables& tb = *ctx_tabs(c);
     hipError_t e = ntt_tables_ensure(tb, lognp + 1, st);
     if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_points_monomial_to_lagrange: twiddles: ") + hipGetErrorString(e));
-    int rc = points_alloc(c, mono->group, cnt, out);
+    const char* who = "ps_points_monomial_to_lagrange";
+    Scope scope(st);
+    int rc = points_alloc(c, mono->group, cnt, scope.result(out));
     if (rc) return rc;
     Xyzz<F>*A = nullptr, *B = nullptr, *E = nullptr;
     Fr *t1 = nullptr, *t2 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(st);
-        for (void* p : {(void*)A, (void*)B, (void*)E, (void*)t1, (void*)t2})
-            if (p) (void)hipFree(p);
-    };
-    auto bail = [&](const char* what, hipError_t err) {
-        cleanup();
-        ps_points_free(*out);
-        *out = nullptr;
-        return fail(PS_ERR_HIP, std::string("ps_points_monomial_to_lagrange: ") + what + ": " + hipGetErrorString(err));
-    };
-    if ((e = hipMalloc((void**)&A, sizeof(Xyzz<F>) * 2 * np)) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&B, sizeof(Xyzz<F>) * np)) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&E, sizeof(Xyzz<F>) * np)) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&t1, sizeof(Fr) * 2 * np)) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&t2, sizeof(Fr) * 2 * np)) != hipSuccess) return bail("hipMalloc", e);
-    if (storage_wait_ready(mono->st, st)) { cleanup(); ps_points_free(*out); *out = nullptr; return fail(PS_ERR_HIP, "event wait failed"); }
+    if ((e = scope.device(&A, 2 * np)) != hipSuccess || (e = scope.device(&B, np)) != hipSuccess || (e = scope.device(&E, np)) != hipSuccess ||
+        (e = scope.device(&t1, 2 * np)) != hipSuccess || (e = scope.device(&t2, 2 * np)) != hipSuccess)
+        return fail_hip(who, "hipMalloc", e);
+    if (storage_wait_ready(mono->st, st)) return fail(PS_ERR_HIP, "event wait failed");
     const u32 npu = (u32)np;
     // g = the monomial points, the identity beyond cnt
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks((size_t)np * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(mono), (u32)cnt, npu, A);
     // ---- T_s^T, s = np .. 128 ----
     for (int logs = lognp; logs >= 7; logs--) {
         // stored transform of the left children, read backwards: hhat = NTT(rev(INTT(zhat))) / s
-        if ((e = hipMemcpyAsync(t1, zhat[logs], sizeof(Fr) * np, hipMemcpyDeviceToDevice, st)) != hipSuccess) return bail("copy", e);
-        if ((e = ntt_run<true>(tb, st, t1, np, logs)) != hipSuccess) return bail("ntt", e);
+        if ((e = hipMemcpyAsync(t1, zhat[logs], sizeof(Fr) * np, hipMemcpyDeviceToDevice, st)) != hipSuccess) return fail_hip(who, "copy", e);
+        if ((e = ntt_run<true>(tb, st, t1, np, logs)) != hipSuccess) return fail_hip(who, "ntt", e);
         hipLaunchKernelGGL(k_fr_rev_mod, dim3(nblk(np)), dim3(256), 0, st, t2, (const Fr*)t1, np, logs);
-        if ((e = ntt_run<false>(tb, st, t2, np, logs)) != hipSuccess) return bail("ntt", e);
+        if ((e = ntt_run<false>(tb, st, t2, np, logs)) != hipSuccess) return fail_hip(who, "ntt", e);
         hipLaunchKernelGGL(k_fr_scale, dim3(nblk(np)), dim3(256), 0, st, t2, (const Fr*)t2, fr_inv2pow_host(logs), np);
-        if ((e = hipMemcpyAsync(B, A, sizeof(Xyzz<F>) * np, hipMemcpyDeviceToDevice, st)) != hipSuccess) return bail("copy", e);
+        if ((e = hipMemcpyAsync(B, A, sizeof(Xyzz<F>) * np, hipMemcpyDeviceToDevice, st)) != hipSuccess) return fail_hip(who, "copy", e);
         ec_ntt<F, false>(tb, st, B, npu, logs);
         hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)np * LN)), dim3(256), 0, st, B, npu, (const Fr*)t2, ~0ull);
         ec_ntt<F, true>(tb, st, B, npu, logs);
         hipLaunchKernelGGL(k_ec_take_right<KF>, dim3(nblocks((size_t)(np / 2) * LN)), dim3(256), 0, st, A, (const Xyzz<F>*)B, npu, logs);
-        if ((e = hipGetLastError()) != hipSuccess) return bail("level", e);
+        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "level", e);
     }
     // ---- B^T on the blocks of 64 ----
     {
@@ -80,12 +72,12 @@ static int monomial_to_lagrange_t(ps_ctx* c, const ps_qap* q, const ps_points* m
                                (u32)(np / 64));
             std::swap(tin, tout);
         }
-        if ((e = hipGetLastError()) != hipSuccess) return bail("base", e);
+        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "base", e);
     }
     // ---- C^T: correlation with v_k = (-1)^k / k! over 2 np, then D^T: times 1 / j! ----
     hipLaunchKernelGGL(k_ec_pad<KF>, dim3(nblocks((size_t)2 * np * LN)), dim3(256), 0, st, (const Xyzz<F>*)E, (u32)cnt, 2 * npu, A);
     hipLaunchKernelGGL(k_fr_v_rev, dim3(nblk(2 * np)), dim3(256), 0, st, t1, (const Fr*)qt.invfact, np);
-    if ((e = ntt_run<false>(tb, st, t1, 2 * np, lognp + 1)) != hipSuccess) return bail("ntt", e);
+    if ((e = ntt_run<false>(tb, st, t1, 2 * np, lognp + 1)) != hipSuccess) return fail_hip(who, "ntt", e);
     hipLaunchKernelGGL(k_fr_scale, dim3(nblk(2 * np)), dim3(256), 0, st, t1, (const Fr*)t1, fr_inv2pow_host(lognp + 1), 2 * np);
     ec_ntt<F, false>(tb, st, A, 2 * npu, lognp + 1);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)2 * np * LN)), dim3(256), 0, st, A, 2 * npu, (const Fr*)t1, ~0ull);
@@ -93,10 +85,9 @@ static int monomial_to_lagrange_t(ps_ctx* c, const ps_qap* q, const ps_points* m
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)cnt * LN)), dim3(256), 0, st, A, (u32)cnt, (const Fr*)qt.invfact, ~0ull);
     // canonical affine points (the chain products of the batch normalisation go behind the cnt points: A holds 2 np)
     batch_to_affine<F>(c, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
-    if ((e = hipGetLastError()) != hipSuccess) return bail("kernels", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bail("run", e);
-    cleanup();
-    return PS_OK;
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "kernels", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(who, "run", e);
+    return scope.finish(PS_OK);
 }
 
 extern "C" int ps_points_monomial_to_lagrange(ps_ctx* c, const ps_qap* q, const ps_points* mono, int nodes, ps_points** out) {
@@ -120,26 +111,20 @@ static int points_scale_each_t(ps_ctx* c, const ps_points* pts, const Fr* k_mont
     constexpr unsigned LN = FieldTraits<KF>::LANES;
     const size_t n = pts->n;
     hipStream_t st = c->stream;
-    int rc = points_alloc(c, pts->group, n, out);
-    if (rc || n == 0) return rc;
+    const char* who = "scaling a point array";
+    Scope scope(st);
+    int rc = points_alloc(c, pts->group, n, scope.result(out));
+    if (rc || n == 0) return scope.finish(rc);
     char* buf = nullptr;  // n XYZZ points, then batch_to_affine's chain products
-    auto bail = [&](const char* what, hipError_t err) {
-        (void)hipStreamSynchronize(st);
-        if (buf) (void)hipFree(buf);
-        ps_points_free(*out);
-        *out = nullptr;
-        return fail(PS_ERR_HIP, std::string("scaling a point array: ") + what + ": " + hipGetErrorString(err));
-    };
     hipError_t e;
-    if ((e = hipMalloc((void**)&buf, batch_affine_tmp_bytes(n, sizeof(Xyzz<F>)))) != hipSuccess) return bail("hipMalloc", e);
-    if (storage_wait_ready(pts->st, st)) return bail("event wait", hipErrorUnknown);
+    if ((e = scope.device(&buf, batch_affine_tmp_bytes(n, sizeof(Xyzz<F>)))) != hipSuccess) return fail_hip(who, "hipMalloc", e);
+    if (storage_wait_ready(pts->st, st)) return fail_hip(who, "event wait", hipErrorUnknown);
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, (Xyzz<F>*)buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (Xyzz<F>*)buf, (u32)n, k_mont, ~0ull);
     batch_to_affine<F>(c, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
-    if ((e = hipGetLastError()) != hipSuccess) return bail("kernels", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bail("run", e);
-    (void)hipFree(buf);
-    return PS_OK;
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "kernels", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(who, "run", e);
+    return scope.finish(PS_OK);
 }
 static int points_scale_each(ps_ctx* c, const ps_points* pts, const Fr* k_mont, ps_points** out) {
     return pts->group == PS_G1 ? points_scale_each_t<Fp>(c, pts, k_mont, out) : points_scale_each_t<Fp2>(c, pts, k_mont, out);
@@ -150,17 +135,13 @@ static int points_scale_each(ps_ctx* c, const ps_points* pts, const Fr* k_mont, 
 // through random twiddles (tests/test_prover_gpu.py).
 static int debug_points_scale(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, ps_points** out) {
     const size_t n = pts->n;
+    Scope scope(c->stream);
     Fr* km = nullptr;
-    hipError_t e = hipMalloc((void**)&km, sizeof(Fr) * n);
-    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_debug_points_scale: hipMalloc: ") + hipGetErrorString(e));
-    int rc = storage_wait_ready(sc->st, c->stream) ? fail(PS_ERR_HIP, "ps_debug_points_scale: event wait failed") : PS_OK;
-    if (!rc) {
-        hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(n)), dim3(256), 0, c->stream, km, scalars_ptr(sc), (u64)n);
-        rc = points_scale_each(c, pts, km, out);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(km);
-    return rc;
+    hipError_t e = scope.device(&km, n);
+    if (e != hipSuccess) return fail_hip("ps_debug_points_scale", "hipMalloc", e);
+    if (storage_wait_ready(sc->st, c->stream)) return fail(PS_ERR_HIP, "ps_debug_points_scale: event wait failed");
+    hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(n)), dim3(256), 0, c->stream, km, scalars_ptr(sc), (u64)n);
+    return points_scale_each(c, pts, km, out);
 }
 extern "C" int ps_debug_points_scale(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, ps_points** out) {
     if (!c || !pts || !sc || !out) return fail(PS_ERR_ARG, "ps_debug_points_scale: NULL argument");

@@ -165,11 +165,10 @@ extern "C" int ps_msm_batch(ps_ctx* c, const ps_points* pts, const ps_scalars* s
     if (!batch_passes((u64)k, shape, msm_batch_limits(c), &passes)) {
         // not even one member fits a pass (n * W >= 2^31, or a forced window whose W * NB buckets exceed the sort's): one by one
         for (size_t j = 0; j < k; j++) {
-            ps_scalars* sl = nullptr;
-            int rc = ps_scalars_slice(sc, j * n, n, &sl);
-            if (rc) return rc;
-            rc = ps_msm(c, pts, sl, out + j * wb);
-            ps_scalars_free(sl);
+            Scope scope;
+            ps_scalars** sl = scope.scalars();
+            int rc = ps_scalars_slice(sc, j * n, n, sl);
+            if (!rc) rc = ps_msm(c, pts, *sl, out + j * wb);
             if (rc) return rc;
         }
         return PS_OK;

@@ -203,9 +203,8 @@ static int qap_create_from(ps_ctx* c, size_t n, size_t m, size_t nio, const CsrS
         if (e != hipSuccess) rc = fail(PS_ERR_HIP, std::string("building the per-n QAP tables: ") + hipGetErrorString(e));
     }
     if (rc != PS_OK) {
-        std::string keep = g_last_error;
+        KeepError keep;
         ps_qap_free(q);
-        g_last_error = keep;
         return rc;
     }
     *out = q;
@@ -342,20 +341,17 @@ extern "C" int ps_poly_mul(ps_ctx* c, const ps_scalars* a, const ps_scalars* b, 
     const u64 S = 1ull << p;
     HIP_TRY(ntt_tables_ensure(tabs, p, st));
     if (storage_wait_ready(a->st, st) || storage_wait_ready(b->st, st)) return fail(PS_ERR_HIP, "ps_poly_mul: event wait failed");
+    Scope scope(st);
     Fr *ta = nullptr, *tb = nullptr, *am = nullptr, *bm = nullptr;
-    HIP_TRY(hipMalloc((void**)&ta, sizeof(Fr) * S));
-    HIP_TRY(hipMalloc((void**)&tb, sizeof(Fr) * S));
-    HIP_TRY(hipMalloc((void**)&am, sizeof(Fr) * a->n));
-    HIP_TRY(hipMalloc((void**)&bm, sizeof(Fr) * b->n));
+    HIP_TRY(scope.device(&ta, S));
+    HIP_TRY(scope.device(&tb, S));
+    HIP_TRY(scope.device(&am, a->n));
+    HIP_TRY(scope.device(&bm, b->n));
     hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(a->n)), dim3(256), 0, st, am, scalars_ptr(a), (u64)a->n);
     hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(b->n)), dim3(256), 0, st, bm, scalars_ptr(b), (u64)b->n);
     hipError_t e = poly_mul_dev(tabs, st, am, a->n, bm, b->n, ta, nout, ta, tb);
-    int rc = PS_OK;
-    if (e != hipSuccess) rc = fail(PS_ERR_HIP, std::string("poly_mul: ") + hipGetErrorString(e));
-    if (rc == PS_OK) rc = scalars_from_mont(c, ta, nout, out);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(ta); (void)hipFree(tb); (void)hipFree(am); (void)hipFree(bm);
-    return rc;
+    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("poly_mul: ") + hipGetErrorString(e));
+    return scope.finish(scalars_from_mont(c, ta, nout, scope.result(out)));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -376,12 +372,11 @@ static Xyzz<F> host_point(const uint8_t* p, bool& ok) {
 
 // run one MSM with a sub-range of a scalar vector
 static int msm_range(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, size_t first, size_t n, uint8_t* out) {
-    ps_scalars* view = nullptr;
-    int rc = ps_scalars_slice(sc, first, n, &view);
+    Scope scope;
+    ps_scalars** view = scope.scalars();
+    int rc = ps_scalars_slice(sc, first, n, view);
     if (rc) return rc;
-    rc = ps_msm(c, pts, view, out);
-    ps_scalars_free(view);
-    return rc;
+    return ps_msm(c, pts, *view, out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -404,27 +399,22 @@ static void host_fixed_base(uint8_t* out, const uint8_t* k_be32) {  // k * G on 
 // u_i(x), v_i(x), w_i(x) = (M^T l(x))_i with l_j the Lagrange basis on {1..n} (qap.go:42-55).
 struct SetupWork {
     hipStream_t st;
-    std::vector<void*> tmp;
+    Scope scope;  // the work buffers, and the key's arrays as results: released once the stream is idle
+    explicit SetupWork(hipStream_t stream) : st(stream), scope(stream) {}
     Fr *pw = nullptr, *uvw[3] = {nullptr, nullptr, nullptr};
     Fr* lj = nullptr;  // l_j(x), j = 1..n: the Lagrange basis of the QAP domain at the secret point
     Fr zx;
     FrPow2Table tab;
     int alloc(Fr** p, size_t cnt) {
-        hipError_t e = hipMalloc((void**)p, sizeof(Fr) * std::max<size_t>(cnt, 1));
+        hipError_t e = scope.device(p, cnt);
         if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("hipMalloc setup: ") + hipGetErrorString(e));
-        tmp.push_back(*p);
         return PS_OK;
-    }
-    void cleanup() {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) (void)hipFree(p);
-        tmp.clear();
     }
 };
 
 static int setup_var_evals(ps_ctx* c, const ps_qap* q, const Fr& x, const char* who, SetupWork& wk) {
     const size_t n = q->n, m = q->m;
-    hipStream_t st = wk.st = c->stream;
+    hipStream_t st = wk.st;
     // x in {1..n} would make a Lagrange denominator vanish (probability n/r for a random x)
     {
         u32 xw[8];
@@ -471,14 +461,16 @@ static int setup_shifted_lagrange(ps_ctx* c, const ps_qap* q, const Fr& x, Fr* o
         if (small && xv >= 1 && xv <= cnt) return fail(PS_ERR_ARG, "setup: the secret point lies on the nodes n+1..2n-1");
     }
     const unsigned pblocks = nblk(cnt);
-    Fr* partial = nullptr;
-    HIP_TRY(hipMalloc((void**)&partial, sizeof(Fr) * std::max<unsigned>(pblocks, 1)));
-    hipLaunchKernelGGL(k_prod_x_minus_j, dim3(pblocks), dim3(256), 0, st, partial, xs, (u64)cnt);
     std::vector<Fr> hp(pblocks);
-    hipError_t e = hipMemcpyAsync(hp.data(), partial, sizeof(Fr) * pblocks, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(partial);
-    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("setup: ") + hipGetErrorString(e));
+    {
+        Scope scope(st);
+        Fr* partial = nullptr;
+        HIP_TRY(scope.device(&partial, pblocks));
+        hipLaunchKernelGGL(k_prod_x_minus_j, dim3(pblocks), dim3(256), 0, st, partial, xs, (u64)cnt);
+        hipError_t e = hipMemcpyAsync(hp.data(), partial, sizeof(Fr) * pblocks, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("setup: ") + hipGetErrorString(e));
+    }
     Fr zs = fr_one();
     for (auto& v : hp) zs = fr_mul(zs, v);
     hipLaunchKernelGGL(k_lagrange_at, dim3(nblk(cnt)), dim3(256), 0, st, out, (const Fr*)q->qt.invfact, xs, zs, (u64)cnt);
@@ -488,12 +480,11 @@ static int setup_shifted_lagrange(ps_ctx* c, const ps_qap* q, const Fr& x, Fr* o
 
 // points = { src[i] * G } for a Montgomery-form device array
 static int commit_mont(ps_ctx* c, int group, const Fr* src, size_t cnt, ps_points** out) {
-    ps_scalars* sc = nullptr;
-    int rc = scalars_from_mont(c, src, cnt, &sc);
+    Scope scope;
+    ps_scalars** sc = scope.scalars();
+    int rc = scalars_from_mont(c, src, cnt, sc);
     if (rc) return rc;
-    rc = ps_points_from_scalars(c, group, sc, out);
-    ps_scalars_free(sc);
-    return rc;
+    return ps_points_from_scalars(c, group, *sc, out);
 }
 
 extern "C" int ps_groth16_setup(ps_ctx* c, const ps_qap* q, const ps_groth16_toxic* tw, ps_groth16_crs* out) {
@@ -507,45 +498,38 @@ extern "C" int ps_groth16_setup(ps_ctx* c, const ps_qap* q, const ps_groth16_tox
              x = fr_mont_from_be32(tw->x), gamma = fr_mont_from_be32(tw->gamma);
     if (fr_is_zero(delta) || fr_is_zero(gamma)) return fail(PS_ERR_ARG, "ps_groth16_setup: delta and gamma must be non-zero");
     const Fr dinv = fr_inv(delta), ginv = fr_inv(gamma);
-    SetupWork wk;
+    SetupWork wk(st);
+    for (ps_points** made : {&out->xi, &out->xi2, &out->xi_t, &out->io_lp, &out->nio_lp, &out->lxi, &out->lxi2, &out->lxi_t}) wk.scope.result(made);
     Fr* lin = nullptr;
     int rc = setup_var_evals(c, q, x, "ps_groth16_setup", wk);
     if (!rc) rc = wk.alloc(&lin, m);
-    if (rc) { wk.cleanup(); return rc; }
+    if (rc) return rc;
     Fr* pw = wk.pw;
     hipLaunchKernelGGL(k_linear_poly, dim3(nblk(m)), dim3(256), 0, st, lin, (const Fr*)wk.uvw[0], (const Fr*)wk.uvw[1],
                        (const Fr*)wk.uvw[2], alpha, beta, ginv, dinv, (u64)diff, (u64)m);
-    do {
-        // Xi, Xi2 = {x^i G}, i < n            (groth16.go:79-80)
-        hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n)), dim3(256), 0, st, pw, wk.tab, fr_one(), (u64)n);
-        if ((rc = commit_mont(c, PS_G1, pw, n, &out->xi))) break;
-        if ((rc = commit_mont(c, PS_G2, pw, n, &out->xi2))) break;
-        // XiT = {x^i t(x)/delta G}, i < n-1   (groth16.go:94-97)
-        hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n - 1)), dim3(256), 0, st, pw, wk.tab, fr_mul(wk.zx, dinv), (u64)(n - 1));
-        if ((rc = commit_mont(c, PS_G1, pw, n - 1, &out->xi_t))) break;
-        // IoLP / NioLP                         (groth16.go:86-91)
-        if ((rc = commit_mont(c, PS_G1, lin, diff, &out->io_lp))) break;
-        if ((rc = commit_mont(c, PS_G1, lin + diff, m - diff, &out->nio_lp))) break;
-        // the same CRS in Lagrange form (see ps_groth16_pk): l_j(x) G1, l_j(x) G2, lambda_k(x) t(x)/delta G1
-        if ((rc = commit_mont(c, PS_G1, wk.lj, n, &out->lxi))) break;
-        if ((rc = commit_mont(c, PS_G2, wk.lj, n, &out->lxi2))) break;
-        if ((rc = setup_shifted_lagrange(c, q, x, pw))) break;
-        hipLaunchKernelGGL(k_fr_scale, dim3(nblk(n - 1)), dim3(256), 0, st, pw, (const Fr*)pw, fr_mul(wk.zx, dinv), (u64)(n - 1));
-        if ((rc = commit_mont(c, PS_G1, pw, n - 1, &out->lxi_t))) break;
-    } while (0);
-    wk.cleanup();
-    if (rc) {
-        ps_points_free(out->lxi); ps_points_free(out->lxi2); ps_points_free(out->lxi_t);
-        ps_points_free(out->xi); ps_points_free(out->xi2); ps_points_free(out->xi_t); ps_points_free(out->io_lp); ps_points_free(out->nio_lp);
-        memset(out, 0, sizeof *out);
-        return rc;
-    }
+    // Xi, Xi2 = {x^i G}, i < n            (groth16.go:79-80)
+    hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n)), dim3(256), 0, st, pw, wk.tab, fr_one(), (u64)n);
+    if ((rc = commit_mont(c, PS_G1, pw, n, &out->xi))) return rc;
+    if ((rc = commit_mont(c, PS_G2, pw, n, &out->xi2))) return rc;
+    // XiT = {x^i t(x)/delta G}, i < n-1   (groth16.go:94-97)
+    hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n - 1)), dim3(256), 0, st, pw, wk.tab, fr_mul(wk.zx, dinv), (u64)(n - 1));
+    if ((rc = commit_mont(c, PS_G1, pw, n - 1, &out->xi_t))) return rc;
+    // IoLP / NioLP                         (groth16.go:86-91)
+    if ((rc = commit_mont(c, PS_G1, lin, diff, &out->io_lp))) return rc;
+    if ((rc = commit_mont(c, PS_G1, lin + diff, m - diff, &out->nio_lp))) return rc;
+    // the same CRS in Lagrange form (see ps_groth16_pk): l_j(x) G1, l_j(x) G2, lambda_k(x) t(x)/delta G1
+    if ((rc = commit_mont(c, PS_G1, wk.lj, n, &out->lxi))) return rc;
+    if ((rc = commit_mont(c, PS_G2, wk.lj, n, &out->lxi2))) return rc;
+    if ((rc = setup_shifted_lagrange(c, q, x, pw))) return rc;
+    hipLaunchKernelGGL(k_fr_scale, dim3(nblk(n - 1)), dim3(256), 0, st, pw, (const Fr*)pw, fr_mul(wk.zx, dinv), (u64)(n - 1));
+    if ((rc = commit_mont(c, PS_G1, pw, n - 1, &out->lxi_t))) return rc;
     host_fixed_base<Fp>(out->alpha, tw->alpha);   // groth16.go:67-76
     host_fixed_base<Fp>(out->beta, tw->beta);
     host_fixed_base<Fp2>(out->beta2, tw->beta);
     host_fixed_base<Fp>(out->delta, tw->delta);
     host_fixed_base<Fp2>(out->delta2, tw->delta);
     host_fixed_base<Fp2>(out->gamma, tw->gamma);
+    wk.scope.finish(PS_OK);  // (the key is the caller's from here, as it has been when this last wait fails)
     HIP_TRY(hipStreamSynchronize(st));
     return PS_OK;
 }
@@ -581,43 +565,38 @@ extern "C" int ps_phgr13_setup(ps_ctx* c, const ps_qap* q, const ps_phgr13_toxic
              ay = fr_mont_from_be32(tw->ay), rv = fr_mont_from_be32(tw->rv), rw = fr_mont_from_be32(tw->rw),
              beta = fr_mont_from_be32(tw->beta), gamma = fr_mont_from_be32(tw->gamma);
     const Fr ry = fr_mul(rv, rw);  // pinochio.go:117
-    SetupWork wk;
+    SetupWork wk(st);
+    for (ps_points** made : {&out->gsi, &out->vs, &out->ws, &out->ys, &out->vas, &out->was, &out->yas, &out->vbs, &out->wbs, &out->ybs, &out->vk_vs,
+                             &out->vk_ws, &out->vk_ys, &out->lgsi})
+        wk.scope.result(made);
     int rc = setup_var_evals(c, q, s, "ps_phgr13_setup", wk);
-    if (rc) { wk.cleanup(); return rc; }
+    if (rc) return rc;
     auto scaled = [&](int group, const Fr* src, size_t first, size_t cnt, const Fr& scale, ps_points** dst) -> int {
         if (cnt) hipLaunchKernelGGL(k_fr_scale, dim3(nblk(cnt)), dim3(256), 0, st, wk.pw, src + first, scale, (u64)cnt);
         return commit_mont(c, group, wk.pw, cnt, dst);
     };
-    do {
-        // gsi = {s^i G}, i = 0..n-2                                         (pinochio.go:101)
-        hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n - 1)), dim3(256), 0, st, wk.pw, wk.tab, fr_one(), (u64)(n - 1));
-        if ((rc = commit_mont(c, PS_G1, wk.pw, n - 1, &out->gsi))) break;
-        // ... and in Lagrange form on the nodes n+1..2n-1 (see ps_phgr13_ek.lgsi)
-        if ((rc = setup_shifted_lagrange(c, q, s, wk.pw))) break;
-        if ((rc = commit_mont(c, PS_G1, wk.pw, n - 1, &out->lgsi))) break;
-        // g_v^(v_k(s)), g_w^(w_k(s)), g_y^(y_k(s)) for all k                 (:158-160)
-        if ((rc = scaled(PS_G1, wk.uvw[0], 0, m, rv, &out->vk_vs))) break;
-        if ((rc = scaled(PS_G2, wk.uvw[1], 0, m, rw, &out->vk_ws))) break;
-        if ((rc = scaled(PS_G1, wk.uvw[2], 0, m, ry, &out->vk_ys))) break;
-        // the prover's non-IO part                                           (:123-125)
-        if ((rc = ps_points_slice(out->vk_vs, diff, nn, &out->vs))) break;
-        if ((rc = ps_points_slice(out->vk_ws, diff, nn, &out->ws))) break;
-        if ((rc = ps_points_slice(out->vk_ys, diff, nn, &out->ys))) break;
-        // shifted by alpha                                                   (:127-129; was uses g1w = rw*G1)
-        if ((rc = scaled(PS_G1, wk.uvw[0], diff, nn, fr_mul(rv, av), &out->vas))) break;
-        if ((rc = scaled(PS_G1, wk.uvw[1], diff, nn, fr_mul(rw, aw), &out->was))) break;
-        if ((rc = scaled(PS_G1, wk.uvw[2], diff, nn, fr_mul(ry, ay), &out->yas))) break;
-        // shifted by beta                                                    (:135-137)
-        if ((rc = scaled(PS_G1, wk.uvw[0], diff, nn, fr_mul(rv, beta), &out->vbs))) break;
-        if ((rc = scaled(PS_G1, wk.uvw[1], diff, nn, fr_mul(rw, beta), &out->wbs))) break;
-        if ((rc = scaled(PS_G1, wk.uvw[2], diff, nn, fr_mul(ry, beta), &out->ybs))) break;
-    } while (0);
-    wk.cleanup();
-    if (rc) {
-        ps_phgr13_crs_free(out);
-        memset(out, 0, sizeof *out);
-        return rc;
-    }
+    // gsi = {s^i G}, i = 0..n-2                                         (pinochio.go:101)
+    hipLaunchKernelGGL(k_fr_powers, dim3(nblk(n - 1)), dim3(256), 0, st, wk.pw, wk.tab, fr_one(), (u64)(n - 1));
+    if ((rc = commit_mont(c, PS_G1, wk.pw, n - 1, &out->gsi))) return rc;
+    // ... and in Lagrange form on the nodes n+1..2n-1 (see ps_phgr13_ek.lgsi)
+    if ((rc = setup_shifted_lagrange(c, q, s, wk.pw))) return rc;
+    if ((rc = commit_mont(c, PS_G1, wk.pw, n - 1, &out->lgsi))) return rc;
+    // g_v^(v_k(s)), g_w^(w_k(s)), g_y^(y_k(s)) for all k                 (:158-160)
+    if ((rc = scaled(PS_G1, wk.uvw[0], 0, m, rv, &out->vk_vs))) return rc;
+    if ((rc = scaled(PS_G2, wk.uvw[1], 0, m, rw, &out->vk_ws))) return rc;
+    if ((rc = scaled(PS_G1, wk.uvw[2], 0, m, ry, &out->vk_ys))) return rc;
+    // the prover's non-IO part                                           (:123-125)
+    if ((rc = ps_points_slice(out->vk_vs, diff, nn, &out->vs))) return rc;
+    if ((rc = ps_points_slice(out->vk_ws, diff, nn, &out->ws))) return rc;
+    if ((rc = ps_points_slice(out->vk_ys, diff, nn, &out->ys))) return rc;
+    // shifted by alpha                                                   (:127-129; was uses g1w = rw*G1)
+    if ((rc = scaled(PS_G1, wk.uvw[0], diff, nn, fr_mul(rv, av), &out->vas))) return rc;
+    if ((rc = scaled(PS_G1, wk.uvw[1], diff, nn, fr_mul(rw, aw), &out->was))) return rc;
+    if ((rc = scaled(PS_G1, wk.uvw[2], diff, nn, fr_mul(ry, ay), &out->yas))) return rc;
+    // shifted by beta                                                    (:135-137)
+    if ((rc = scaled(PS_G1, wk.uvw[0], diff, nn, fr_mul(rv, beta), &out->vbs))) return rc;
+    if ((rc = scaled(PS_G1, wk.uvw[1], diff, nn, fr_mul(rw, beta), &out->wbs))) return rc;
+    if ((rc = scaled(PS_G1, wk.uvw[2], diff, nn, fr_mul(ry, beta), &out->ybs))) return rc;
     uint8_t k[32];
     host_fixed_base<Fp2>(out->av, tw->av);        // :144
     host_fixed_base<Fp>(out->aw, tw->aw);         // :146 (a G1 element in the reference as well)
@@ -628,6 +607,7 @@ extern "C" int ps_phgr13_setup(ps_ctx* c, const ps_qap* q, const ps_phgr13_toxic
     host_fixed_base<Fp2>(out->bgamma2, k);        // :153
     fr_mont_to_be32(k, fr_mul(wk.zx, ry));        // t(s) * r_y, :155-157
     host_fixed_base<Fp2>(out->yts, k);
+    wk.scope.finish(PS_OK);  // (as in ps_groth16_setup)
     HIP_TRY(hipStreamSynchronize(st));
     return PS_OK;
 }
@@ -701,23 +681,23 @@ static int groth16_prepare(ps_ctx* c, const ps_groth16_pk* pk, size_t n, size_t 
     if (xi->n != n || xi2->n != n || xi_t->n + 1 != n)  // algebra.go:350-352 would panic
         return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(n) + " and blinded eval points " +
                                        std::to_string(xi->n));
-    ps_points *fa = nullptr, *fb = nullptr, *fc = nullptr;
+    Scope scope;
+    ps_points **fa = scope.points(), **fb = scope.points(), **fc = scope.points();
     int rc;
     for (const ps_points* arr : {xi, xi2, pk->nio_lp, xi_t})
         if (storage_wait_ready(arr->st, c->stream)) return fail(PS_ERR_HIP, "ps_groth16_prove: event wait failed");
-    if ((rc = upload_fixed_points<Fp>(c, PS_G1, {pk->delta, pk->alpha}, &fa))) return rc;
-    if ((rc = upload_fixed_points<Fp2>(c, PS_G2, {pk->delta2, pk->beta2}, &fb))) { ps_points_free(fa); return rc; }
-    if (split) rc = upload_fixed_points<Fp>(c, PS_G1, {pk->beta}, &fc);
-    else rc = upload_fixed_points<Fp>(c, PS_G1, {pk->delta, pk->alpha, pk->beta}, &fc);
-    if (rc) { ps_points_free(fa); ps_points_free(fb); return rc; }
-    rc = points_concat(c, PS_G1, {{points_ptr(xi), n}, {points_ptr(fa), 2}}, &c->g16_pa);
-    if (!rc) rc = points_concat(c, PS_G2, {{points_ptr(xi2), n}, {points_ptr(fb), 2}}, &c->g16_pb);
+    if ((rc = upload_fixed_points<Fp>(c, PS_G1, {pk->delta, pk->alpha}, fa))) return rc;
+    if ((rc = upload_fixed_points<Fp2>(c, PS_G2, {pk->delta2, pk->beta2}, fb))) return rc;
+    if (split) rc = upload_fixed_points<Fp>(c, PS_G1, {pk->beta}, fc);
+    else rc = upload_fixed_points<Fp>(c, PS_G1, {pk->delta, pk->alpha, pk->beta}, fc);
+    if (rc) return rc;
+    rc = points_concat(c, PS_G1, {{points_ptr(xi), n}, {points_ptr(*fa), 2}}, &c->g16_pa);
+    if (!rc) rc = points_concat(c, PS_G2, {{points_ptr(xi2), n}, {points_ptr(*fb), 2}}, &c->g16_pb);
     // split form of C (groth16_prove_impl): PC = [NioLP | XiT | Beta], no third copy of Xi
-    if (!rc && split) rc = points_concat(c, PS_G1, {{points_ptr(pk->nio_lp), nn}, {points_ptr(xi_t), n - 1}, {points_ptr(fc), 1}}, &c->g16_pc);
-    else if (!rc) rc = points_concat(c, PS_G1, {{points_ptr(pk->nio_lp), nn}, {points_ptr(xi_t), n - 1}, {points_ptr(xi), n}, {points_ptr(fc), 3}},
+    if (!rc && split) rc = points_concat(c, PS_G1, {{points_ptr(pk->nio_lp), nn}, {points_ptr(xi_t), n - 1}, {points_ptr(*fc), 1}}, &c->g16_pc);
+    else if (!rc) rc = points_concat(c, PS_G1, {{points_ptr(pk->nio_lp), nn}, {points_ptr(xi_t), n - 1}, {points_ptr(xi), n}, {points_ptr(*fc), 3}},
                                      &c->g16_pc);
-    (void)hipStreamSynchronize(c->stream);
-    ps_points_free(fa); ps_points_free(fb); ps_points_free(fc);
+    (void)hipStreamSynchronize(c->stream);  // the copies out of fa, fb, fc are complete
     // window tables when there is room for them (13 rows of 128 / 256 B per point): a table that does not fit is not an
     // error -- the sums over that array take the plain plan, which needs no memory beyond the array itself
     if (!rc && tabs) {
@@ -764,8 +744,7 @@ static inline const u32* small_slot(const ps_ctx* c, int i) { return (const u32*
 // the quotient 2.4 x slower (11.9 -> 29 ms) for the same total -- the NTT passes are VALU-bound by instructions, the
 // bucket accumulations by multiplications, so neither has idle issue slots to lend -- and even the digit sorts alone
 // (LDS / memory-bound, but 140 KB of LDS per workgroup) cost the quotient 2.7 ms for 0.7 ms of sorting hidden.
-struct G16Vectors { ps_scalars *SA = nullptr, *SB = nullptr, *SC = nullptr; };
-static void g16_free(G16Vectors& v) { v = G16Vectors(); }  // (the vectors are the context's: prover_vector, capi.hip)
+struct G16Vectors { ps_scalars *SA = nullptr, *SB = nullptr, *SC = nullptr; };  // borrowed: the vectors are the context's (prover_vector, capi.hip)
 
 // stage 0: SpMV + gate check; 1: A interpolated, SA ready; 2: B interpolated, SB ready; 3: h, SC ready.
 static int g16_quotient_stage(ps_ctx* c, const ps_qap* q, const ps_scalars* sol, hipStream_t qs, int stage, const Fr& rm, const Fr& sm,
@@ -927,10 +906,8 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
     if ((rc = groth16_small_scalars(c, r_be32, s_be32, &rm, &sm))) return rc;
     G16Vectors v;
     if ((rc = prover_vector(c, 0, n + 2, &v.SA)) || (rc = prover_vector(c, 1, n + 2, &v.SB)) ||
-        (rc = prover_vector(c, 2, split ? nn + (n - 1) + 1 : nn + (n - 1) + n + 3, &v.SC))) {
-        g16_free(v);
+        (rc = prover_vector(c, 2, split ? nn + (n - 1) + 1 : nn + (n - 1) + n + 3, &v.SC)))
         return rc;
-    }
     // the quotient's stream: the context's high-priority one, ordered after whatever the caller left on the context stream
     hipStream_t qs = c->tail;
     if (!c->ev_q) HIP_TRY(hipEventCreateWithFlags(&c->ev_q, hipEventDisableTiming));
@@ -940,8 +917,7 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
     // A witness uploaded as int64 (the reference's Vector = []int) keeps its short-scalar plan: its NioLP part is
     // then a sum of its own (a quarter of the windows) over the caller's array, and C = C' + N.
     const bool split_nio = nn > 0 && sol->max_bits < 255;
-    std::vector<ps_points*> pv;  // slices, freed at the end
-    std::vector<ps_scalars*> sv;
+    Scope scope;  // the slices the sums run over, freed at the return: every way out from here on passes sums.drain() below
     // kind: 0 = A, 1 = B, 2 = a part of C, 3 = B1' (split form); the results of a kind's pieces in the order of their launch
     SumQueue sums{c, false};
     std::vector<std::vector<uint8_t>> parts[4];
@@ -951,13 +927,12 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
             const ps_points* pp = pts;
             const ps_scalars* ss = sc;
             if (pc.off != 0 || pc.len != pts->n) {
-                ps_points* p1 = nullptr;
-                ps_scalars* s1 = nullptr;
-                int r2 = ps_points_slice(pts, pc.off, pc.len, &p1);
-                if (!r2) r2 = ps_scalars_slice(sc, pc.off, pc.len, &s1);
-                if (r2) { ps_points_free(p1); ps_scalars_free(s1); return r2; }
-                pv.push_back(p1); sv.push_back(s1);
-                pp = p1; ss = s1;
+                ps_points** p1 = scope.points();
+                ps_scalars** s1 = scope.scalars();
+                int r2 = ps_points_slice(pts, pc.off, pc.len, p1);
+                if (!r2) r2 = ps_scalars_slice(sc, pc.off, pc.len, s1);
+                if (r2) return r2;
+                pp = *p1; ss = *s1;
             }
             std::vector<uint8_t> slot(wire_bytes(pts->group));
             parts[kind].push_back(slot);
@@ -973,8 +948,8 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
         for (auto& p : parts[kind]) flat.insert(flat.end(), p.begin(), p.end());
         return ps_points_sum(group, flat.data(), parts[kind].size(), out);
     };
-    ps_points *pc_rest = nullptr, *pa_xi = nullptr;
-    ps_scalars *sc_rest = nullptr, *sol_nio = nullptr, *sb_b = nullptr;
+    ps_points **pc_rest = scope.points(), **pa_xi = scope.points();
+    ps_scalars **sc_rest = scope.scalars(), **sol_nio = scope.scalars(), **sb_b = scope.scalars();
     // Small circuits: launching the sums before the host waits for the gate check (they wait on the device for their
     // scalars' ready events) was measured and is off (PS_G16_EARLY_SUMS = 0): the GPU finishes earlier (0.80 instead of
     // 1.02 ms under the profiler at 2^10 constraints) but the proof takes LONGER on the wall clock (1.2 vs 0.93 ms) -- a
@@ -984,21 +959,21 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
         int r2 = launch(1, c->g16_pb, v.SB, {{0, n}}, 2);  // B first: the longest point pass
         if (!r2) r2 = launch(0, c->g16_pa, v.SA, {{0, n}}, 2);
         if (!r2 && split) {  // B1' = sum_j b_j Xi_j: views of PA and SB
-            if ((r2 = ps_points_slice(c->g16_pa, 0, n, &pa_xi)) || (r2 = ps_scalars_slice(v.SB, 0, n, &sb_b))) return r2;
-            r2 = launch(3, pa_xi, sb_b, {{0, n}}, 0);
+            if ((r2 = ps_points_slice(c->g16_pa, 0, n, pa_xi)) || (r2 = ps_scalars_slice(v.SB, 0, n, sb_b))) return r2;
+            r2 = launch(3, *pa_xi, *sb_b, {{0, n}}, 0);
         }
         return r2;
     };
     auto launch_C = [&]() -> int {
         int r2 = PS_OK;
         if (split_nio) {
-            if ((r2 = ps_scalars_slice(sol, diff, nn, &sol_nio))) return r2;
-            if ((r2 = launch(2, pk->nio_lp, sol_nio, {{0, nn}}, 0))) return r2;
+            if ((r2 = ps_scalars_slice(sol, diff, nn, sol_nio))) return r2;
+            if ((r2 = launch(2, pk->nio_lp, *sol_nio, {{0, nn}}, 0))) return r2;
             // [XiT | Xi | Delta, Alpha, Beta] = PC without its NioLP head ([XiT | Beta] in the split form)
-            if ((r2 = ps_points_slice(c->g16_pc, nn, c->g16_pc->n - nn, &pc_rest))) return r2;
-            if ((r2 = ps_scalars_slice(v.SC, nn, v.SC->n - nn, &sc_rest))) return r2;
-            if (split) return launch(2, pc_rest, sc_rest, {{0, n - 1}}, 1);
-            return launch(2, pc_rest, sc_rest, {{0, n - 1}, {n - 1, n}}, 3);
+            if ((r2 = ps_points_slice(c->g16_pc, nn, c->g16_pc->n - nn, pc_rest))) return r2;
+            if ((r2 = ps_scalars_slice(v.SC, nn, v.SC->n - nn, sc_rest))) return r2;
+            if (split) return launch(2, *pc_rest, *sc_rest, {{0, n - 1}}, 1);
+            return launch(2, *pc_rest, *sc_rest, {{0, n - 1}, {n - 1, n}}, 3);
         }
         if (split) return launch(2, c->g16_pc, v.SC, {{0, nn}, {nn, n - 1}}, 1);
         return launch(2, c->g16_pc, v.SC, {{0, nn}, {nn, n - 1}, {nn + n - 1, n}}, 3);
@@ -1036,11 +1011,6 @@ static int groth16_prove_impl(ps_ctx* c, const ps_groth16_pk* pk, const ps_qap* 
     // the caller's stream continues after the quotient's
     (void)hipEventRecord(c->ev_q, qs);
     (void)hipStreamWaitEvent(c->stream, c->ev_q, 0);
-    for (auto* p : pv) ps_points_free(p);
-    for (auto* p2 : sv) ps_scalars_free(p2);
-    ps_points_free(pc_rest); ps_scalars_free(sc_rest); ps_scalars_free(sol_nio);
-    ps_points_free(pa_xi); ps_scalars_free(sb_b);
-    g16_free(v);
     if (rc || sums.err) return rc ? rc : sums.err;
     if ((rc = fold(0, PS_G1, A_out)) || (rc = fold(1, PS_G2, B_out)) || (rc = fold(2, PS_G1, C_out))) return rc;
     if (split) {  // C = C' + (s A + r B1')

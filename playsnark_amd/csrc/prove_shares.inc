@@ -188,7 +188,7 @@ struct Phgr13Share {
     const ps_scalars* sv;     // solution[diff + first, cnt]
     const ps_points* hp;      // gsi -- or lgsi -- over this share's range of h
 };
-// hands over this share's range of h as a vector on the context (a view: phgr13_share_sums frees it)
+// hands over this share's range of h as a vector on the context (a view, into a slot of phgr13_share_sums's scope)
 typedef std::function<int(ps_scalars**)> Phgr13GetH;
 
 // The sums of one share on context c.  Order of work (measured at n = 2^20, see groth16_prove_impl): the quotient has run
@@ -208,19 +208,20 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     const size_t cnt = sh.sv->n;
     ps_ctx* ring[PS_MULTI_RING] = {nullptr, nullptr, nullptr, nullptr};
     MsmPlan mpl{};
-    ps_scalars* h = nullptr;
+    Scope scope;
+    ps_scalars** h = scope.scalars();
     bool sums = false, h_launched = false;
     auto t_h = std::chrono::steady_clock::now();
     auto launch_h = [&]() -> int {
         const auto t_wait = std::chrono::steady_clock::now();
-        int r2 = get_h(&h);
+        int r2 = get_h(h);
         if (!h_first) {
             c->phase_ms[0] = ms_since(t_wait);
             t_h = std::chrono::steady_clock::now();
             // not chained behind an accumulation of an earlier call's workspace (the point passes above re-recorded them)
             c->last_chain = nullptr;
         }
-        if (!r2 && !(r2 = msm_launch_impl(c, sh.hp, h, true))) h_launched = true;
+        if (!r2 && !(r2 = msm_launch_impl(c, sh.hp, *h, true))) h_launched = true;
         return r2;
     };
     int rc = PS_OK;
@@ -232,7 +233,7 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     }
     if (!rc && h_first) rc = launch_h();
     if (!rc && cnt) {
-        hipEvent_t after_h = (h_first && h->n && c->last_chain) ? c->last_chain->ev_acc_local : nullptr;
+        hipEvent_t after_h = (h_first && (*h)->n && c->last_chain) ? c->last_chain->ev_acc_local : nullptr;
         if (!(rc = msm_multi_points(c, ring, sh.pts, 7, sh.sv, mpl, after_h))) sums = true;
     }
     if (!rc && !h_first) rc = launch_h();
@@ -255,7 +256,6 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     c->phase_ms[2] = ms_since(t_sums);
     if (!rc && !cnt)  // an empty range: every solution sum is the identity
         for (int i = 0; i < 7; i++) write_identity(i == 1 ? PS_G2 : PS_G1, dst[i]);
-    ps_scalars_free(h);
     return rc;
 }
 
@@ -298,11 +298,11 @@ extern "C" int ps_phgr13_prove(ps_ctx* c, const ps_phgr13_ek* ek, const ps_qap* 
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->phase_ms[0] = ms_since(t_start);
     if (multi) {
-        ps_scalars* view = nullptr;
-        if ((rc = ps_scalars_slice(sol, diff, nn, &view))) return rc;
-        const Phgr13Share sh{{ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, c->phgr_bsum}, view, gsi};
+        Scope scope;
+        ps_scalars** view = scope.scalars();
+        if ((rc = ps_scalars_slice(sol, diff, nn, view))) return rc;
+        const Phgr13Share sh{{ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, c->phgr_bsum}, *view, gsi};
         rc = phgr13_share_sums(c, sh, true, [&](ps_scalars** o) { return ps_scalars_slice(h, 0, h->n, o); }, out);
-        ps_scalars_free(view);
         c->phase_ms[3] = ms_since(t_start);
         return rc;
     }
@@ -353,17 +353,15 @@ extern "C" int ps_phgr13_prove_shard(ps_ctx* c, const ps_phgr13_ek* ek, const ps
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->phase_ms[0] = ms_since(t_start);
     const ps_points* whole[7] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, nn ? c->phgr_bsum : ek->vbs};
-    ps_points* views[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ps_scalars* sv = nullptr;
-    for (int i = 0; i < 7 && !rc; i++) rc = ps_points_slice(whole[i], fs, cs, &views[i]);
-    if (!rc) rc = ps_points_slice(gsi, fh, ch, &views[7]);
-    if (!rc) rc = ps_scalars_slice(sol, diff + fs, cs, &sv);
-    if (!rc) {
-        const Phgr13Share sh{{views[0], views[1], views[2], views[3], views[4], views[5], views[6]}, sv, views[7]};
-        rc = phgr13_share_sums(c, sh, true, [&](ps_scalars** o) { return ps_scalars_slice(h, 0, ch, o); }, part);
-    }
-    for (ps_points* v : views) ps_points_free(v);
-    ps_scalars_free(sv);
+    Scope scope;
+    ps_points** views[8];  // the seven arrays and gsi over this rank's ranges
+    ps_scalars** sv = scope.scalars();
+    for (int i = 0; i < 8; i++) views[i] = scope.points();
+    for (int i = 0; i < 7; i++)
+        if ((rc = ps_points_slice(whole[i], fs, cs, views[i]))) return rc;
+    if ((rc = ps_points_slice(gsi, fh, ch, views[7])) || (rc = ps_scalars_slice(sol, diff + fs, cs, sv))) return rc;
+    const Phgr13Share sh{{*views[0], *views[1], *views[2], *views[3], *views[4], *views[5], *views[6]}, *sv, *views[7]};
+    rc = phgr13_share_sums(c, sh, true, [&](ps_scalars** o) { return ps_scalars_slice(h, 0, ch, o); }, part);
     c->phase_ms[3] = ms_since(t_start);
     return rc;
 }
@@ -415,15 +413,16 @@ extern "C" int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, p
         const ps_phgr13_ek& ek = dev[d].ek;
         const auto t_start = std::chrono::steady_clock::now();
         int rc = hipSetDevice(c->device) == hipSuccess ? PS_OK : fail(PS_ERR_HIP, "ps_phgr13_prove_multi: hipSetDevice failed");
+        Scope scope;  // this thread's, on this device
         size_t fs, cs, fh, ch;
         shard_range_c(nn, (int)d, (int)ndev, &fs, &cs);
         shard_range_c(n - 1, (int)d, (int)ndev, &fh, &ch);
         const ps_points* hp = lag ? ek.lgsi : ek.gsi;
         if (!rc && ctx_busy(c)) rc = fail(PS_ERR_ARG, "ps_phgr13_prove_multi: an MSM is pending on a context");
         if (!rc) rc = phgr13_prepare(c, &ek, cs, hp);  // over the local arrays
-        ps_scalars* sv = nullptr;
-        if (!rc) rc = ps_scalars_slice(dev[d].sol, diff + fs, cs, &sv);
-        const Phgr13Share sh{{ek.vs, ek.ws, ek.ys, ek.vas, ek.was, ek.yas, cs ? c->phgr_bsum : ek.vbs}, sv, hp};
+        ps_scalars** sv = scope.scalars();
+        if (!rc) rc = ps_scalars_slice(dev[d].sol, diff + fs, cs, sv);
+        const Phgr13Share sh{{ek.vs, ek.ws, ek.ys, ek.vas, ek.was, ek.yas, cs ? c->phgr_bsum : ek.vbs}, *sv, hp};
         if (d == 0) {
             ps_scalars* h = nullptr;  // all of h: the others copy from it
             if (!rc) rc = quotient_run(c, dev[0].qap, dev[0].sol, lag ? Q_H_VALUES : Q_H_ONLY);
@@ -452,7 +451,6 @@ extern "C" int ps_phgr13_prove_multi(const ps_phgr13_device* dev, size_t ndev, p
             rc = phgr13_share_sums(c, sh, false, get_h, &parts[d]);
         }
         if (rc) ho.set(rc);
-        ps_scalars_free(sv);
         c->phase_ms[3] = ms_since(t_start);
     };
     run_per_device(ndev, work);
@@ -570,13 +568,14 @@ static int g16_lagrange_share(ps_ctx* c, const G16LocalShare& sh, const uint8_t*
     // plan over NioLP, which no table of full-width windows helps
     for (const ps_points* arr : {sh.lxi2, sh.lxi, sh.lxi_t, sh.nio_lp})
         if (!rc && tables_wanted(c, arr->n) && (arr != sh.nio_lp || sol->max_bits >= 255)) rc = points_ensure_table(c, arr, 0, true);
-    ps_scalars *va = nullptr, *vb = nullptr, *vh = nullptr, *sn = nullptr;  // the context's own vectors, and a view of the solution
+    Scope scope;
+    ps_scalars *va = nullptr, *vb = nullptr, *vh = nullptr, **sn = scope.scalars();  // the context's own vectors, and a view of the solution
     if (!rc) rc = prover_vector(c, 0, cn, &va);
     if (!rc) rc = prover_vector(c, 1, cn, &vb);
     if (!rc) rc = prover_vector(c, 2, ch, &vh);
     if (!rc && !c->ev_q && hipEventCreateWithFlags(&c->ev_q, hipEventDisableTiming) != hipSuccess) rc = fail(PS_ERR_HIP, "Groth16 share: event creation failed");
-    if (!rc) rc = ps_scalars_slice(sol, diff + fq, cq, &sn);
-    if (rc) { ps_scalars_free(sn); return rc; }
+    if (!rc) rc = ps_scalars_slice(sol, diff + fq, cq, sn);
+    if (rc) return rc;
     // the share's own kernels run on the context's high-priority stream, as the quotient of groth16_prove_impl does: the sums
     // launched right behind them (worker contexts) must not hold back what every other device may be waiting for
     hipStream_t qs = c->tail;
@@ -619,7 +618,7 @@ static int g16_lagrange_share(ps_ctx* c, const G16LocalShare& sh, const uint8_t*
         }
         own_ms = ms_since(t_start);
         if (flag) { rc = fail(PS_ERR_NOT_DIVISIBLE, "apocalypse"); break; }  // qap.go:158-160
-        if ((rc = sums.launch(G16_N, sh.nio_lp, sn, part[G16_N]))) break;
+        if ((rc = sums.launch(G16_N, sh.nio_lp, *sn, part[G16_N]))) break;
         // 3. h on the own range of nodes, from the three convolutions wherever they were computed, then h.lxi_t behind it
         const auto t_wait = std::chrono::steady_clock::now();
         if (ch) {
@@ -638,11 +637,9 @@ static int g16_lagrange_share(ps_ctx* c, const G16LocalShare& sh, const uint8_t*
     while (!sums.empty())
         if (sums.finish_one() == G16_H) h_ms = ms_since(t_h);
     (void)hipStreamSynchronize(qs);
-    ps_scalars_free(sn);
     if (rc || sums.err) {
-        std::string keep = g_last_error;
+        KeepError keep;
         (void)ps_ctx_sync(c);
-        g_last_error = keep;
         return rc ? rc : sums.err;
     }
     rc = g16_share_c(part[G16_N], part[G16_H], part[G16_A], part[G16_B1], r_be32, s_be32, C_part);
@@ -773,16 +770,16 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
     std::vector<uint8_t> hA, hB, hH;
     {
         auto piece = [&](size_t d, int what, std::vector<uint8_t>* dst) -> int {  // 0: A, 1: B, 2: h, 3: all three
-            ps_scalars *a = nullptr, *b = nullptr, *h = nullptr;
+            Scope scope;
+            ps_scalars **a = scope.scalars(), **b = scope.scalars(), **h = scope.scalars();
             int rc = PS_OK;
-            if (what == 0) rc = ps_qap_interpolate(dev[d].ctx, dev[d].qap, dev[d].sol, 0, &a);
-            else if (what == 1) rc = ps_qap_interpolate(dev[d].ctx, dev[d].qap, dev[d].sol, 1, &b);
-            else if (what == 2) rc = ps_qap_quotient(dev[d].ctx, dev[d].qap, dev[d].sol, nullptr, nullptr, nullptr, &h);
-            else rc = ps_qap_quotient(dev[d].ctx, dev[d].qap, dev[d].sol, &a, &b, nullptr, &h);
-            if (!rc && a) rc = g16_download_all(dev[d].ctx, a, what == 3 ? hA : *dst);
-            if (!rc && b) rc = g16_download_all(dev[d].ctx, b, what == 3 ? hB : *dst);
-            if (!rc && h) rc = g16_download_all(dev[d].ctx, h, what == 3 ? hH : *dst);
-            ps_scalars_free(a); ps_scalars_free(b); ps_scalars_free(h);
+            if (what == 0) rc = ps_qap_interpolate(dev[d].ctx, dev[d].qap, dev[d].sol, 0, a);
+            else if (what == 1) rc = ps_qap_interpolate(dev[d].ctx, dev[d].qap, dev[d].sol, 1, b);
+            else if (what == 2) rc = ps_qap_quotient(dev[d].ctx, dev[d].qap, dev[d].sol, nullptr, nullptr, nullptr, h);
+            else rc = ps_qap_quotient(dev[d].ctx, dev[d].qap, dev[d].sol, a, b, nullptr, h);
+            if (!rc && *a) rc = g16_download_all(dev[d].ctx, *a, what == 3 ? hA : *dst);
+            if (!rc && *b) rc = g16_download_all(dev[d].ctx, *b, what == 3 ? hB : *dst);
+            if (!rc && *h) rc = g16_download_all(dev[d].ctx, *h, what == 3 ? hH : *dst);
             return rc;
         };
         int rc;
@@ -809,20 +806,20 @@ extern "C" int ps_groth16_prove_multi(const ps_groth16_device* dev, size_t ndev,
         shard_range_c(n, (int)d, (int)ndev, &fn, &cn);
         shard_range_c(n - 1, (int)d, (int)ndev, &fh, &ch);
         shard_range_c(nn, (int)d, (int)ndev, &fq, &cq);
-        ps_scalars *a = nullptr, *b = nullptr, *h = nullptr, *sn = nullptr;
-        int rc = ps_scalars_upload(c, hA.data() + 32 * fn, cn, &a);
-        if (!rc) rc = ps_scalars_upload(c, hB.data() + 32 * fn, cn, &b);
-        if (!rc) rc = ps_scalars_upload(c, hH.data() + 32 * fh, ch, &h);
-        if (!rc) rc = ps_scalars_slice(dev[d].sol, diff + fq, cq, &sn);
+        Scope scope;  // this thread's: freed on it, each handle on its own device
+        ps_scalars **a = scope.scalars(), **b = scope.scalars(), **h = scope.scalars(), **sn = scope.scalars();
+        int rc = ps_scalars_upload(c, hA.data() + 32 * fn, cn, a);
+        if (!rc) rc = ps_scalars_upload(c, hB.data() + 32 * fn, cn, b);
+        if (!rc) rc = ps_scalars_upload(c, hH.data() + 32 * fh, ch, h);
+        if (!rc) rc = ps_scalars_slice(dev[d].sol, diff + fq, cq, sn);
         // five sums through the queue, as ps_msm_launch places them (the context's own stream included: no quotient runs on it)
         SumQueue sums{c, true};
         uint8_t part[5][192];
         const struct { int kind; const ps_points* pts; const ps_scalars* sc; } five[5] = {
-            {G16_B, pk.xi2, b}, {G16_A, pk.xi, a}, {G16_B1, pk.xi, b}, {G16_N, pk.nio_lp, sn}, {G16_H, pk.xi_t, h}};
+            {G16_B, pk.xi2, *b}, {G16_A, pk.xi, *a}, {G16_B1, pk.xi, *b}, {G16_N, pk.nio_lp, *sn}, {G16_H, pk.xi_t, *h}};
         for (int k = 0; k < 5 && !rc && !sums.err; k++) rc = sums.launch(five[k].kind, five[k].pts, five[k].sc, part[five[k].kind]);  // none after a failed finish
         sums.drain();
         if (!rc) rc = sums.err;
-        ps_scalars_free(a); ps_scalars_free(b); ps_scalars_free(h); ps_scalars_free(sn);
         if (!rc) rc = g16_share_c(part[G16_N], part[G16_H], part[G16_A], part[G16_B1], r_be32, s_be32, parts[d].C);
         if (!rc) {
             memcpy(parts[d].A, part[G16_A], 96);

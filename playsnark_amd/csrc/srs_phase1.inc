@@ -32,27 +32,53 @@ extern "C" int ps_scalars_powers(ps_ctx* c, const uint8_t* s_be32, const uint8_t
         return fail(PS_ERR_ENCODING, "ps_scalars_powers: s and c must be below r");
     if ((unsigned long long)n >= (1ull << 32)) return fail(PS_ERR_ARG, "ps_scalars_powers: 2^32 powers or more");
     HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
     Fr* pw = nullptr;
-    hipError_t e = hipMalloc((void**)&pw, sizeof(Fr) * std::max<size_t>(n, 1));
+    hipError_t e = scope.device(&pw, n);
     if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_scalars_powers: hipMalloc: ") + hipGetErrorString(e));
     if (n) fr_powers_launch(c, s, k, n, pw);
-    int rc = scalars_from_mont(c, pw, n, out);
-    if (!rc && (e = hipGetLastError()) != hipSuccess) rc = fail(PS_ERR_HIP, std::string("ps_scalars_powers: kernels: ") + hipGetErrorString(e));
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess && !rc) rc = fail(PS_ERR_HIP, std::string("ps_scalars_powers: run: ") + hipGetErrorString(e));
-    (void)hipFree(pw);
-    if (rc && *out) {
-        std::string keep = g_last_error;
-        ps_scalars_free(*out);
-        *out = nullptr;
-        g_last_error = keep;
-    }
-    return rc;
+    int rc = scalars_from_mont(c, pw, n, scope.result(out));
+    if (rc) return rc;
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_scalars_powers: kernels: ") + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_scalars_powers: run: ") + hipGetErrorString(e));
+    return scope.finish(PS_OK);
 }
 
 static bool srs_groups_ok(const ps_groth16_srs* s) {
     return s->tau_g1->group == PS_G1 && s->tau_g2->group == PS_G2 && s->alpha_tau_g1->group == PS_G1 && s->beta_tau_g1->group == PS_G1;
 }
 
+// The four scaled arrays into a zeroed `out`, arguments validated: all four or none
+static int srs_contribute_run(ps_ctx* c, const ps_groth16_srs* in, const uint8_t* t_be32, const uint8_t* a_be32, const uint8_t* b_be32, const Fr& t, const Fr& a,
+                              const Fr& b, ps_groth16_srs* out, ps_groth16_srs_share* share) {
+    const size_t longest = std::max(std::max(in->tau_g1->n, in->tau_g2->n), std::max(in->alpha_tau_g1->n, in->beta_tau_g1->n));
+    if ((unsigned long long)longest >= (1ull << 32)) return fail(PS_ERR_ARG, "ps_groth16_srs_contribute: an array of 2^32 points or more");
+    ps_points *t1, *t2, *ta, *tb;  // the string's (const) arrays once all four are made
+    Scope scope(c->stream);
+    for (ps_points** made : {&t1, &t2, &ta, &tb}) scope.result(made);
+    Fr* pw = nullptr;  // ONE table, as long as the longest array: t^i, then a t^i, then b t^i (each scaling returns complete)
+    hipError_t e = scope.device(&pw, longest);
+    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_srs_contribute: hipMalloc: ") + hipGetErrorString(e));
+    int rc;
+    uint8_t gen2[192];
+    generator_bytes<Fp2>(gen2);
+    if ((rc = ps_points_lincomb(PS_G2, in->beta_g2, b_be32, 1, out->beta_g2))) return rc;
+    if ((rc = ps_points_lincomb(PS_G2, gen2, t_be32, 1, share->t_g2))) return rc;
+    if ((rc = ps_points_lincomb(PS_G2, gen2, a_be32, 1, share->a_g2))) return rc;
+    if ((rc = ps_points_lincomb(PS_G2, gen2, b_be32, 1, share->b_g2))) return rc;
+    if (longest) fr_powers_launch(c, t, fr_one(), longest, pw);
+    if ((rc = points_scale_each(c, in->tau_g1, pw, &t1))) return rc;
+    if ((rc = points_scale_each(c, in->tau_g2, pw, &t2))) return rc;
+    if (in->alpha_tau_g1->n) fr_powers_launch(c, t, a, in->alpha_tau_g1->n, pw);
+    if ((rc = points_scale_each(c, in->alpha_tau_g1, pw, &ta))) return rc;
+    if (in->beta_tau_g1->n) fr_powers_launch(c, t, b, in->beta_tau_g1->n, pw);
+    if ((rc = points_scale_each(c, in->beta_tau_g1, pw, &tb))) return rc;
+    out->tau_g1 = t1;
+    out->tau_g2 = t2;
+    out->alpha_tau_g1 = ta;
+    out->beta_tau_g1 = tb;
+    return scope.finish(PS_OK);
+}
 extern "C" int ps_groth16_srs_contribute(ps_ctx* c, const ps_groth16_srs* in, const uint8_t* t_be32, const uint8_t* a_be32, const uint8_t* b_be32,
                                          ps_groth16_srs* out, ps_groth16_srs_share* share) {
     if (!c || !in || !t_be32 || !a_be32 || !b_be32 || !out || !share || in == out || !in->tau_g1 || !in->tau_g2 || !in->alpha_tau_g1 || !in->beta_tau_g1)
@@ -65,43 +91,12 @@ extern "C" int ps_groth16_srs_contribute(ps_ctx* c, const ps_groth16_srs* in, co
         return fail(PS_ERR_ENCODING, "ps_groth16_srs_contribute: t, a and b must be below r");
     if (fr_is_zero(t) || fr_is_zero(a) || fr_is_zero(b)) return fail(PS_ERR_ARG, "ps_groth16_srs_contribute: the shares t, a and b must be non-zero");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t longest = std::max(std::max(in->tau_g1->n, in->tau_g2->n), std::max(in->alpha_tau_g1->n, in->beta_tau_g1->n));
-    if ((unsigned long long)longest >= (1ull << 32)) return fail(PS_ERR_ARG, "ps_groth16_srs_contribute: an array of 2^32 points or more");
-    Fr* pw = nullptr;  // ONE table, as long as the longest array: t^i, then a t^i, then b t^i (each scaling returns complete)
-    hipError_t e = hipMalloc((void**)&pw, sizeof(Fr) * std::max<size_t>(longest, 1));
-    if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_srs_contribute: hipMalloc: ") + hipGetErrorString(e));
-    ps_points *t1 = nullptr, *t2 = nullptr, *ta = nullptr, *tb = nullptr;
-    int rc = PS_OK;
-    do {
-        uint8_t gen2[192];
-        generator_bytes<Fp2>(gen2);
-        if ((rc = ps_points_lincomb(PS_G2, in->beta_g2, b_be32, 1, out->beta_g2))) break;
-        if ((rc = ps_points_lincomb(PS_G2, gen2, t_be32, 1, share->t_g2))) break;
-        if ((rc = ps_points_lincomb(PS_G2, gen2, a_be32, 1, share->a_g2))) break;
-        if ((rc = ps_points_lincomb(PS_G2, gen2, b_be32, 1, share->b_g2))) break;
-        if (longest) fr_powers_launch(c, t, fr_one(), longest, pw);
-        if ((rc = points_scale_each(c, in->tau_g1, pw, &t1))) break;
-        if ((rc = points_scale_each(c, in->tau_g2, pw, &t2))) break;
-        if (in->alpha_tau_g1->n) fr_powers_launch(c, t, a, in->alpha_tau_g1->n, pw);
-        if ((rc = points_scale_each(c, in->alpha_tau_g1, pw, &ta))) break;
-        if (in->beta_tau_g1->n) fr_powers_launch(c, t, b, in->beta_tau_g1->n, pw);
-        if ((rc = points_scale_each(c, in->beta_tau_g1, pw, &tb))) break;
-    } while (0);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(pw);
-    if (rc) {
-        std::string keep = g_last_error;
-        for (ps_points* p : {t1, t2, ta, tb}) ps_points_free(p);
+    const int rc = srs_contribute_run(c, in, t_be32, a_be32, b_be32, t, a, b, out, share);
+    if (rc) {  // (the run has freed the arrays it made)
         memset(out, 0, sizeof *out);
         memset(share, 0, sizeof *share);
-        g_last_error = keep;
-        return rc;
     }
-    out->tau_g1 = t1;
-    out->tau_g2 = t2;
-    out->alpha_tau_g1 = ta;
-    out->beta_tau_g1 = tb;
-    return PS_OK;
+    return rc;
 }
 
 // e(a1, b1) == e(a2, b2) for points the caller has validated (no subgroup test here): e(a1, b1) e(-a2, b2) == 1
@@ -112,12 +107,11 @@ static int pairing_pair_equal_trusted(ps_ctx* c, const uint8_t* a1, const uint8_
     g1_negated(g1 + 96, a2);
     memcpy(g2, b1, 192);
     memcpy(g2 + 192, b2, 192);
-    ps_points *p1 = nullptr, *p2 = nullptr;
-    int rc = ps_points_upload(c, PS_G1, g1, 2, PS_FMT_AFFINE, &p1);
-    if (!rc) rc = ps_points_upload(c, PS_G2, g2, 2, PS_FMT_AFFINE, &p2);
-    if (!rc) rc = ps_pairing_product_is_one(c, p1, p2, 0, equal);
-    ps_points_free(p1);
-    ps_points_free(p2);
+    Scope scope;
+    ps_points **p1 = scope.points(), **p2 = scope.points();
+    int rc = ps_points_upload(c, PS_G1, g1, 2, PS_FMT_AFFINE, p1);
+    if (!rc) rc = ps_points_upload(c, PS_G2, g2, 2, PS_FMT_AFFINE, p2);
+    if (!rc) rc = ps_pairing_product_is_one(c, *p1, *p2, 0, equal);
     return rc;
 }
 // every one of k G2 encodings decodes (PS_ERR_ENCODING otherwise); *good = none is the identity and all lie in the subgroup
@@ -131,11 +125,11 @@ static int g2_points_usable(ps_ctx* c, const char* who, const uint8_t* enc, size
     }
     if (identity) return PS_OK;
     if (subgroup) {
-        ps_points* up = nullptr;
+        Scope scope;
+        ps_points** up = scope.points();
         int in = 0;
-        int rc = ps_points_upload(c, PS_G2, enc, k, PS_FMT_AFFINE, &up);
-        if (!rc) rc = ps_points_check_subgroup(c, up, &in);
-        ps_points_free(up);
+        int rc = ps_points_upload(c, PS_G2, enc, k, PS_FMT_AFFINE, up);
+        if (!rc) rc = ps_points_check_subgroup(c, *up, &in);
         if (rc || !in) return rc;
     }
     *good = true;
@@ -197,31 +191,29 @@ static int srs_check_impl(ps_ctx* c, const char* who, const ps_groth16_srs* s, c
     // one ps_msm_multi and so one digit sort (tau_g2, alpha_tau_g1 and beta_tau_g1 of a string cut for a circuit).
     uint8_t lo[4][192], hi[4][192];
     bool summed[4] = {false, false, false, false};
-    ps_scalars* rho = nullptr;
-    if (pairs && (rc = ps_scalars_upload(c, rho_be32, pairs, &rho))) return rc;
-    for (int i = 0; i < 4 && !rc; i++) {
+    Scope scope;
+    ps_scalars** rho = scope.scalars();
+    if (pairs && (rc = ps_scalars_upload(c, rho_be32, pairs, rho))) return rc;
+    for (int i = 0; i < 4; i++) {
         const size_t m = arr[i]->n;
         if (summed[i] || m < 2) continue;  // a lone point has no neighbour to be tested against
         ps_points* views[8] = {};
         uint8_t* outs[8];
         size_t k = 0;
-        for (int j = i; j < 4 && !rc; j++) {
+        for (int j = i; j < 4; j++) {
             if (arr[j]->n != m) continue;
             summed[j] = true;
             outs[k] = lo[j];
             outs[k + 1] = hi[j];
-            rc = ps_points_slice(arr[j], 0, m - 1, &views[k]);
-            if (!rc) rc = ps_points_slice(arr[j], 1, m - 1, &views[k + 1]);
+            ps_points **first = scope.points(), **next = scope.points();
+            if ((rc = ps_points_slice(arr[j], 0, m - 1, first)) || (rc = ps_points_slice(arr[j], 1, m - 1, next))) return rc;
+            views[k] = *first;
+            views[k + 1] = *next;
             k += 2;
         }
-        ps_scalars* w = nullptr;
-        if (!rc) rc = ps_scalars_slice(rho, 0, m - 1, &w);
-        if (!rc) rc = ps_msm_multi(c, views, k, w, outs);
-        ps_scalars_free(w);
-        for (ps_points* v : views) ps_points_free(v);
+        ps_scalars** w = scope.scalars();
+        if ((rc = ps_scalars_slice(*rho, 0, m - 1, w)) || (rc = ps_msm_multi(c, views, k, *w, outs))) return rc;
     }
-    ps_scalars_free(rho);
-    if (rc) return rc;
     // Each equation is a product of its own: two errors cannot cancel.
     int eq = 0;
     //   e(sum rho_i X[i], tau G2) = e(sum rho_i X[i + 1], G2) for X = T1, A, B: X[i + 1] = tau X[i]

@@ -14,25 +14,18 @@ static int column_sums_t(ps_ctx* c, const ps_qap* q, int which, const ps_points*
     const DevCsr& t = q->matT[which];
     const size_t m = q->m, nnz = t.nnz;
     hipStream_t st = c->stream;
-    int rc = points_alloc(c, p->group, m, out);
+    Scope scope(st);
+    int rc = points_alloc(c, p->group, m, scope.result(out));
     if (rc) return rc;
     char* buf = nullptr;  // m XYZZ points, then batch_to_affine's chain products
     u64* mag = nullptr;
     u32* cs = nullptr;
-    auto done = [&](int code) {
-        (void)hipStreamSynchronize(st);
-        for (void* b : {(void*)buf, (void*)mag, (void*)cs})
-            if (b) (void)hipFree(b);
-        if (code) { ps_points_free(*out); *out = nullptr; }
-        return code;
-    };
     const bool wide = q->wide[which] != 0;  // (ec_spmv.hpp: four magnitude words per entry instead of one)
     hipError_t e;
-    if ((e = hipMalloc((void**)&buf, batch_affine_tmp_bytes(m, sizeof(Xyzz<F>)))) != hipSuccess ||
-        (e = hipMalloc((void**)&mag, sizeof(u64) * (wide ? 4 : 1) * std::max<size_t>(nnz, 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&cs, sizeof(u32) * std::max<size_t>(nnz, 1))) != hipSuccess)
-        return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMalloc: ") + hipGetErrorString(e)));
-    if (storage_wait_ready(p->st, st)) return done(fail(PS_ERR_HIP, "ps_qap_column_sums: event wait failed"));
+    if ((e = scope.device(&buf, batch_affine_tmp_bytes(m, sizeof(Xyzz<F>)))) != hipSuccess ||
+        (e = scope.device(&mag, (wide ? 4 : 1) * std::max<size_t>(nnz, 1))) != hipSuccess || (e = scope.device(&cs, nnz)) != hipSuccess)
+        return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMalloc: ") + hipGetErrorString(e));
+    if (storage_wait_ready(p->st, st)) return fail(PS_ERR_HIP, "ps_qap_column_sums: event wait failed");
     const Affine<F>* pts = (const Affine<F>*)points_ptr(p);
     if (!wide) {
         if (nnz) hipLaunchKernelGGL(k_colsum_coef, dim3(nblk(nnz)), dim3(256), 0, st, (const Fr*)t.val, (const u32*)t.col, (u32)nnz, mag, cs);
@@ -50,36 +43,34 @@ static int column_sums_t(ps_ctx* c, const ps_qap* q, int which, const ps_points*
                                (const u32*)t.row_ptr, (const u64*)mag, (const u32*)cs, (u32)nnz, pts, (const u32*)t.long_narrow, (Xyzz<F>*)buf);
         for (size_t k = 0; k < t.long_wide_h.size(); k += 3)  // long rows with one: the identity here, their sum below
             if ((e = hipMemsetAsync(buf + sizeof(Xyzz<F>) * t.long_wide_h[k], 0, sizeof(Xyzz<F>), st)) != hipSuccess)
-                return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemsetAsync: ") + hipGetErrorString(e)));
+                return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemsetAsync: ") + hipGetErrorString(e));
     }
     batch_to_affine<F>(c, buf, m, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
-    if ((e = hipGetLastError()) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: kernels: ") + hipGetErrorString(e)));
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_qap_column_sums: run: ") + hipGetErrorString(e)));
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: kernels: ") + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: run: ") + hipGetErrorString(e));
     // A long row that holds a wide entry is a multi-scalar multiplication, sum_e v_e P[col_e], of thousands of full-width
     // terms (every round constant of a hash multiplies `const`).  k_colsum_long_wide took 1.33 s for the 65 528 wide entries of
     // R's `const` column of a 2^16-gate MiMC circuit, 2 000 x all other work of the three column sums; the library's own sum
     // takes 3.3 ms for it, gather and conversion included (profiles/column_sums_wide.txt).  So: the row's points gathered
     // (k_gather_words), its coefficients as the scalars, ps_msm -- bit-exact on identities, repeated and opposite points.
     if (wide)
-        for (size_t k = 0; k < t.long_wide_h.size() && rc == PS_OK; k += 3) {
+        for (size_t k = 0; k < t.long_wide_h.size(); k += 3) {
             const u32 row = t.long_wide_h[k], first = t.long_wide_h[k + 1], len = t.long_wide_h[k + 2];
             constexpr u32 W = sizeof(Affine<F>) / 4;
-            ps_points* gp = nullptr;
-            ps_scalars* sc = nullptr;
+            Scope row_scope;  // (freed row by row: a circuit may have many such rows)
+            ps_points** gp = row_scope.points();
+            ps_scalars** sc = row_scope.scalars();
             uint8_t wire[192];
-            if ((rc = points_alloc(c, p->group, len, &gp)) == PS_OK) {
-                hipLaunchKernelGGL(k_gather_words, dim3(nblocks((size_t)len * W)), dim3(256), 0, st, (const u32*)pts, (const u32*)t.col + first, len,
-                                   (u64)W, (u64)0, W, (u32*)gp->st->p);
-                if ((rc = scalars_from_mont(c, t.val + first, len, &sc)) == PS_OK) rc = ps_msm(c, gp, sc, wire);
-            }
+            if ((rc = points_alloc(c, p->group, len, gp))) return rc;
+            hipLaunchKernelGGL(k_gather_words, dim3(nblocks((size_t)len * W)), dim3(256), 0, st, (const u32*)pts, (const u32*)t.col + first, len, (u64)W,
+                               (u64)0, W, (u32*)(*gp)->st->p);
+            if ((rc = scalars_from_mont(c, t.val + first, len, sc)) || (rc = ps_msm(c, *gp, *sc, wire))) return rc;
             Affine<F> sum;
-            if (rc == PS_OK && !read_affine(sum, wire)) rc = fail(PS_ERR_HIP, "ps_qap_column_sums: the sum of a long row is no point");
-            if (rc == PS_OK && (e = hipMemcpy((char*)(*out)->st->p + sizeof(Affine<F>) * row, &sum, sizeof sum, hipMemcpyHostToDevice)) != hipSuccess)
-                rc = fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemcpy: ") + hipGetErrorString(e));
-            ps_scalars_free(sc);
-            ps_points_free(gp);
+            if (!read_affine(sum, wire)) return fail(PS_ERR_HIP, "ps_qap_column_sums: the sum of a long row is no point");
+            if ((e = hipMemcpy((char*)(*out)->st->p + sizeof(Affine<F>) * row, &sum, sizeof sum, hipMemcpyHostToDevice)) != hipSuccess)
+                return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemcpy: ") + hipGetErrorString(e));
         }
-    return done(rc);
+    return scope.finish(PS_OK);
 }
 
 extern "C" int ps_qap_column_sums(ps_ctx* c, const ps_qap* q, int which, const ps_points* p, ps_points** out) {
@@ -100,28 +91,22 @@ static int points_scale_uniform_t(ps_ctx* c, const ps_points* pts, const Fr& k_m
     constexpr unsigned LN = FieldTraits<KF>::LANES;
     const size_t n = pts->n;
     hipStream_t st = c->stream;
-    int rc = points_alloc(c, pts->group, n, out);
-    if (rc || n == 0) return rc;
+    Scope scope(st);
+    int rc = points_alloc(c, pts->group, n, scope.result(out));
+    if (rc || n == 0) return scope.finish(rc);
     char* buf = nullptr;
     Fr* km = nullptr;
-    auto done = [&](int code) {
-        (void)hipStreamSynchronize(st);
-        if (buf) (void)hipFree(buf);
-        if (km) (void)hipFree(km);
-        if (code) { ps_points_free(*out); *out = nullptr; }
-        return code;
-    };
     hipError_t e;
-    if ((e = hipMalloc((void**)&buf, batch_affine_tmp_bytes(n, sizeof(Xyzz<F>)))) != hipSuccess || (e = hipMalloc((void**)&km, sizeof(Fr))) != hipSuccess ||
+    if ((e = scope.device(&buf, batch_affine_tmp_bytes(n, sizeof(Xyzz<F>)))) != hipSuccess || (e = scope.device(&km, 1)) != hipSuccess ||
         (e = hipMemcpy(km, &k_mont, sizeof(Fr), hipMemcpyHostToDevice)) != hipSuccess)
-        return done(fail(PS_ERR_HIP, std::string("scaling a point array: ") + hipGetErrorString(e)));
-    if (storage_wait_ready(pts->st, st)) return done(fail(PS_ERR_HIP, "scaling a point array: event wait failed"));
+        return fail(PS_ERR_HIP, std::string("scaling a point array: ") + hipGetErrorString(e));
+    if (storage_wait_ready(pts->st, st)) return fail(PS_ERR_HIP, "scaling a point array: event wait failed");
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, (Xyzz<F>*)buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (Xyzz<F>*)buf, (u32)n, (const Fr*)km, 0ull);
     batch_to_affine<F>(c, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
-    if ((e = hipGetLastError()) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("scaling a point array: kernels: ") + hipGetErrorString(e)));
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("scaling a point array: run: ") + hipGetErrorString(e)));
-    return done(PS_OK);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("scaling a point array: kernels: ") + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("scaling a point array: run: ") + hipGetErrorString(e));
+    return scope.finish(PS_OK);
 }
 static int points_scale_uniform(ps_ctx* c, const ps_points* pts, const Fr& k_mont, ps_points** out) {
     return pts->group == PS_G1 ? points_scale_uniform_t<Fp>(c, pts, k_mont, out) : points_scale_uniform_t<Fp2>(c, pts, k_mont, out);
@@ -141,36 +126,38 @@ static int srs_xi_t(ps_ctx* c, const ps_qap* q, const ps_points* tau, ps_points*
     NttTables& tb = *ctx_tabs(c);
     hipError_t e = ntt_tables_ensure(tb, p, st);
     if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: twiddles: ") + hipGetErrorString(e));
-    int rc = points_alloc(c, PS_G1, cnt, out);
+    Scope scope(st);
+    int rc = points_alloc(c, PS_G1, cnt, scope.result(out));
     if (rc) return rc;
     Xyzz<F>* A = nullptr;  // S points; the chain products of the batch normalisation go behind the first cnt < S / 2
     Fr* t1 = nullptr;
-    auto done = [&](int code) {
-        (void)hipStreamSynchronize(st);
-        if (A) (void)hipFree(A);
-        if (t1) (void)hipFree(t1);
-        if (code) { ps_points_free(*out); *out = nullptr; }
-        return code;
-    };
-    if ((e = hipMalloc((void**)&A, sizeof(Xyzz<F>) * S)) != hipSuccess || (e = hipMalloc((void**)&t1, sizeof(Fr) * S)) != hipSuccess)
-        return done(fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: hipMalloc: ") + hipGetErrorString(e)));
-    if (storage_wait_ready(tau->st, st)) return done(fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: event wait failed"));
+    if ((e = scope.device(&A, S)) != hipSuccess || (e = scope.device(&t1, S)) != hipSuccess)
+        return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: hipMalloc: ") + hipGetErrorString(e));
+    if (storage_wait_ready(tau->st, st)) return fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: event wait failed");
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(tau), (u32)len, S, A);
     hipLaunchKernelGGL(k_fr_rev_pad, dim3(nblk(S)), dim3(256), 0, st, t1, (const Fr*)q->qt.z, (u64)(n + 1), p);
-    if ((e = ntt_run<false>(tb, st, t1, S, p)) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: ntt: ") + hipGetErrorString(e)));
+    if ((e = ntt_run<false>(tb, st, t1, S, p)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: ntt: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(k_fr_scale, dim3(nblk(S)), dim3(256), 0, st, t1, (const Fr*)t1, fr_inv2pow_host(p), (u64)S);
     ec_ntt<F, false>(tb, st, A, S, p);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, A, S, (const Fr*)t1, ~0ull);
     ec_ntt<F, true>(tb, st, A, S, p);
     batch_to_affine<F>(c, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
-    if ((e = hipGetLastError()) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: kernels: ") + hipGetErrorString(e)));
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: run: ") + hipGetErrorString(e)));
-    return done(PS_OK);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: kernels: ") + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: run: ") + hipGetErrorString(e));
+    return scope.finish(PS_OK);
 }
 
 static void crs_release(ps_groth16_crs* k) {
     for (ps_points* p : {k->xi, k->xi2, k->io_lp, k->nio_lp, k->xi_t, k->lxi, k->lxi2, k->lxi_t}) ps_points_free(p);
     memset(k, 0, sizeof *k);
+}
+// a key that is complete or empty: an error releases what `out` holds by then and keeps its text
+static int crs_or_nothing(int rc, ps_groth16_crs* out) {
+    if (rc) {
+        KeepError keep;
+        crs_release(out);
+    }
+    return rc;
 }
 template <class F>
 static void generator_bytes(uint8_t* out) {
@@ -183,11 +170,50 @@ static int points_copy(ps_ctx* c, const ps_points* p, size_t first, size_t n, ps
     return points_concat(c, p->group, {{(const char*)points_ptr(p) + first * point_bytes(p->group), n}}, out);
 }
 
+// The key's arrays into a zeroed `out`, arguments validated; on an error `out` is left as far as it got (crs_or_nothing).
+static int setup_from_srs_run(ps_ctx* c, const ps_qap* q, const ps_groth16_srs* srs, ps_groth16_crs* out) {
+    const size_t n = q->n, m = q->m, diff = q->m - q->nio;
+    Scope scope(c->stream);
+    ps_points **la = scope.points(), **lb = scope.points(), **sums[3] = {scope.points(), scope.points(), scope.points()}, **lin = scope.points();
+    scope.in_flight();  // the temporaries are freed with the stream idle, on an error too
+    int rc;
+    // Alpha, Beta: the first points of the scaled arrays; Beta2 as given; Delta, Delta2, Gamma: the generators   (groth16.go:67-76)
+    if ((rc = ps_points_download(c, srs->alpha_tau_g1, 0, 1, out->alpha))) return rc;
+    if ((rc = ps_points_download(c, srs->beta_tau_g1, 0, 1, out->beta))) return rc;
+    memcpy(out->beta2, srs->beta_g2, 192);
+    generator_bytes<Fp>(out->delta);
+    generator_bytes<Fp2>(out->delta2);
+    generator_bytes<Fp2>(out->gamma);
+    // Xi, Xi2: the first n powers, and their Lagrange forms                                                    (groth16.go:79-80)
+    if ((rc = points_copy(c, srs->tau_g1, 0, n, &out->xi))) return rc;
+    if ((rc = points_copy(c, srs->tau_g2, 0, n, &out->xi2))) return rc;
+    if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi, 0, &out->lxi))) return rc;
+    if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi2, 0, &out->lxi2))) return rc;
+    // IoLP | NioLP = {(beta u_i(x) + alpha v_i(x) + w_i(x)) G1}: L over {beta l_j(x) G1}, R over {alpha l_j(x) G1}, O over
+    // {l_j(x) G1}                                                                                       (groth16.go:86-91, 254-264)
+    if ((rc = ps_points_monomial_to_lagrange(c, q, srs->beta_tau_g1, 0, lb))) return rc;
+    if ((rc = ps_points_monomial_to_lagrange(c, q, srs->alpha_tau_g1, 0, la))) return rc;
+    if ((rc = ps_qap_column_sums(c, q, 0, *lb, sums[0]))) return rc;
+    if ((rc = ps_qap_column_sums(c, q, 1, *la, sums[1]))) return rc;
+    if ((rc = ps_qap_column_sums(c, q, 2, out->lxi, sums[2]))) return rc;
+    if ((rc = points_alloc(c, PS_G1, m, lin))) return rc;
+    hipLaunchKernelGGL(k_points_add3<Fp>, dim3(nblocks(m)), dim3(256), 0, c->stream, (const Affine<Fp>*)points_ptr(*sums[0]),
+                       (const Affine<Fp>*)points_ptr(*sums[1]), (const Affine<Fp>*)points_ptr(*sums[2]), (u32)m, (Affine<Fp>*)(*lin)->st->p);
+    if (hipGetLastError() != hipSuccess) return fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: the sum of the three column sums failed to launch");
+    if ((rc = points_copy(c, *lin, 0, diff, &out->io_lp))) return rc;
+    if ((rc = points_copy(c, *lin, diff, m - diff, &out->nio_lp))) return rc;
+    // XiT = {x^i t(x) G1}, i < n - 1, and its Lagrange form on the nodes n+1..2n-1                              (groth16.go:94-97)
+    if ((rc = srs_xi_t(c, q, srs->tau_g1, &out->xi_t))) return rc;
+    if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi_t, 1, &out->lxi_t))) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: the device reported an error");
+    return PS_OK;
+}
+
 extern "C" int ps_groth16_setup_from_srs(ps_ctx* c, const ps_qap* q, const ps_groth16_srs* srs, ps_groth16_crs* out) {
     if (!c || !q || !srs || !out || !srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1)
         return fail(PS_ERR_ARG, "ps_groth16_setup_from_srs: NULL argument");
     memset(out, 0, sizeof *out);
-    const size_t n = q->n, m = q->m, diff = q->m - q->nio;
+    const size_t n = q->n;
     if (n < 2) return fail(PS_ERR_ARG, "ps_groth16_setup_from_srs: needs at least 2 gates");
     if (srs->tau_g1->group != PS_G1 || srs->tau_g2->group != PS_G2 || srs->alpha_tau_g1->group != PS_G1 || srs->beta_tau_g1->group != PS_G1)
         return fail(PS_ERR_ARG, "ps_groth16_setup_from_srs: tau_g2 is a G2 array, the other three are G1 arrays");
@@ -203,82 +229,38 @@ extern "C" int ps_groth16_setup_from_srs(ps_ctx* c, const ps_qap* q, const ps_gr
         if (!read_affine(b2, srs->beta_g2)) return fail(PS_ERR_ENCODING, "ps_groth16_setup_from_srs: beta_g2 is not a canonical point on the curve");
     }
     HIP_TRY(hipSetDevice(c->device));
-    ps_points *la = nullptr, *lb = nullptr, *sums[3] = {nullptr, nullptr, nullptr}, *lin = nullptr;
-    int rc = PS_OK;
-    do {
-        // Alpha, Beta: the first points of the scaled arrays; Beta2 as given; Delta, Delta2, Gamma: the generators   (groth16.go:67-76)
-        if ((rc = ps_points_download(c, srs->alpha_tau_g1, 0, 1, out->alpha))) break;
-        if ((rc = ps_points_download(c, srs->beta_tau_g1, 0, 1, out->beta))) break;
-        memcpy(out->beta2, srs->beta_g2, 192);
-        generator_bytes<Fp>(out->delta);
-        generator_bytes<Fp2>(out->delta2);
-        generator_bytes<Fp2>(out->gamma);
-        // Xi, Xi2: the first n powers, and their Lagrange forms                                                    (groth16.go:79-80)
-        if ((rc = points_copy(c, srs->tau_g1, 0, n, &out->xi))) break;
-        if ((rc = points_copy(c, srs->tau_g2, 0, n, &out->xi2))) break;
-        if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi, 0, &out->lxi))) break;
-        if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi2, 0, &out->lxi2))) break;
-        // IoLP | NioLP = {(beta u_i(x) + alpha v_i(x) + w_i(x)) G1}: L over {beta l_j(x) G1}, R over {alpha l_j(x) G1}, O over
-        // {l_j(x) G1}                                                                                       (groth16.go:86-91, 254-264)
-        if ((rc = ps_points_monomial_to_lagrange(c, q, srs->beta_tau_g1, 0, &lb))) break;
-        if ((rc = ps_points_monomial_to_lagrange(c, q, srs->alpha_tau_g1, 0, &la))) break;
-        if ((rc = ps_qap_column_sums(c, q, 0, lb, &sums[0]))) break;
-        if ((rc = ps_qap_column_sums(c, q, 1, la, &sums[1]))) break;
-        if ((rc = ps_qap_column_sums(c, q, 2, out->lxi, &sums[2]))) break;
-        if ((rc = points_alloc(c, PS_G1, m, &lin))) break;
-        hipLaunchKernelGGL(k_points_add3<Fp>, dim3(nblocks(m)), dim3(256), 0, c->stream, (const Affine<Fp>*)points_ptr(sums[0]),
-                           (const Affine<Fp>*)points_ptr(sums[1]), (const Affine<Fp>*)points_ptr(sums[2]), (u32)m, (Affine<Fp>*)lin->st->p);
-        if (hipGetLastError() != hipSuccess) { rc = fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: the sum of the three column sums failed to launch"); break; }
-        if ((rc = points_copy(c, lin, 0, diff, &out->io_lp))) break;
-        if ((rc = points_copy(c, lin, diff, m - diff, &out->nio_lp))) break;
-        // XiT = {x^i t(x) G1}, i < n - 1, and its Lagrange form on the nodes n+1..2n-1                              (groth16.go:94-97)
-        if ((rc = srs_xi_t(c, q, srs->tau_g1, &out->xi_t))) break;
-        if ((rc = ps_points_monomial_to_lagrange(c, q, out->xi_t, 1, &out->lxi_t))) break;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PS_ERR_HIP, "ps_groth16_setup_from_srs: the device reported an error");
-    } while (0);
-    (void)hipStreamSynchronize(c->stream);
-    for (ps_points* p : {la, lb, sums[0], sums[1], sums[2], lin}) ps_points_free(p);
-    if (rc) {
-        std::string keep = g_last_error;
-        crs_release(out);
-        g_last_error = keep;
-    }
-    return rc;
+    return crs_or_nothing(setup_from_srs_run(c, q, srs, out), out);
 }
 
+static int crs_contribute_run(ps_ctx* c, const ps_groth16_crs* in, const uint8_t* d_be32, const uint8_t* g_be32, const Fr& dinv, const Fr& ginv,
+                              ps_groth16_crs* out) {
+    int rc;
+    memcpy(out->alpha, in->alpha, 96);
+    memcpy(out->beta, in->beta, 96);
+    memcpy(out->beta2, in->beta2, 192);
+    if ((rc = ps_points_lincomb(PS_G1, in->delta, d_be32, 1, out->delta))) return rc;
+    if ((rc = ps_points_lincomb(PS_G2, in->delta2, d_be32, 1, out->delta2))) return rc;
+    if ((rc = ps_points_lincomb(PS_G2, in->gamma, g_be32, 1, out->gamma))) return rc;
+    // NioLP, XiT (and its Lagrange form) carry 1 / delta, IoLP carries 1 / gamma   (groth16.go:86-97)
+    if ((rc = points_scale_uniform(c, in->nio_lp, dinv, &out->nio_lp))) return rc;
+    if ((rc = points_scale_uniform(c, in->xi_t, dinv, &out->xi_t))) return rc;
+    if (in->lxi_t && (rc = points_scale_uniform(c, in->lxi_t, dinv, &out->lxi_t))) return rc;
+    if ((rc = points_scale_uniform(c, in->io_lp, ginv, &out->io_lp))) return rc;
+    // the arrays no share touches: views of the input's storage
+    if ((rc = ps_points_slice(in->xi, 0, in->xi->n, &out->xi))) return rc;
+    if ((rc = ps_points_slice(in->xi2, 0, in->xi2->n, &out->xi2))) return rc;
+    if (in->lxi && (rc = ps_points_slice(in->lxi, 0, in->lxi->n, &out->lxi))) return rc;
+    if (in->lxi2 && (rc = ps_points_slice(in->lxi2, 0, in->lxi2->n, &out->lxi2))) return rc;
+    return PS_OK;
+}
 extern "C" int ps_groth16_crs_contribute(ps_ctx* c, const ps_groth16_crs* in, const uint8_t* d_be32, const uint8_t* g_be32, ps_groth16_crs* out) {
     if (!c || !in || !d_be32 || !g_be32 || !out || in == out) return fail(PS_ERR_ARG, "ps_groth16_crs_contribute: NULL argument (or out == in)");
     if (!in->xi || !in->xi2 || !in->io_lp || !in->nio_lp || !in->xi_t) return fail(PS_ERR_ARG, "ps_groth16_crs_contribute: the key lacks an array");
     memset(out, 0, sizeof *out);
     const Fr d = fr_mont_from_be32(d_be32), g = fr_mont_from_be32(g_be32);
     if (fr_is_zero(d) || fr_is_zero(g)) return fail(PS_ERR_ARG, "ps_groth16_crs_contribute: the shares d and g must be non-zero");
-    const Fr dinv = fr_inv(d), ginv = fr_inv(g);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = PS_OK;
-    do {
-        memcpy(out->alpha, in->alpha, 96);
-        memcpy(out->beta, in->beta, 96);
-        memcpy(out->beta2, in->beta2, 192);
-        if ((rc = ps_points_lincomb(PS_G1, in->delta, d_be32, 1, out->delta))) break;
-        if ((rc = ps_points_lincomb(PS_G2, in->delta2, d_be32, 1, out->delta2))) break;
-        if ((rc = ps_points_lincomb(PS_G2, in->gamma, g_be32, 1, out->gamma))) break;
-        // NioLP, XiT (and its Lagrange form) carry 1 / delta, IoLP carries 1 / gamma   (groth16.go:86-97)
-        if ((rc = points_scale_uniform(c, in->nio_lp, dinv, &out->nio_lp))) break;
-        if ((rc = points_scale_uniform(c, in->xi_t, dinv, &out->xi_t))) break;
-        if (in->lxi_t && (rc = points_scale_uniform(c, in->lxi_t, dinv, &out->lxi_t))) break;
-        if ((rc = points_scale_uniform(c, in->io_lp, ginv, &out->io_lp))) break;
-        // the arrays no share touches: views of the input's storage
-        if ((rc = ps_points_slice(in->xi, 0, in->xi->n, &out->xi))) break;
-        if ((rc = ps_points_slice(in->xi2, 0, in->xi2->n, &out->xi2))) break;
-        if (in->lxi && (rc = ps_points_slice(in->lxi, 0, in->lxi->n, &out->lxi))) break;
-        if (in->lxi2 && (rc = ps_points_slice(in->lxi2, 0, in->lxi2->n, &out->lxi2))) break;
-    } while (0);
-    if (rc) {
-        std::string keep = g_last_error;
-        crs_release(out);
-        g_last_error = keep;
-    }
-    return rc;
+    return crs_or_nothing(crs_contribute_run(c, in, d_be32, g_be32, fr_inv(d), fr_inv(g), out), out);
 }
 
 // -P for an affine encoding that has been validated
@@ -293,12 +275,11 @@ static int pairing_pair_equal(ps_ctx* c, const uint8_t* a1, const uint8_t* b1, c
     g1_negated(g1 + 96, a2);
     memcpy(g2, b1, 192);
     memcpy(g2 + 192, b2, 192);
-    ps_points *p1 = nullptr, *p2 = nullptr;
-    int rc = ps_points_upload(c, PS_G1, g1, 2, PS_FMT_AFFINE, &p1);
-    if (!rc) rc = ps_points_upload(c, PS_G2, g2, 2, PS_FMT_AFFINE, &p2);
-    if (!rc) rc = ps_pairing_product_is_one(c, p1, p2, 1, equal);
-    ps_points_free(p1);
-    ps_points_free(p2);
+    Scope scope;
+    ps_points **p1 = scope.points(), **p2 = scope.points();
+    int rc = ps_points_upload(c, PS_G1, g1, 2, PS_FMT_AFFINE, p1);
+    if (!rc) rc = ps_points_upload(c, PS_G2, g2, 2, PS_FMT_AFFINE, p2);
+    if (!rc) rc = ps_pairing_product_is_one(c, *p1, *p2, 1, equal);
     return rc;
 }
 static bool points_same_view(const ps_points* a, const ps_points* b) { return a->st == b->st && a->first == b->first && a->n == b->n && a->group == b->group; }
@@ -361,20 +342,17 @@ extern "C" int ps_groth16_crs_check_update(ps_ctx* c, const ps_groth16_crs* befo
     if (rc) return rc;
     if (!eq) return PS_OK;
     // e(sum rho_i N'_i, delta2') == e(sum rho_i N_i, delta2), and likewise IoLP against gamma: one random linear combination per array
-    ps_scalars* rho = nullptr;
-    if (longest && (rc = ps_scalars_upload(c, rho_be32, longest, &rho))) return rc;
+    Scope scope;
+    ps_scalars** rho = scope.scalars();
+    if (longest && (rc = ps_scalars_upload(c, rho_be32, longest, rho))) return rc;
     for (const Scaled& s : scaled) {
         if (!s.was || !s.was->n) continue;
-        ps_scalars* view = nullptr;
+        ps_scalars** view = scope.scalars();
         uint8_t was_sum[96], is_sum[96];
-        rc = ps_scalars_slice(rho, 0, s.was->n, &view);
-        if (!rc) rc = ps_msm(c, s.was, view, was_sum);
-        if (!rc) rc = ps_msm(c, s.is, view, is_sum);
-        ps_scalars_free(view);
-        if (!rc) rc = pairing_pair_equal(c, is_sum, s.is2, was_sum, s.was2, &eq);
-        if (rc || !eq) { ps_scalars_free(rho); return rc; }
+        if ((rc = ps_scalars_slice(*rho, 0, s.was->n, view)) || (rc = ps_msm(c, s.was, *view, was_sum)) || (rc = ps_msm(c, s.is, *view, is_sum)) ||
+            (rc = pairing_pair_equal(c, is_sum, s.is2, was_sum, s.was2, &eq)) || !eq)
+            return rc;
     }
-    ps_scalars_free(rho);
     *ok = 1;
     return PS_OK;
 }

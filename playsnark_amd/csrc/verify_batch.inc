@@ -120,17 +120,14 @@ static int points_scale_g1(ps_ctx* c, const ps_points* pts, const Fr* k_mont, ps
     const size_t n = pts->n;
     int rc = c->vb_xyzz.ensure(batch_affine_tmp_bytes(n, sizeof(Xyzz<Fp>)));
     if (rc) return rc;
-    if ((rc = points_alloc(c, PS_G1, n, out))) return rc;
+    Scope scope;
+    if ((rc = points_alloc(c, PS_G1, n, scope.result(out)))) return rc;
     Xyzz<Fp>* buf = (Xyzz<Fp>*)c->vb_xyzz.p;
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, c->stream, (const Affine<Fp>*)points_ptr(pts), (u32)n, (u32)n, buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, c->stream, buf, (u32)n, k_mont, ~0ull);
     batch_to_affine<Fp>(c, (char*)buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<Fp>));
-    if (hipGetLastError() != hipSuccess) {
-        ps_points_free(*out);
-        *out = nullptr;
-        return fail(PS_ERR_HIP, "ps_groth16_verify_batch: scaling kernels failed to launch");
-    }
-    return PS_OK;
+    if (hipGetLastError() != hipSuccess) return fail(PS_ERR_HIP, "ps_groth16_verify_batch: scaling kernels failed to launch");
+    return scope.finish(PS_OK);
 }
 
 // t_j = sum_i w_i m_ij over a rows x cols matrix of plain scalars on the device; the result is row 0 of *res
@@ -240,66 +237,60 @@ static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, con
     const size_t wbs[3] = {96, 192, 96}, offs[3] = {0, 96, 288};
     const int groups[3] = {PS_G1, PS_G2, PS_G1};
     const char* names[3] = {"A", "B", "C"};
-    ps_points* arr[3] = {nullptr, nullptr, nullptr};
-    ps_points* ra = nullptr;
-    ps_scalars *rho = nullptr, *t = nullptr;
-    auto done = [&](int code) {
-        for (ps_points* p : arr) if (p) ps_points_free(p);
-        if (ra) ps_points_free(ra);
-        if (rho) ps_scalars_free(rho);
-        if (t) ps_scalars_free(t);
-        return code;
-    };
+    Scope scope;
+    ps_points** arr[3] = {scope.points(), scope.points(), scope.points()};
+    ps_points** ra = scope.points();
+    ps_scalars **rho = scope.scalars(), **t = scope.scalars();
     for (int k = 0; k < 3; k++) {
         raw[k].resize(wbs[k] * N);
         for (size_t i = 0; i < N; i++) memcpy(raw[k].data() + wbs[k] * i, proofs + 384 * i + offs[k], wbs[k]);
-        rc = ps_points_upload(c, groups[k], raw[k].data(), N, PS_FMT_AFFINE, &arr[k]);
+        rc = ps_points_upload(c, groups[k], raw[k].data(), N, PS_FMT_AFFINE, arr[k]);
         if (rc == PS_ERR_ENCODING) {
             const size_t bad = groups[k] == PS_G1 ? first_bad_encoding<Fp>(raw[k], N, 96) : first_bad_encoding<Fp2>(raw[k], N, 192);
-            return done(fail(PS_ERR_ENCODING, fn + ": " + names[k] + " of proof " + std::to_string(bad) +
-                                                  " is not a canonical point on the curve"));
+            return fail(PS_ERR_ENCODING, fn + ": " + names[k] + " of proof " + std::to_string(bad) +
+                                                  " is not a canonical point on the curve");
         }
-        if (rc) return done(rc);
+        if (rc) return rc;
     }
     for (int k = 0; k < 3; k++) {
         int in = 0;
-        if ((rc = ps_points_check_subgroup(c, arr[k], &in))) return done(rc);
-        if (!in) return done(fail(PS_ERR_ENCODING, fn + ": a proof's " + names[k] + " is outside the order-r subgroup"));
+        if ((rc = ps_points_check_subgroup(c, *arr[k], &in))) return rc;
+        if (!in) return fail(PS_ERR_ENCODING, fn + ": a proof's " + names[k] + " is outside the order-r subgroup");
     }
     clk.mark(0);
     // rho on the device: plain words for the sum over C, Montgomery form for the scaling of A and the column sums
-    if ((rc = ps_scalars_upload(c, rho_be32, N, &rho))) return done(rc);
-    if ((rc = c->vb_rho.ensure(sizeof(Fr) * N))) return done(rc);
+    if ((rc = ps_scalars_upload(c, rho_be32, N, rho))) return rc;
+    if ((rc = c->vb_rho.ensure(sizeof(Fr) * N))) return rc;
     Fr* rho_m = (Fr*)c->vb_rho.p;
-    hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(N)), dim3(256), 0, c->stream, rho_m, scalars_ptr(rho), (u64)N);
+    hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(N)), dim3(256), 0, c->stream, rho_m, scalars_ptr(*rho), (u64)N);
     // the device's share: prod_i miller(rho_i A_i, B_i)
-    if ((rc = points_scale_g1(c, arr[0], rho_m, &ra))) return done(rc);
+    if ((rc = points_scale_g1(c, *arr[0], rho_m, ra))) return rc;
     clk.mark(1);
     const pairing_dev::Fp12* fdev = nullptr;
-    rc = keep ? locate_miller_levels(c, (const Affine<Fp>*)points_ptr(ra), (const Affine<Fp2>*)points_ptr(arr[1]), N, &fdev, &clk)
-              : miller_product_launch(c, (const Affine<Fp>*)points_ptr(ra), (const Affine<Fp2>*)points_ptr(arr[1]), N, &fdev, &clk);
-    if (rc) return done(rc);
+    rc = keep ? locate_miller_levels(c, (const Affine<Fp>*)points_ptr(*ra), (const Affine<Fp2>*)points_ptr(*arr[1]), N, &fdev, &clk)
+              : miller_product_launch(c, (const Affine<Fp>*)points_ptr(*ra), (const Affine<Fp2>*)points_ptr(*arr[1]), N, &fdev, &clk);
+    if (rc) return rc;
     // (the loops are only enqueued: the column sums and the two sums below queue up behind them while they run, and the
     // product is fetched after the sums)
     // X = sum_j (sum_i rho_i io_ij) IoLP_j and sum_i rho_i C_i: two sums instead of N
     uint8_t xb[96], cb[96];
     if (diff) {
-        if (storage_wait_ready(io->st, c->stream)) return done(fail(PS_ERR_HIP, fn + ": event wait failed"));
+        if (storage_wait_ready(io->st, c->stream)) return fail(PS_ERR_HIP, fn + ": event wait failed");
         const u32* tw = nullptr;
-        if ((rc = weighted_columns(c, rho_m, scalars_ptr(io), N, diff, &tw))) return done(rc);
-        if ((rc = scalars_alloc(c, diff, &t))) return done(rc);
-        if (hipMemcpyAsync(t->st->p, tw, 32 * diff, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || storage_mark_ready(t->st, c->stream))
-            return done(fail(PS_ERR_HIP, fn + ": copy of the column sums failed"));
-        if ((rc = ps_msm(c, vk->io_lp, t, xb))) return done(rc);
+        if ((rc = weighted_columns(c, rho_m, scalars_ptr(io), N, diff, &tw))) return rc;
+        if ((rc = scalars_alloc(c, diff, t))) return rc;
+        if (hipMemcpyAsync((*t)->st->p, tw, 32 * diff, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || storage_mark_ready((*t)->st, c->stream))
+            return fail(PS_ERR_HIP, fn + ": copy of the column sums failed");
+        if ((rc = ps_msm(c, vk->io_lp, *t, xb))) return rc;
     } else {
         write_identity(PS_G1, xb);
     }
-    if ((rc = ps_msm(c, arr[2], rho, cb))) return done(rc);
+    if ((rc = ps_msm(c, *arr[2], *rho, cb))) return rc;
     clk.mark(4);
     pairing::Fp12 f;
-    if ((rc = miller_product_fetch(c, fdev, &f))) return done(rc);
+    if ((rc = miller_product_fetch(c, fdev, &f))) return rc;
     Affine<Fp> x, sc;
-    if (!read_g1(x, xb) || !read_g1(sc, cb)) return done(fail(PS_ERR_ENCODING, fn + ": bad point from a sum"));
+    if (!read_g1(x, xb) || !read_g1(sc, cb)) return fail(PS_ERR_ENCODING, fn + ": bad point from a sum");
     // the host's share: (-(sum rho) alpha, beta2), (-X, gamma), (-sum rho_i C_i, delta2), one final exponentiation
     typedef Affine<Fq> H1;
     H1 sa;
@@ -320,14 +311,14 @@ static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, con
     *ok = pairing::f12_eq(pairing::final_exp(f), pairing::f12_one()) ? 1 : 0;
     clk.mark(5);
     if (keep && !*ok) {
-        keep->c_pts = arr[2];
-        keep->rho = rho;
-        arr[2] = nullptr;
-        rho = nullptr;
+        keep->c_pts = *arr[2];  // out of the scope's slots: the holder's from here on
+        keep->rho = *rho;
+        *arr[2] = nullptr;
+        *rho = nullptr;
         keep->alpha = affine_to_host<Fp>(alpha);
         for (int k = 0; k < 3; k++) keep->g2[k] = tail[k].second;
     }
-    return done(PS_OK);
+    return PS_OK;
 }
 
 extern "C" int ps_groth16_verify_batch(ps_ctx* c, const ps_groth16_vk* vk, const ps_scalars* io, const uint8_t* proofs, size_t nproofs,

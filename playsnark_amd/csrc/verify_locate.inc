@@ -227,6 +227,9 @@ extern "C" int ps_groth16_verify_batch_locate(ps_ctx* c, const ps_groth16_vk* vk
     int ok = 0;
     VbKeep keep;
     int rc = verify_batch_impl(c, "ps_groth16_verify_batch_locate", PS_VERIFY_LOCATE_MAX, "2^20", vk, io, proofs, nproofs, rho_be32, &ok, &keep);
+    Scope scope;  // what a rejected batch handed over is this call's from here on
+    *scope.points() = keep.c_pts;
+    *scope.scalars() = keep.rho;
     if (rc || nproofs == 0) return rc;
     c->lc_info.checks = 1;
     if (ok) {
@@ -234,8 +237,6 @@ extern "C" int ps_groth16_verify_batch_locate(ps_ctx* c, const ps_groth16_vk* vk
         return PS_OK;
     }
     rc = locate_descent(c, vk, io, nproofs, keep, valid, ninvalid);
-    if (keep.c_pts) ps_points_free(keep.c_pts);
-    if (keep.rho) ps_scalars_free(keep.rho);
     if (rc) *ninvalid = 0;
     return rc;
 }
