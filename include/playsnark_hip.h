@@ -208,8 +208,19 @@ int ps_msm_set_slice(ps_ctx* ctx, int entries /* sorted entries per accumulation
  * take shallow trees of lane-cooperative point additions, long ones the work-efficient chains), 1 = chains, 2 = trees.
  * Same group element, same bytes, either way (A/B runs and tests). */
 int ps_msm_set_tail(ps_ctx* ctx, int mode);
+/* The point pass of a sum: 1 = fixed slices of the sorted entry list (cut buckets are mended by the fix-up kernels),
+ * 2 = whole buckets, one lane each, taken in order of size (no partial sums, no fix-up; correct for every input, slow when
+ * a few buckets hold most of the entries), 0 = automatic: slices, unless the sum is long, its scalars are wider than an
+ * int64 witness's, it has at least 2^18 buckets of at most 64 entries on average AND the sort finds them evenly filled -- that
+ * last part is decided on the device, without a host wait, and ps_msm_last_accumulate reports what the sum finished last
+ * took (1 or 2; 0 before the first sum).
+ * ps_msm_batch always takes slices.  Same group element, same bytes, either way.  Added within revision 5 (found by
+ * symbol, no existing struct changed). */
+int ps_msm_set_accumulate(ps_ctx* ctx, int mode);
+int ps_msm_last_accumulate(ps_ctx* ctx, int* path);
 /* Per-stage device time of the sum finished last, measured with HIP events on the streams its kernels
- * run on.  Stages: 0 digits (+counter memset), 1 scan, 2 scatter, 3 queue (bucket memset, and with
+ * run on.  Stages: 0 digits (+counter memset), 1 scan, 2 scatter (+ the buckets' order by size where whole buckets are
+ * considered, ps_msm_set_accumulate), 3 queue (bucket memset, and with
  * several sums in flight the wait for the previous sum's accumulation), 4 accumulate (the dominant
  * kernel, bracketed tightly), 5 fix-up, 6 bucket reduction. */
 /* Measured issue rate of v_mad_u64_u32 (lane-operations per second, two waves per SIMD on every CU; ~1 ms): the

@@ -36,6 +36,7 @@ SYMBOLS = [
     "ps_points_lagrange_check", "ps_groth16_crs_check_from_srs",
     "ps_qap_create_fr", "ps_qap_wide_entries",
     "ps_msm_batch", "ps_msm_batch_set_chunk", "ps_groth16_prove_batch",
+    "ps_msm_set_accumulate", "ps_msm_last_accumulate",
 ]
 
 
@@ -182,6 +183,9 @@ def _load():
     lib.ps_ctx_set_timing.argtypes = [vp, i]
     lib.ps_msm_set_slice.argtypes = [vp, i]
     lib.ps_msm_set_tail.argtypes = [vp, i]
+    if hasattr(lib, "ps_msm_set_accumulate"):  # found by symbol: an older build named by PLAYSNARK_HIP_LIB (A/B runs) loads without the knob
+        lib.ps_msm_set_accumulate.argtypes = [vp, i]
+        lib.ps_msm_last_accumulate.argtypes = [vp, C.POINTER(C.c_int)]
     lib.ps_microbench_mad.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ps_ctx_set_table_budget.argtypes = [vp, C.c_longlong]
     lib.ps_qap_is_valid.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

@@ -100,6 +100,16 @@ class Context:
         """0 automatic, 1 chains (the long sums' tail), 2 trees of lane-cooperative additions (the short sums' tail)."""
         _check(lib.ps_msm_set_tail(self._h, mode))
 
+    def set_accumulate(self, mode: int):
+        """The point pass: 0 automatic, 1 fixed slices, 2 whole buckets in order of size (ps_msm_set_accumulate)."""
+        _check(lib.ps_msm_set_accumulate(self._h, mode))
+
+    def last_accumulate_path(self) -> int:
+        """The point pass the sum finished last took: 1 slices, 2 whole buckets (0: no sum yet)."""
+        path = C.c_int(0)
+        _check(lib.ps_msm_last_accumulate(self._h, C.byref(path)))
+        return path.value
+
     STAGES = ("digits", "scan", "scatter", "queue", "accumulate", "fixup", "reduce")
 
     def set_timing(self, enable: bool):

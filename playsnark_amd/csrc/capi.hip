@@ -94,6 +94,7 @@ struct ps_ctx {
     bool tail_used = false;
     // MSM workspace
     DevBuf counts, offs, bsum, keys, ranks, vals, sorted, buckets, parts, segs, wins, heavy, hparts, coarse;
+    DevBuf perm, border;  // buckets in order of size (beside offs, made by the sort) and [class histogram][class cursors][verdict, largest class, non-empty buckets] (bucket_order.hpp)
     DevBuf mb_fold, mb_out;  // ps_msm_batch: the members' folded sums (XYZZ + the chain products of k_batch_to_affine), then affine + wire bytes
     int batch_chunk = 0;     // ps_msm_batch_set_chunk: members per pass, 0 = automatic
     hipEvent_t mb_ev[2] = {nullptr, nullptr};  // timed contexts: around the fold, the normalisation and the encoding of a batch's last pass
@@ -147,6 +148,8 @@ struct ps_ctx {
     int forced_c = 0;
     int forced_slice = 0;
     int forced_tail = 0;             // ps_msm_set_tail: 0 automatic, 1 chains, 2 trees of lane-cooperative additions
+    int forced_acc = 0;              // ps_msm_set_accumulate: 0 automatic, 1 slices, 2 whole buckets in order of size
+    int last_acc = 0;                // ps_msm_last_accumulate: the point pass of the sum finished last (0: none yet)
     QuotientCache* qcache = nullptr;
     // Groth16 fused driver: secondary context (own stream + workspace) for the concurrent G2 MSM,
     // and the concatenated CRS arrays of the last proving key
@@ -304,7 +307,7 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->tail) (void)hipStreamSynchronize(c->tail);
     for (DevBuf* b : {&c->counts, &c->offs, &c->bsum, &c->keys, &c->ranks, &c->sorted, &c->buckets, &c->parts,
-                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->staging, &c->affine_tmp, &c->mb_fold, &c->mb_out, &c->pb_x, &c->pb_y, &c->pb_small, &c->fb_table[0], &c->fb_table[1],
+                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->perm, &c->border, &c->staging, &c->affine_tmp, &c->mb_fold, &c->mb_out, &c->pb_x, &c->pb_y, &c->pb_small, &c->fb_table[0], &c->fb_table[1],
                       &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols,
                       &c->lc_f12, &c->lc_pts, &c->lc_rows, &c->lc_iolp, &c->lc_work})
         b->release();
@@ -1130,6 +1133,22 @@ static int msm_sort(ps_ctx* c, const ps_scalars* sc, const MsmPlan& pl, bool tim
         hipLaunchKernelGGL(k_scatter, dim3(nblocks(total)), dim3(256), 0, st, (const u32*)c->keys.p, (const u32*)c->vals.p,
                            (const u32*)c->ranks.p, (const u32*)c->offs.p, total, (u32*)c->sorted.p);
     }
+    if (pl.acc != ACC_SLICES) {
+        // buckets in order of size and the verdict word for the whole-bucket point pass (msm.hpp section 4b); the verdict
+        // travels to the host like the entry count below, ahead of the results
+        if ((rc = c->perm.ensure(4 * G))) return rc;
+        if ((rc = c->border.ensure(4 * (2 * (size_t)BO_CLASSES + 4)))) return rc;
+        u32* hist = (u32*)c->border.p;
+        u32* cursors = hist + BO_CLASSES;
+        u32* verdict = cursors + BO_CLASSES;
+        const unsigned tiles = (unsigned)((G + BO_PLACE_TILE - 1) / BO_PLACE_TILE);
+        HIP_TRY(hipMemsetAsync(hist, 0, 4 * BO_CLASSES, st));
+        hipLaunchKernelGGL(k_bo_count, dim3(tiles), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, hist);
+        hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(BO_CLASSES), 0, st, (const u32*)hist, (const u32*)c->offs.p, (u32)G, (u32)pl.acc, cursors,
+                           verdict);
+        hipLaunchKernelGGL(k_bo_place, dim3(tiles), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, cursors, (u32*)c->perm.p);
+        HIP_TRY(hipMemcpyAsync((char*)c->h_pinned + c->h_pinned_cap - 16, verdict, 4, hipMemcpyDeviceToHost, st));
+    }
     PS_STAGE_MARK();  // 3: after scatter
     HIP_TRY(hipGetLastError());
     // entry count for introspection (read back with the window sums; a short sum's last kernel appends it to its results)
@@ -1224,9 +1243,19 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     if (wait_acc) HIP_TRY(hipStreamWaitEvent(st, wait_acc, 0));
     PS_STAGE_MARK();  // 4: buffers cleared and the previous sum's accumulation done ("queue")
     constexpr bool PF = LN == 1 || PS_G2_ACC_WAVES == 1;  // next point prefetched (the lane-pair G2 kernel at two waves per SIMD has no registers to spare)
+    // Whole buckets in order of size (msm.hpp section 4b) where the plan asks for them: forced, only that path is launched;
+    // automatic, both are enqueued and the verdict word the sort left on the device lets one of them return at once.
+    // ps_msm_batch (dev_sets) keeps the slices.
+    const u32 acc_mode = dev_sets ? (u32)ACC_SLICES : (u32)pl.acc;
+    const u32* verdict = acc_mode == ACC_SLICES ? nullptr : (const u32*)c->border.p + 2 * BO_CLASSES;
+    if (acc_mode != ACC_SLICES)
+        hipLaunchKernelGGL((k_bucket_sum<KF, PF>), dim3(nblocks(G * LN)), dim3(256), 0, st, src, (const u32*)c->sorted.p,
+                           (const u32*)c->offs.p, (const u32*)c->perm.p, (u32)G, idx_mask, w_stride, pstride, (Xyzz<F>*)wc->buckets.p,
+                           (u32*)wc->heavy.p, verdict);
+    if (acc_mode != ACC_BUCKETS)
     hipLaunchKernelGGL((k_accumulate<KF, PF>), dim3(nblocks((size_t)nthreads_acc * LN)), dim3(256), 0, st, src,
                        (const u32*)c->sorted.p, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, idx_mask, w_stride, pstride,
-                       (Xyzz<F>*)wc->buckets.p, (Xyzz<F>*)wc->parts.p, (u32*)wc->heavy.p);
+                       (Xyzz<F>*)wc->buckets.p, (Xyzz<F>*)wc->parts.p, (u32*)wc->heavy.p, verdict);
     if (acc_done) HIP_TRY(hipEventRecord(acc_done, st));
     PS_STAGE_MARK();  // 5: after accumulate
     HIP_TRY(hipEventRecord(wc->ev_acc_local, st));
@@ -1234,7 +1263,9 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
         st = wc->tail;   // ---- the rest runs on the high-priority tail stream ----
         HIP_TRY(hipStreamWaitEvent(st, wc->ev_acc_local, 0));
     }
-    if (pl.shortsum && pl.lpb >= 1) {
+    if (acc_mode == ACC_BUCKETS) {
+        // every bucket is final: no fix-up of any kind
+    } else if (pl.shortsum && pl.lpb >= 1) {
         // the plan of a multi-sum is shared by arrays of both groups (PHGR13: six G1 sums and a G2 one over one sort): the
         // quads of a bucket must fit THIS group's 256-thread block (64 G1 points, 32 G2 points)
         const u32 lpb = qlpb;
@@ -1244,10 +1275,10 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
         u32* ccount = (u32*)wc->heavy.p + 1;
         u32* clist = (u32*)wc->heavy.p + 2 + 2 * max_heavy + 1;
         hipLaunchKernelGGL(k_fixup_classify<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
-                           (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2, ccount, clist);
+                           (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2, ccount, clist, verdict);
         if (nthreads_acc > 1)  // one logical thread per slice boundary
             hipLaunchKernelGGL(k_fixup_pair<KF>, dim3(nblocks((size_t)(nthreads_acc - 1) * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G,
-                               pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p);
+                               pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, verdict);
         // a quad per listed bucket; the list's length stays on the device, so the grid is that of the longest list, within
         // one round of blocks
         constexpr u32 chain_npb = 256 / QTraits<KF>::GL;
@@ -1257,7 +1288,7 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     } else
     hipLaunchKernelGGL(k_fixup<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
                        (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2);
-    {
+    if (acc_mode != ACC_BUCKETS) {
         const u32* hcount = (const u32*)wc->heavy.p;
         const u32* hlist = hcount + 2;
         u32* job_base = (u32*)wc->heavy.p + 2 + max_heavy;
@@ -1465,6 +1496,9 @@ static int msm_plan_checked(ps_ctx* c, const ps_points* const* pts, size_t k, si
     msm_plan_tail(pl, n, plan_group, c->forced_tail, c->q_len > 0);
     if (c->forced_slice) pl.M = c->forced_slice;
     if (pl.shortsum) msm_plan_lpb(pl, n, plan_group);
+    // the point pass (bucket_order.hpp): forced, or automatic where the plan can make whole buckets pay; then the sort also
+    // orders the buckets by size and leaves the verdict word for msm_points_t
+    pl.acc = c->forced_acc ? c->forced_acc : bo_host_admits(pl.shortsum, pl.G, (u64)pl.W * n, max_bits) ? (int)ACC_AUTO : (int)ACC_SLICES;
     if ((u64)pl.W * (u64)n >= (1ull << 32))
         return fail(PS_ERR_ARG, "MSM too long: windows x length = " + std::to_string((u64)pl.W * (u64)n) +
                                     " digits do not fit the 32-bit sort offsets (split the sum, e.g. ps_points_slice)");
@@ -1534,6 +1568,11 @@ static u32 msm_entries(const ps_ctx* c, const MsmPlan& pl, int group) {
     if (!pl.qtail) return *(const u32*)((const char*)c->h_pinned + c->h_pinned_cap - 8);
     const size_t pt = group == PS_G1 ? sizeof(Xyzz<Fp>) : sizeof(Xyzz<Fp2>);
     return *(const u32*)((const char*)c->h_pinned + pt * (pl.sets > 1 ? (size_t)pl.sets : (size_t)pl.c));
+}
+
+// the point pass a finished sum took: what the plan fixed, or the verdict word that came back ahead of the results
+static int msm_acc_path(const ps_ctx* c, const MsmPlan& pl) {
+    return pl.acc != ACC_AUTO ? pl.acc : (int)*(const u32*)((const char*)c->h_pinned + c->h_pinned_cap - 16);
 }
 
 static void write_identity(int group, uint8_t* out) {  // zero.Clone(), algebra.go:353
@@ -1616,6 +1655,7 @@ static int msm_multi_finish(ps_ctx* c, ps_ctx* w0, const ps_points* const* pts, 
         else msm_fold_host<Fp2>(w0, pl, (int)i, out[i]);
     }
     c->last_info = ps_msm_info{pl.c, pl.W, msm_entries(w0, pl, pts[0]->group), pl.G, pl.M, pl.table ? 1 : 0};
+    c->last_acc = msm_acc_path(w0, pl);
     return PS_OK;
 }
 
@@ -1684,6 +1724,7 @@ static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc
         wc->forced_c = c->forced_c;
         wc->forced_slice = c->forced_slice;
         wc->forced_tail = c->forced_tail;
+        wc->forced_acc = c->forced_acc;
     }
     // Inputs enqueued on the context stream before the FIRST launch of a burst are visible to the worker
     // streams: the fork event is recorded while the queue is empty, ahead of that launch's own kernels
@@ -1737,6 +1778,7 @@ extern "C" int ps_msm_finish(ps_ctx* c, uint8_t* out) {
     if (e.group == PS_G1) msm_fold_host<Fp>(e.wc, pl, 0, out);
     else msm_fold_host<Fp2>(e.wc, pl, 0, out);
     c->last_info = ps_msm_info{pl.c, pl.W, msm_entries(e.wc, pl, e.group), pl.G, pl.M, pl.table ? 1 : 0};
+    c->last_acc = msm_acc_path(e.wc, pl);
     c->last_timed = e.wc;
     return PS_OK;
 }
@@ -1807,6 +1849,16 @@ extern "C" int ps_msm_set_slice(ps_ctx* c, int entries) {
 extern "C" int ps_msm_set_tail(ps_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return fail(PS_ERR_ARG, "tail mode must be 0 (automatic), 1 (chains) or 2 (trees)");
     c->forced_tail = mode;
+    return PS_OK;
+}
+extern "C" int ps_msm_set_accumulate(ps_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return fail(PS_ERR_ARG, "accumulate mode must be 0 (automatic), 1 (slices) or 2 (whole buckets)");
+    c->forced_acc = mode;
+    return PS_OK;
+}
+extern "C" int ps_msm_last_accumulate(ps_ctx* c, int* path) {
+    if (!c || !path) return fail(PS_ERR_ARG, "NULL argument");
+    *path = c->last_acc;
     return PS_OK;
 }
 extern "C" int ps_ctx_set_timing(ps_ctx* c, int enable) {

@@ -13,6 +13,8 @@
 //                   witness vectors, repeated scalars) -- and walks it with an XYZZ accumulator,
 //                   flushing whenever the bucket id changes.  Buckets that lie inside one slice
 //                   are final; runs cut by a slice boundary go to a head/tail partial slot.
+//   4b k_bucket_sum instead of 4 and 5 for long sums whose buckets are many and evenly filled: one lane per WHOLE bucket,
+//                   buckets taken in order of size (k_bo_count / k_bo_scan / k_bo_place at the end of the sort); no partial slots
 //   5 k_fixup_classify / k_fixup_pair / k_qfixup_chain   add up the partial slots of the buckets a slice boundary cuts
 //                   (short sums: k_qfixup, or k_fixup in one kernel)
 //   6 k_reduce_l1/pyr/sum/fin  per bucket set  sum_b (b+1)*B[b]: 8-bucket running sums, then sums by the bits of the
@@ -26,6 +28,7 @@
 #pragma once
 #include "curve.hpp"
 #include "fixup_class.hpp"
+#include "bucket_order.hpp"
 
 namespace ps {
 
@@ -56,6 +59,7 @@ struct MsmPlan {
     int lpb;      // quads per bucket in k_qfixup (0: the one-thread-per-bucket k_fixup)
     int rc_s;     // column bits of the row / column split of a bucket set (0: bit sums straight from the buckets)
     bool busy;    // planned while other sums were pending on the context: lane-time counts, not depth (capi.hip, msm_plan_tail)
+    int acc;      // the point pass (bucket_order.hpp): ACC_SLICES, ACC_BUCKETS, or ACC_AUTO = both enqueued, the device's verdict word picks
 };
 // Entries of the sorted list: point index | window << ENTRY_W_SHIFT | sign << 31.  The window field is used only
 // with a window table (then the index must fit ENTRY_W_SHIFT bits); without one the index may use all 31 bits.
@@ -91,6 +95,7 @@ static inline MsmPlan msm_plan(size_t n, int max_bits, int forced_c) {
     while (best.M < 1024 && (u64)best.M * 5 * best.G < total) best.M *= 2;  // ... and an average bucket spans <= 5 slices (below)
     while (best.M > 8 && total / (u64)best.M < (1u << 17) && (u64)(best.M / 2) * 5 * best.G >= total) best.M /= 2;  // short sums (below)
     best.SEG = 8;
+    best.acc = ACC_SLICES;  // msm_plan_checked (capi.hip) decides otherwise
     return best;
 }
 // Plan over a window table built for c-bit windows: one bucket set whatever the number of windows.
@@ -114,6 +119,7 @@ static inline MsmPlan msm_plan_table(size_t n, int max_bits, int c) {
     // than 2^17 threads (two waves per SIMD), halve it -- down to 8, and never past the five-slice rule above.
     while (pl.M > 8 && total / (u64)pl.M < (1u << 17) && (u64)(pl.M / 2) * 5 * pl.G >= total) pl.M /= 2;
     pl.SEG = 8;
+    pl.acc = ACC_SLICES;
     return pl;
 }
 
@@ -869,7 +875,8 @@ __global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_accumulate(const char
                                                        u32 G, int Mplan, u32 T, u32 idx_mask, u64 w_stride, u32 pstride,
                                                        Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
                                                        Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
-                                                       u32* __restrict__ heavy_count) {
+                                                       u32* __restrict__ heavy_count, const u32* __restrict__ verdict) {
+    if (verdict && *verdict == ACC_BUCKETS) return;  // automatic choice: k_bucket_sum took this sum (section 4b)
     const u32 E = offs[G];
     const int M = eff_slice(E, T, Mplan);
     const u32 t = logical_tid<KF>();
@@ -926,6 +933,131 @@ __global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_accumulate(const char
         }
     }
     flush_run<KF>(acc, g, run_start, end, start, t, offs, buckets, parts);
+}
+
+// ---------------------------------------------------------------------------------------
+// 4b. bucket accumulation over whole buckets in order of size
+// ---------------------------------------------------------------------------------------
+// Fixed slices cut nearly every bucket of an evenly filled long sum (2^20 points over a 20-bit table: 2^19 buckets of ~26
+// entries, slices of 32): every run start costs its wave a whole mixed addition for a copy, and the cut buckets need the
+// fix-up family with its partial slots.  Here ONE lane sums ONE bucket: E - G mixed additions, no partial slots, no binary
+// search, every bucket written by exactly one lane (empty ones included).  A wave runs as long as its largest bucket, so the
+// buckets are taken in order of size (bucket_order.hpp): the three kernels below run at the end of the sort.
+// The verdict word: ACC_BUCKETS or ACC_SLICES, decided on the device by k_bo_scan (or forced by the host); every kernel of
+// the path not taken reads it with one scalar load and returns.
+__global__ void __launch_bounds__(256) k_bo_count(const u32* __restrict__ offs, u32 G, u32* __restrict__ hist) {
+    PS_TAIL_PRIO_HERE;
+    __shared__ u32 lh[BO_CLASSES];
+    const u32 tid = threadIdx.x;
+    lh[tid] = 0;
+    __syncthreads();
+    const u32 base = blockIdx.x * BO_PLACE_TILE;
+#pragma unroll
+    for (u32 j = 0; j < BO_PLACE_ITEMS; j++) {
+        const u32 g = base + j * 256 + tid;
+        const bool act = g < G;
+        lds_count(lh, act ? bo_class(offs[g], offs[g + 1]) : 0u, act);
+    }
+    __syncthreads();
+    if (lh[tid]) atomicAdd(&hist[tid], lh[tid]);
+}
+// one workgroup: cursors[k] = first position of class k in perm[]; out[0] = the verdict (`forced` when not ACC_AUTO),
+// out[1] = the largest class, out[2] = non-empty buckets
+__global__ void __launch_bounds__(BO_CLASSES) k_bo_scan(const u32* __restrict__ hist, const u32* __restrict__ offs, u32 G, u32 forced,
+                                                        u32* __restrict__ cursors, u32* __restrict__ out) {
+    PS_TAIL_PRIO_HERE;
+    __shared__ u32 lh[BO_CLASSES], ls[BO_CLASSES];
+    __shared__ u32 maxc_s;
+    const u32 tid = threadIdx.x;
+    lh[tid] = hist[tid];
+    __syncthreads();
+    if (tid == 0) maxc_s = bo_scan_desc(lh, ls);  // 256 steps on one lane: a microsecond, and the host test runs the same code
+    __syncthreads();
+    cursors[tid] = ls[tid];
+    if (tid == 0) {
+        const u32 nonempty = G - lh[0];
+        out[0] = forced != ACC_AUTO ? forced : bo_verdict(maxc_s, nonempty, offs[G]);
+        out[1] = maxc_s;
+        out[2] = nonempty;
+    }
+}
+// perm[pos] = g: a workgroup reserves its run in every class with one returning add, LDS ranks inside it.  The order inside
+// a class differs from run to run; every bucket still has one writer and the arithmetic is exact, so the bytes do not.
+__global__ void __launch_bounds__(256) k_bo_place(const u32* __restrict__ offs, u32 G, u32* __restrict__ cursors, u32* __restrict__ perm) {
+    PS_TAIL_PRIO_HERE;
+    __shared__ u32 lh[BO_CLASSES];
+    const u32 tid = threadIdx.x;
+    lh[tid] = 0;
+    __syncthreads();
+    const u32 base = blockIdx.x * BO_PLACE_TILE;
+    u32 cls[BO_PLACE_ITEMS];
+#pragma unroll
+    for (u32 j = 0; j < BO_PLACE_ITEMS; j++) {
+        const u32 g = base + j * 256 + tid;
+        const bool act = g < G;
+        cls[j] = act ? bo_class(offs[g], offs[g + 1]) : 0u;
+        lds_count(lh, cls[j], act);
+    }
+    __syncthreads();
+    const u32 cnt = lh[tid];
+    __syncthreads();
+    lh[tid] = cnt ? atomicAdd(&cursors[tid], cnt) : 0u;
+    __syncthreads();
+#pragma unroll
+    for (u32 j = 0; j < BO_PLACE_ITEMS; j++) {
+        const u32 g = base + j * 256 + tid;
+        const bool act = g < G;
+        const u32 pos = lds_rank(lh, cls[j], act);
+        if (act) perm[pos] = g;  // pos < G: the classes' runs tile [0, G)
+    }
+}
+
+// Logical thread t sums bucket perm[t].  The first entry is a copy, and it is every lane's first trip at once (a wave's
+// buckets start together), so no lane pays an addition for it; the loop holds the one inlined mixed addition, with the
+// lookahead of k_accumulate: entries two ahead, points one ahead.
+template <class KF, bool PREFETCH>
+__global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_bucket_sum(const char* __restrict__ points, const u32* __restrict__ sorted,
+                                                       const u32* __restrict__ offs, const u32* __restrict__ perm, u32 G,
+                                                       u32 idx_mask, u64 w_stride, u32 pstride,
+                                                       Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
+                                                       u32* __restrict__ heavy_count, const u32* __restrict__ verdict) {
+    if (*verdict != ACC_BUCKETS) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) heavy_count[0] = heavy_count[1] = 0;  // no heavy and no chain buckets: the tail kernels that follow find nothing to do
+    const u32 t = logical_tid<KF>();
+    if (t >= G) return;
+    const u32 g = perm[t];
+    const u32 start = offs[g], end = offs[g + 1];
+    Xyzz<KF> acc = xyzz_identity<KF>();
+    if (start < end) {
+        if (PREFETCH) {
+            u32 e = sorted[start];
+            u32 e1 = start + 1 < end ? sorted[start + 1] : e;
+            Affine<KF> pt = ld_entry_point<KF>(points, e, idx_mask, w_stride, pstride);
+            for (u32 p = start; p < end; p++) {
+                Affine<KF> nxt = pt;
+                u32 e2 = e1;
+                if (p + 1 < end) nxt = ld_entry_point<KF>(points, e1, idx_mask, w_stride, pstride);
+                if (p + 2 < end) e2 = sorted[p + 2];
+                if (!affine_is_identity<KF>(pt)) {
+                    if (e >> 31) pt.y = f_neg(pt.y);
+                    if (p == start) acc = xyzz_from_affine<KF>(pt.x, pt.y);
+                    else xyzz_madd_inl<KF>(acc, pt.x, pt.y);
+                }
+                pt = nxt; e = e1; e1 = e2;
+            }
+        } else {
+            for (u32 p = start; p < end; p++) {
+                const u32 e = sorted[p];
+                Affine<KF> pt = ld_entry_point<KF>(points, e, idx_mask, w_stride, pstride);
+                if (!affine_is_identity<KF>(pt)) {
+                    if (e >> 31) pt.y = f_neg(pt.y);
+                    if (p == start) acc = xyzz_from_affine<KF>(pt.x, pt.y);
+                    else xyzz_madd_inl<KF>(acc, pt.x, pt.y);
+                }
+            }
+        }
+    }
+    st_xyzz<KF>(&buckets[g], acc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -989,8 +1121,10 @@ template <class KF>
 __global__ void __launch_bounds__(256) k_fixup_classify(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
                                                         Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
                                                         u32* __restrict__ heavy_count, u32* __restrict__ heavy_list,
-                                                        u32* __restrict__ chain_count, u32* __restrict__ chain_list) {
+                                                        u32* __restrict__ chain_count, u32* __restrict__ chain_list,
+                                                        const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
+    if (verdict && *verdict == ACC_BUCKETS) return;  // k_bucket_sum wrote every bucket and left both lists empty
     const u32 g = logical_tid<KF>();
     if (g >= G) return;
     const int M = eff_slice(offs[G], T, Mplan);
@@ -1008,8 +1142,10 @@ __global__ void __launch_bounds__(256) k_fixup_classify(const u32* __restrict__ 
 template <class KF>
 __global__ void __launch_bounds__(256, PS_TAIL_WAVES) k_fixup_pair(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
                                                        const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
-                                                       Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets) {
+                                                       Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
+                                                       const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
+    if (verdict && *verdict == ACC_BUCKETS) return;
     const u32 t = logical_tid<KF>() + 1;  // slice boundary t lies between slices t - 1 and t
     if (t >= T) return;
     const u32 E = offs[G];

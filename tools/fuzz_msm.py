@@ -2,7 +2,9 @@
 tables), slice lengths, tail (chains / trees of lane-cooperative additions / automatic), scalar distributions (uniform,
 short, skewed, zeros, r - 1, repeated points); every fourth case a multi-sum over arrays of BOTH groups (one sort, one
 plan) or a burst of sums in flight.
-  python3 tools/fuzz_msm.py [seconds] [seed]        (GPU box; exits non-zero on the first mismatch)"""
+  python3 tools/fuzz_msm.py [seconds] [seed] [auto|mixed]   (GPU box; exits non-zero on the first mismatch)
+The point pass (ctx.set_accumulate) is left automatic; `mixed` draws it per case -- automatic, slices, whole buckets -- from
+a generator of its own, so the cases of a seed are the same either way."""
 import os
 import random
 import sys
@@ -15,6 +17,7 @@ from playsnark_amd import api  # noqa: E402
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rnd = random.Random(seed)
+acc_rnd = random.Random(seed ^ 0xACC) if len(sys.argv) > 3 and sys.argv[3] == "mixed" else None
 ctx = api.Context(0)
 t_end = time.time() + budget
 cases = 0
@@ -57,6 +60,8 @@ while time.time() < t_end:
         ctx.set_slice(m)
     tail = rnd.choice([0, 0, 1, 2, 2])
     ctx.set_tail(tail)
+    acc = acc_rnd.choice([0, 1, 2, 2]) if acc_rnd else 0
+    ctx.set_accumulate(acc)
     try:
         poly = api.Poly.upload(ctx, sc)
         got = poly.BlindEval(pts)
@@ -95,8 +100,9 @@ while time.time() < t_end:
         ctx.set_window(0)
         ctx.set_slice(0)
         ctx.set_tail(0)
+        ctx.set_accumulate(0)
     if got != want:
-        print("MISMATCH", dict(group=group, n=n, dist=dist, mode=mode, c=c, m=m, tail=tail, seed=seed, case=cases, info=ctx.last_msm_info()))
+        print("MISMATCH", dict(group=group, n=n, dist=dist, mode=mode, c=c, m=m, tail=tail, acc=acc, seed=seed, case=cases, info=ctx.last_msm_info()))
         sys.exit(1)
     cases += 1
     if cases % 50 == 0:
