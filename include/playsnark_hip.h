@@ -56,7 +56,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_groth16_srs), ps_groth16_crs_contribute and ps_groth16_crs_check_update; then ps_scalars_powers,
  *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
  *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
- *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch. */
+ *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch;
+ *      then ps_msm_batch_multi and ps_phgr13_prove_batch. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -180,6 +181,24 @@ int ps_msm_multi(ps_ctx* ctx, const ps_points* const* points, size_t k, const ps
  * the members of a pass (0 = automatic).  A batch of which not even one member fits a pass is summed by ps_msm per member. */
 int ps_msm_batch(ps_ctx* ctx, const ps_points* points, const ps_scalars* scalars, size_t k, uint8_t* out);
 int ps_msm_batch_set_chunk(ps_ctx* ctx, int members /* sums per pass; 0 = automatic */);
+/* The product of the two: k scalar vectors over `a` point arrays, ONE digit sort per pass shared by all arrays (as in
+ * ps_msm_multi) and one bucket problem of k * W bucket sets per array (as in ps_msm_batch).
+ * out[i][j] = sum_{t<n} scalars[j*stride + first + t] * points[i][t],  i < a, j < k,  n = the common length of the arrays.
+ * out[i]: k * 96 (G1) / k * 192 (G2) bytes.  Arrays may mix groups.  Entry (i, j) is byte-identical to ps_msm over points[i]
+ * and the slice [j*stride + first, +n) of `scalars`; with a == 1, stride == n, first == 0 the call is ps_msm_batch.  This is
+ * the shape of computeSolCommit on solution[diff:] (pinochio.go:222-241) for k solutions stored back to back: stride = the
+ * number of variables, first = diff.  Scalars outside the members' ranges -- the IO part of a witness, the gaps between
+ * members -- are never read.
+ * a <= PS_MSM_MULTI_MAX; a NULL array or a NULL out[i] is PS_ERR_ARG.  Arrays of different lengths: PS_ERR_LENGTH
+ * (algebra.go:350-352); so are first + n > stride and ps_scalars_len(scalars) != k*stride.  a == 0 or k == 0: PS_OK;
+ * n == 0: PS_OK, identities.  Needs an empty MSM queue (PS_ERR_ARG otherwise).  Window tables on the arrays are ignored;
+ * ps_msm_set_window, ps_msm_set_slice, ps_msm_set_tail and ps_msm_batch_set_chunk are honoured as in ps_msm_batch, and a
+ * batch of which not even one member fits a pass is summed by ps_msm per (array, member).
+ * Each array's point pass, fold and encoding run on a workspace of their own (four rotate), so the folds of different arrays
+ * -- serial chains of ~250 doublings each -- run side by side; every workspace is idle again when the call returns, on every
+ * path.  Added within revision 5 (found by symbol, no existing struct changed). */
+int ps_msm_batch_multi(ps_ctx* ctx, const ps_points* const* points, size_t a, const ps_scalars* scalars, size_t k,
+                       size_t stride, size_t first, uint8_t* const* out);
 /* Host-side conversion of ONE point between PS_FMT_AFFINE and PS_FMT_COMPRESSED (what the shim
  * needs to feed proof elements back to kyber's UnmarshalBinary).  Validates the encoding. */
 int ps_point_convert(int group, int in_fmt, int out_fmt, const uint8_t* in, uint8_t* out);
@@ -381,6 +400,23 @@ typedef struct { /* PHGR13Proof (pinochio.go:180-203) */
 /* PHGR13Prove (pinochio.go:207-254). */
 int ps_phgr13_prove(ps_ctx* ctx, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sol,
                     ps_phgr13_proof* out);
+
+/* k proofs under one evaluation key: sols holds k solution vectors of q's m variables back to back; out: k proofs.
+ * Proof j is byte-identical to ps_phgr13_prove(ctx, ek, q, sols[j*m .. (j+1)*m), &out[j]).  (pinochio.go:207-254, k times.)
+ * One pass of wire values and gate checks over all witnesses, the h values witness by witness without a host
+ * synchronisation between them, hs as one ps_msm_batch over lgsi, and the other seven elements as ONE ps_msm_batch_multi
+ * over vs, ws, ys, vas, was, yas and the pointwise sum of the three beta arrays, reading solution[diff:] of every witness in
+ * place.
+ * Needs lgsi in the key: PS_ERR_ARG otherwise, naming ps_points_monomial_to_lagrange.  The nine solution arrays must have one
+ * length nn with diff + nn <= m, and gsi / lgsi n - 1 points (PS_ERR_LENGTH otherwise); ps_scalars_len(sols) == k*m and
+ * n >= 2 (PS_ERR_ARG); k*m and k*(n-1) below 2^31 (PS_ERR_ARG: split the batch).
+ * valid == NULL: a witness that violates a gate fails the call with PS_ERR_NOT_DIVISIBLE ("apocalypse", qap.go:158-160; the
+ * message names the first such index).  valid != NULL: PS_OK, valid[j] = 0 and all 864 bytes of proof j are zero, every
+ * other proof as above.  k == 0: PS_OK.  Needs an empty MSM queue; ps_msm_batch_set_chunk bounds the members per pass.
+ * ps_prove_last_phase_ms: [0] wire values, gate check and h values, [1] the h sum, [2] the solution sums, [3] total.
+ * Added within revision 5 (found by symbol, no existing struct changed). */
+int ps_phgr13_prove_batch(ps_ctx* ctx, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sols, size_t k,
+                          ps_phgr13_proof* out, int* valid);
 
 /* One rank's share of PHGR13Prove when the sums are sharded over `world` GPUs (one process each), the twin of
  * ps_groth16_prove_shard: every rank holds the WHOLE key and computes the quotient itself; rank g sums its index range of

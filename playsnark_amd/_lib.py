@@ -36,6 +36,7 @@ SYMBOLS = [
     "ps_points_lagrange_check", "ps_groth16_crs_check_from_srs",
     "ps_qap_create_fr", "ps_qap_wide_entries",
     "ps_msm_batch", "ps_msm_batch_set_chunk", "ps_groth16_prove_batch",
+    "ps_msm_batch_multi", "ps_phgr13_prove_batch",
     "ps_msm_set_accumulate", "ps_msm_last_accumulate",
 ]
 
@@ -176,6 +177,7 @@ def _load():
     lib.ps_msm_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.POINTER(vp)]
     lib.ps_msm_batch.argtypes = [vp, vp, vp, sz, C.c_char_p]
     lib.ps_msm_batch_set_chunk.argtypes = [vp, i]
+    lib.ps_msm_batch_multi.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz, C.POINTER(vp)]
     lib.ps_points_sum.argtypes = [i, C.c_char_p, sz, C.c_char_p]
     lib.ps_point_convert.argtypes = [i, i, i, C.c_char_p, C.c_char_p]
     lib.ps_msm_last_info.argtypes = [vp, C.POINTER(MsmInfo)]
@@ -211,6 +213,7 @@ def _load():
     lib.ps_groth16_prove_local.argtypes = [vp, C.POINTER(Groth16Pk), vp, vp, C.c_char_p, C.c_char_p, i, i, C.c_char_p,
                                            C.c_char_p, C.c_char_p]
     lib.ps_phgr13_prove.argtypes = [vp, C.POINTER(Phgr13Ek), vp, vp, C.POINTER(Phgr13Proof)]
+    lib.ps_phgr13_prove_batch.argtypes = [vp, C.POINTER(Phgr13Ek), vp, vp, sz, C.POINTER(Phgr13Proof), C.POINTER(C.c_int)]
     lib.ps_phgr13_prove_shard.argtypes = [vp, C.POINTER(Phgr13Ek), vp, vp, i, i, C.POINTER(Phgr13Proof)]
     lib.ps_phgr13_prove_multi.argtypes = [C.POINTER(Phgr13Device), sz, C.POINTER(Phgr13Proof)]
     lib.ps_groth16_setup.argtypes = [vp, vp, C.POINTER(Groth16Toxic), C.POINTER(Groth16Crs)]

@@ -395,6 +395,20 @@ def msm_batch(ctx: Context, points: Points, scalars: Poly, k: int) -> list:
     return [out.raw[j * nb : (j + 1) * nb] for j in range(k)]
 
 
+def msm_batch_multi(ctx: Context, points: list, scalars: Poly, k: int, stride: Optional[int] = None, first: int = 0) -> list:
+    """out[i][j] = scalars[j*stride + first : j*stride + first + n].BlindEval(points[i]), n = the arrays' common length
+    (ps_msm_batch_multi): k scalar vectors over several point arrays, one digit sort per pass shared by all arrays and one
+    bucket problem per array.  stride=None: the members back to back (stride = n).  Returns a list per array of k results."""
+    a = len(points)
+    if stride is None:
+        stride = len(points[0]) if a else 0
+    outs = [C.create_string_buffer(max(k, 1) * _WIRE[p.group]) for p in points]
+    pa = (C.c_void_p * max(a, 1))(*[p._h for p in points])
+    oa = (C.c_void_p * max(a, 1))(*[C.cast(o, C.c_void_p) for o in outs])
+    _check(lib.ps_msm_batch_multi(ctx._h, pa, a, scalars._h, k, stride, first, oa))
+    return [[o.raw[j * _WIRE[p.group] : (j + 1) * _WIRE[p.group]] for j in range(k)] for p, o in zip(points, outs)]
+
+
 def point_convert(group: int, raw: bytes, in_fmt: int, out_fmt: int) -> bytes:
     """One point between the ZCash uncompressed and compressed forms (kyber MarshalBinary)."""
     out = C.create_string_buffer(_WIRE[group] if out_fmt == _lib.PS_FMT_AFFINE else _WIRE[group] // 2)
@@ -944,6 +958,19 @@ def PHGR13Prove(ek: PHGR13EvalKey, qap: QAP, solution: Poly) -> PHGR13Proof:
     s = ek._struct()
     _check(lib.ps_phgr13_prove(qap.ctx._h, C.byref(s), qap._h, solution._h, C.byref(out)))
     return PHGR13Proof(out)
+
+
+def PHGR13ProveBatch(ek: PHGR13EvalKey, qap: QAP, sols: Poly, k: int, valid: bool = False):
+    """[PHGR13Prove(ek, qap, sols[j*m:(j+1)*m]) for j in range(k)] in one call (ps_phgr13_prove_batch): the witnesses of ONE
+    circuit back to back in `sols`, one key, which must carry lgsi (with_lagrange; NewPHGR13TrustedSetup emits it).
+    valid=False: a list of PHGR13Proof; a witness that violates a gate raises Apocalypse.  valid=True: (proofs, flags) with
+    flags[j] == 0 and proof j all zero bytes for such a witness, every other proof as usual."""
+    out = (_lib.Phgr13Proof * max(k, 1))()
+    flags = (C.c_int * max(k, 1))() if valid else None
+    s = ek._struct()
+    _check(lib.ps_phgr13_prove_batch(qap.ctx._h, C.byref(s), qap._h, sols._h, k, out, flags))
+    proofs = [PHGR13Proof(out[j]) for j in range(k)]
+    return (proofs, list(flags)[:k]) if valid else proofs
 
 
 def PHGR13ProveShard(ek: PHGR13EvalKey, qap: QAP, solution: Poly, rank: int, world: int) -> PHGR13Proof:

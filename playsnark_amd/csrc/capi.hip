@@ -20,6 +20,7 @@
 #include "msm.hpp"
 #include "msm_batch.hpp"
 #include "msm_batch_plan.hpp"
+#include "msm_batch_multi_plan.hpp"
 #include "quotient.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
@@ -2048,6 +2049,7 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "prove.inc"
 #include "prove_shares.inc"
 #include "prove_batch.inc"
+#include "phgr13_batch.inc"
 #include "lagrange.inc"
 #include "pairing.inc"
 #include "pairing_dev.hpp"

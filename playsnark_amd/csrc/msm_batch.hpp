@@ -13,8 +13,10 @@
 
 namespace ps {
 
-// k_sort_count over the virtual array: codes[w][j] for j < N, coarse histogram of the batch keys
-__global__ void __launch_bounds__(DIGITS_THREADS) k_sort_count_batch(const u32* __restrict__ scalars, u32 n, u32 N, int c, int W, u32 NB,
+// k_sort_count over the virtual array: codes[w][j] for j < N, coarse histogram of the batch keys.  Member j's scalars start
+// at scalar index j * stride (stride >= n: ps_msm_batch packs its members, stride == n, and reads the addresses it always
+// read; ps_msm_batch_multi reads n scalars out of each solution vector and never touches what lies between them)
+__global__ void __launch_bounds__(DIGITS_THREADS) k_sort_count_batch(const u32* __restrict__ scalars, u32 n, u32 stride, u32 N, int c, int W, u32 NB,
                                                                      DigitConst cadd, int fold_neg, u32 ncoarse, int fb,
                                                                      u32* __restrict__ codes, u32* __restrict__ coarse_cnt) {
     PS_TAIL_PRIO_HERE;
@@ -26,8 +28,9 @@ __global__ void __launch_bounds__(DIGITS_THREADS) k_sort_count_batch(const u32* 
         const u32 i = (blockIdx.x * COUNT_PER_THREAD + (u32)j) * DIGITS_THREADS + tid;
         const bool in = i < N;
         u32 k[8], carry = 0, flip = 0;
-        if (in) scalar_plus_c(scalars, i, cadd, fold_neg, k, carry, flip);
-        const u32 set0 = in ? (i / n) * (u32)W : 0u;  // first bucket set of this entry's member
+        const u32 mem = in ? i / n : 0u;  // this entry's member
+        if (in) scalar_plus_c(scalars, mem * stride + (i - mem * n), cadd, fold_neg, k, carry, flip);
+        const u32 set0 = mem * (u32)W;  // first bucket set of the member
         for (int w = 0; w < W; w++) {  // uniform trip count: lds_count is called by whole waves
             u32 code = 0xffffffffu;
             if (in) {

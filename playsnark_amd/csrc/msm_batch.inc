@@ -38,8 +38,10 @@ static MsmPlan msm_batch_plan(const ps_ctx* c, const MsmPlan& one, size_t n, siz
     return pl;
 }
 
-// The two-level sort of msm_sort over the virtual array of kc * n scalars starting at `scal` (msm_batch.hpp).
-static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t kc, int fold_neg, const MsmPlan& pl, bool timed, hipStream_t st) {
+// The two-level sort of msm_sort over the virtual array of kc * n scalars (msm_batch.hpp): member j's n scalars start at
+// scalar index j * stride of `scal` (ps_msm_batch: stride == n, the members back to back).
+static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, size_t kc, int fold_neg, const MsmPlan& pl, bool timed,
+                          hipStream_t st) {
     const u64 N = (u64)kc * n;
     const u64 total = (u64)pl.W * N;  // upper bound on entries
     const u64 G = pl.G;
@@ -73,8 +75,8 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t kc, int f
     if (may_have_big_bins) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 4 * G, st));
     const dim3 cgrid((unsigned)((N + (size_t)COUNT_PER_THREAD * DIGITS_THREADS - 1) / ((size_t)COUNT_PER_THREAD * DIGITS_THREADS)));
     const dim3 dgrid((unsigned)((N + DIGITS_CHUNK - 1) / DIGITS_CHUNK), (unsigned)pl.W);
-    hipLaunchKernelGGL(k_sort_count_batch, cgrid, dim3(DIGITS_THREADS), 0, st, scal, (u32)n, (u32)N, pl.c, pl.W, pl.NB, cadd, fold_neg, ncoarse, fb,
-                       (u32*)c->ranks.p, coarse_cnt);
+    hipLaunchKernelGGL(k_sort_count_batch, cgrid, dim3(DIGITS_THREADS), 0, st, scal, (u32)n, (u32)stride, (u32)N, pl.c, pl.W, pl.NB, cadd, fold_neg,
+                       ncoarse, fb, (u32*)c->ranks.p, coarse_cnt);
     PS_BATCH_MARK();  // 1: after digits + coarse histogram
     hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_MAX_COARSE), 0, st, (const u32*)coarse_cnt, ncoarse, coarse_off, coarse_cur,
                        (u32*)c->offs.p + G, tile_base);
@@ -99,43 +101,151 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t kc, int f
     return PS_OK;
 }
 
-// One pass: members [first, first + kc) of `sc`, their wire bytes to out[first ..] -- everything on the context stream; the
-// caller synchronises once behind the last pass.
+// Where a workspace keeps what one pass leaves in its mb_out: the affine sums of the array it is working on (read by the
+// encoding only), then one slot of wire bytes per array it serves in this pass -- a workspace that serves several arrays
+// (more arrays than workspaces) keeps every array's bytes until the copies at the end of the pass.
+struct BatchOut { size_t affine_bytes, slot_bytes; };
+
+// One array's share of a pass: the point pass over the sort that `c` owns (sorted / offs), the fold per member, the
+// normalisation and the encoding -- all on workspace wc's stream and in wc's buffers (wc == c: ps_msm_batch).  The kc * wb
+// wire bytes are left in slot `slot` of wc->mb_out.
 template <class F>
-static int msm_batch_pass(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, size_t first, size_t kc, const MsmPlan& one, uint8_t* out) {
+static int msm_batch_points(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, size_t kc, const MsmPlan& pl, bool timed,
+                            const BatchOut& lay, size_t slot) {
     typedef typename KernelField<F>::type KF;
     constexpr unsigned LN = FieldTraits<KF>::LANES;
-    const size_t n = pts->n, wb = wire_bytes(pts->group);
-    const MsmPlan pl = msm_batch_plan(c, one, n, kc, pts->group);
-    hipStream_t st = c->stream;
+    hipStream_t st = wc->stream;
     int rc;
-    if ((rc = msm_batch_sort(c, scalars_ptr(sc) + 8 * first * n, n, kc, sc->neg_small ? 1 : 0, pl, c->timing, st))) return rc;
     Xyzz<F>* dsets = nullptr;
-    if ((rc = msm_points_t<F>(c, c, pts, kc * n, pl, c->timing, 0, nullptr, nullptr, true, &dsets))) return rc;
-    c->ev_valid = c->timing;
-    c->last_timed = c;
-    if ((rc = c->mb_fold.ensure(batch_affine_tmp_bytes(kc, sizeof(Xyzz<F>))))) return rc;
-    if ((rc = c->mb_out.ensure(kc * (sizeof(Affine<F>) + wb)))) return rc;
-    if (c->timing) {
+    if ((rc = msm_points_t<F>(c, wc, pts, kc * n, pl, timed, 0, nullptr, nullptr, true, &dsets))) return rc;
+    if (timed) {
         for (auto& e : c->mb_ev) if (!e) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipEventRecord(c->mb_ev[0], st));
     }
     hipLaunchKernelGGL(k_batch_fold<KF>, dim3(nblocks(kc * LN)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, pl.W, pl.c,
-                       (Xyzz<F>*)c->mb_fold.p);
-    batch_to_affine<F>(c, (char*)c->mb_fold.p, kc, (char*)c->mb_out.p, (u32)sizeof(Affine<F>));
-    uint8_t* d_bytes = (uint8_t*)c->mb_out.p + kc * sizeof(Affine<F>);
+                       (Xyzz<F>*)wc->mb_fold.p);
+    batch_to_affine<F>(wc, (char*)wc->mb_fold.p, kc, (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+    uint8_t* d_bytes = (uint8_t*)wc->mb_out.p + lay.affine_bytes + slot * lay.slot_bytes;
     if (pts->group == PS_G1)
-        hipLaunchKernelGGL(k_points_to_bytes_g1, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp>*)c->mb_out.p, (u32)kc, d_bytes);
+        hipLaunchKernelGGL(k_points_to_bytes_g1, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp>*)wc->mb_out.p, (u32)kc, d_bytes);
     else
-        hipLaunchKernelGGL(k_points_to_bytes_g2, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp2>*)c->mb_out.p, (u32)kc, d_bytes);
+        hipLaunchKernelGGL(k_points_to_bytes_g2, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp2>*)wc->mb_out.p, (u32)kc, d_bytes);
     HIP_TRY(hipGetLastError());
-    if (c->timing) HIP_TRY(hipEventRecord(c->mb_ev[1], st));
-    HIP_TRY(hipMemcpyAsync(out + first * wb, d_bytes, kc * wb, hipMemcpyDeviceToHost, st));
-    // the results of this pass are read and the tail's buffers free before the next pass reuses them (same stream), and the
-    // context's other users order themselves behind ev_tail_done as behind any sum
-    HIP_TRY(hipEventRecord(c->ev_tail_done, st));
+    if (timed) HIP_TRY(hipEventRecord(c->mb_ev[1], st));
+    return PS_OK;
+}
+
+// The workspaces a call over `a` arrays uses: ring[i % PS_MULTI_RING] serves array i, the first min(a, PS_MULTI_RING) entries
+// are distinct (msm_multi_ring).
+static inline size_t msm_batch_used(size_t a) { return std::min<size_t>(a, PS_MULTI_RING); }
+
+// One pass: members [first, first + kc) of the batch, for every array.  ONE sort on the context stream over the strided
+// source (`scal`: the first scalar of member 0), then per array msm_batch_points on its workspace -- the folds of different
+// arrays (serial chains of ~250 doublings) sit on different streams and run side by side; a workspace that serves a second
+// array takes it up behind its own fold, in stream order.  Every array's launches are enqueued before the first copy: a
+// copy to pageable memory holds the host until its stream has drained.  The caller synchronises behind the last pass.
+static int msm_batch_pass(ps_ctx* c, ps_ctx* const* ring, const ps_points* const* pts, size_t a, const u32* scal, size_t n, size_t stride,
+                          size_t first, size_t kc, int fold_neg, const MsmPlan& one, int plan_group, uint8_t* const* out) {
+    const MsmPlan pl = msm_batch_plan(c, one, n, kc, plan_group);
+    const size_t used = msm_batch_used(a);
+    const bool timed = c->timing && a == 1;  // stage events describe one array's pass
+    hipStream_t st = c->stream;
+    int rc;
+    // buffers of every workspace, sized for the largest group it serves, before anything is enqueued
+    BatchOut lay{0, 0};
+    size_t xyzz = 0;
+    for (size_t i = 0; i < a; i++) {
+        const bool g1 = pts[i]->group == PS_G1;
+        lay.affine_bytes = std::max(lay.affine_bytes, kc * (g1 ? sizeof(Affine<Fp>) : sizeof(Affine<Fp2>)));
+        lay.slot_bytes = std::max(lay.slot_bytes, kc * wire_bytes(pts[i]->group));
+        xyzz = std::max(xyzz, g1 ? sizeof(Xyzz<Fp>) : sizeof(Xyzz<Fp2>));
+    }
+    for (size_t j = 0; j < used; j++) {
+        const size_t slots = (a - j + PS_MULTI_RING - 1) / PS_MULTI_RING;  // arrays j, j + ring, ...
+        if ((rc = ring[j]->mb_fold.ensure(batch_affine_tmp_bytes(kc, xyzz)))) return rc;
+        if ((rc = ring[j]->mb_out.ensure(lay.affine_bytes + slots * lay.slot_bytes))) return rc;
+    }
+    // the point passes of the pass before, on the other workspaces, still read sorted / offs (the context's own: msm_batch_sort)
+    for (size_t j = 0; j < used; j++)
+        if (ring[j] != c && ring[j]->tail_used) HIP_TRY(hipStreamWaitEvent(st, ring[j]->ev_tail_done, 0));
+    if ((rc = msm_batch_sort(c, scal + 8 * first * stride, n, stride, kc, fold_neg, pl, timed, st))) return rc;
+    if (used > 1) {
+        if (!c->ev_sorted) HIP_TRY(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->ev_sorted, st));
+        for (size_t j = 0; j < used; j++)
+            if (ring[j] != c) HIP_TRY(hipStreamWaitEvent(ring[j]->stream, c->ev_sorted, 0));
+    }
+    for (size_t i = 0; i < a; i++) {
+        ps_ctx* wc = ring[i % PS_MULTI_RING];
+        rc = pts[i]->group == PS_G1 ? msm_batch_points<Fp>(c, wc, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING)
+                                    : msm_batch_points<Fp2>(c, wc, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING);
+        if (rc) return rc;
+    }
+    c->ev_valid = timed;
+    c->last_timed = c;
+    for (size_t i = 0; i < a; i++) {
+        ps_ctx* wc = ring[i % PS_MULTI_RING];
+        const size_t wb = wire_bytes(pts[i]->group);
+        const uint8_t* d_bytes = (const uint8_t*)wc->mb_out.p + lay.affine_bytes + (i / PS_MULTI_RING) * lay.slot_bytes;
+        HIP_TRY(hipMemcpyAsync(out[i] + first * wb, d_bytes, kc * wb, hipMemcpyDeviceToHost, wc->stream));
+    }
+    // the results of this pass are read and the tails' buffers free before the next pass reuses them (same streams), and the
+    // workspaces' other users order themselves behind ev_tail_done as behind any sum
+    for (size_t j = 0; j < used; j++) HIP_TRY(hipEventRecord(ring[j]->ev_tail_done, ring[j]->stream));
     c->last_info = ps_msm_info{pl.c, pl.W, 0, pl.G, pl.M, 0};
     return PS_OK;
+}
+
+// every workspace the call used is idle when it returns, whatever happened: the next call on the context starts clean
+static int msm_batch_drain(ps_ctx* const* ring, size_t a) {
+    hipError_t first = hipSuccess;
+    for (size_t j = 0; j < msm_batch_used(a); j++) {
+        const hipError_t e = hipStreamSynchronize(ring[j]->stream);
+        if (first == hipSuccess) first = e;
+    }
+    if (first != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_msm_batch: hipStreamSynchronize: ") + hipGetErrorString(first));
+    return PS_OK;
+}
+
+// k members of n scalars each (member j at scalar index j * stride + first of `sc`) over `a` arrays of n points; the caller has
+// checked every length.  ps_msm_batch is a == 1 on the context's own workspace.
+static int msm_batch_run(ps_ctx* c, const ps_points* const* pts, size_t a, const ps_scalars* sc, size_t k, size_t stride, size_t first,
+                         uint8_t* const* out) {
+    const size_t n = pts[0]->n;
+    bool any_g1 = false, any_g2 = false;
+    for (size_t i = 0; i < a; i++) (pts[i]->group == PS_G1 ? any_g1 : any_g2) = true;
+    const int plan_group = any_g2 ? PS_G2 : PS_G1;  // the tail is sized for the group whose points take more lanes (msm_plan_checked)
+    HIP_TRY(hipSetDevice(c->device));
+    const MsmPlan one = msm_plan(n, sc->max_bits, c->forced_c);
+    const u64 pb = batch_multi_point_bytes(any_g1, any_g2, sizeof(Xyzz<Fp>), sizeof(Xyzz<Fp2>));
+    const BatchShape shape{(u64)n, (u64)one.W, (u64)one.NB, pb, (u64)(c->forced_slice ? c->forced_slice : 2)};
+    std::vector<BatchPass> passes;
+    if (!batch_multi_passes((u64)k, shape, msm_batch_limits(c), (u64)stride, &passes)) {
+        // not even one member fits a pass (n * W >= 2^31, or a forced window whose W * NB buckets exceed the sort's): one by one
+        for (size_t i = 0; i < a; i++)
+            for (size_t j = 0; j < k; j++) {
+                Scope scope;
+                ps_scalars** sl = scope.scalars();
+                int rc = ps_scalars_slice(sc, j * stride + first, n, sl);
+                if (!rc) rc = ps_msm(c, pts[i], *sl, out[i] + j * wire_bytes(pts[i]->group));
+                if (rc) return rc;
+            }
+        return PS_OK;
+    }
+    ps_ctx* ring[PS_MULTI_RING];
+    int rc = msm_multi_ring(c, true, a, ring);
+    if (rc) return rc;
+    if (storage_wait_ready(sc->st, c->stream)) return fail(PS_ERR_HIP, "ps_msm_batch: event wait failed");  // asynchronously produced scalars
+    for (const BatchPass& p : passes)
+        if ((rc = msm_batch_pass(c, ring, pts, a, scalars_ptr(sc) + 8 * first, n, stride, (size_t)p.first, (size_t)p.count, sc->neg_small ? 1 : 0,
+                                 one, plan_group, out)))
+            break;
+    if (rc) {
+        KeepError keep;
+        (void)msm_batch_drain(ring, a);
+        return rc;
+    }
+    return msm_batch_drain(ring, a);
 }
 
 extern "C" int ps_msm_batch_set_chunk(ps_ctx* c, int members) {
@@ -157,35 +267,36 @@ extern "C" int ps_msm_batch(ps_ctx* c, const ps_points* pts, const ps_scalars* s
         for (size_t j = 0; j < k; j++) write_identity(pts->group, out + j * wb);
         return PS_OK;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const MsmPlan one = msm_plan(n, sc->max_bits, c->forced_c);
-    const u64 pb = pts->group == PS_G1 ? sizeof(Xyzz<Fp>) : sizeof(Xyzz<Fp2>);
-    const BatchShape shape{(u64)n, (u64)one.W, (u64)one.NB, pb, (u64)(c->forced_slice ? c->forced_slice : 2)};
-    std::vector<BatchPass> passes;
-    if (!batch_passes((u64)k, shape, msm_batch_limits(c), &passes)) {
-        // not even one member fits a pass (n * W >= 2^31, or a forced window whose W * NB buckets exceed the sort's): one by one
-        for (size_t j = 0; j < k; j++) {
-            Scope scope;
-            ps_scalars** sl = scope.scalars();
-            int rc = ps_scalars_slice(sc, j * n, n, sl);
-            if (!rc) rc = ps_msm(c, pts, *sl, out + j * wb);
-            if (rc) return rc;
-        }
+    return msm_batch_run(c, &pts, 1, sc, k, n, 0, &out);
+}
+
+extern "C" int ps_msm_batch_multi(ps_ctx* c, const ps_points* const* pts, size_t a, const ps_scalars* sc, size_t k, size_t stride, size_t first,
+                                  uint8_t* const* out) {
+    if (!c || !sc || (a && (!pts || !out))) return fail(PS_ERR_ARG, "ps_msm_batch_multi: NULL argument");
+    if (a > PS_MSM_MULTI_MAX) return fail(PS_ERR_ARG, "ps_msm_batch_multi: more than PS_MSM_MULTI_MAX point arrays");
+    for (size_t i = 0; i < a; i++)
+        if (!pts[i] || (k && !out[i])) return fail(PS_ERR_ARG, "ps_msm_batch_multi: NULL argument");
+    if (c->q_len || c->pending || (c->aux && c->aux->pending))
+        return fail(PS_ERR_ARG, "ps_msm_batch_multi: sums are pending on this context (ps_msm_finish them first)");
+    if (a == 0) return PS_OK;
+    const size_t n = pts[0]->n;
+    for (size_t i = 1; i < a; i++)
+        if (pts[i]->n != n)  // algebra.go:350-352
+            return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(n) + " and blinded eval points " +
+                                           std::to_string(pts[i]->n));
+    if (first > stride || n > stride - first)
+        return fail(PS_ERR_LENGTH, "ps_msm_batch_multi: a member's range [" + std::to_string(first) + ", +" + std::to_string(n) +
+                                       ") does not lie within the stride " + std::to_string(stride));
+    if ((stride && k > (size_t)-1 / stride) || sc->n != k * stride)
+        return fail(PS_ERR_LENGTH, "mismatch of length between " + std::to_string(k) + " polys of stride " + std::to_string(stride) + " and " +
+                                       std::to_string(sc->n) + " scalars");
+    if (k == 0) return PS_OK;
+    if (n == 0) {
+        for (size_t i = 0; i < a; i++)
+            for (size_t j = 0; j < k; j++) write_identity(pts[i]->group, out[i] + j * wire_bytes(pts[i]->group));
         return PS_OK;
     }
-    if (storage_wait_ready(sc->st, c->stream)) return fail(PS_ERR_HIP, "ps_msm_batch: event wait failed");  // asynchronously produced scalars
-    int rc = PS_OK;
-    for (const BatchPass& p : passes) {
-        rc = pts->group == PS_G1 ? msm_batch_pass<Fp>(c, pts, sc, (size_t)p.first, (size_t)p.count, one, out)
-                                 : msm_batch_pass<Fp2>(c, pts, sc, (size_t)p.first, (size_t)p.count, one, out);
-        if (rc) break;
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PS_OK;
+    return msm_batch_run(c, pts, a, sc, k, stride, first, out);
 }
 
 // Measurement hook (tools/prove_batch_sweep.py; not in the header).  Of the last timed call on the context (ps_ctx_set_timing):

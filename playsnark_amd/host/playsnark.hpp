@@ -272,6 +272,18 @@ inline ps_phgr13_proof PHGR13Prove(Context& c, const ps_phgr13_ek& ek, const QAP
     return out;
 }
 
+// PHGR13Prove for each of the k witnesses of `sols` (k solution vectors of qap's variables back to back) under one evaluation key
+// that carries lgsi, in one call (ps_phgr13_prove_batch); proof j is byte for byte PHGR13Prove of witness j.
+// valid == nullptr: a witness that violates a gate throws Apocalypse; otherwise (*valid)[j] == 0 and proof j is all zero bytes
+inline std::vector<ps_phgr13_proof> PHGR13ProveBatch(Context& c, const ps_phgr13_ek& ek, const QAP& qap, const Poly& sols, size_t k,
+                                                     std::vector<int>* valid = nullptr) {
+    std::vector<ps_phgr13_proof> out(k + 1);
+    if (valid) valid->assign(k, 0);
+    check(ps_phgr13_prove_batch(c.get(), &ek, qap.get(), sols.get(), k, out.data(), valid && k ? valid->data() : nullptr));
+    out.resize(k);
+    return out;
+}
+
 // One rank's share of PHGR13Prove over the whole key; the ranks' eight elements add up (ps_points_sum) to the proof
 inline ps_phgr13_proof PHGR13ProveShard(Context& c, const ps_phgr13_ek& ek, const QAP& qap, const Poly& solution, int rank,
                                         int world) {
@@ -428,7 +440,28 @@ inline std::vector<Bytes> BlindEvalBatch(Context& c, const Points& points, const
     for (size_t j = 0; j < k; j++) out.emplace_back(flat.begin() + wb * j, flat.begin() + wb * (j + 1));
     return out;
 }
-// members per pass of BlindEvalBatch / Groth16ProveBatch (ps_msm_batch_set_chunk); 0: automatic
+// k scalar vectors over several point arrays (ps_msm_batch_multi): member j is scalars[j * stride + first, + n), n the arrays'
+// common length -- computeSolCommit (pinochio.go:222-241) for k solutions back to back with stride = the number of variables
+// and first = diff.  One digit sort per pass serves every array.  out[i][j] = the sum of member j over arrays[i]
+inline std::vector<std::vector<Bytes>> SolCommitsBatch(Context& c, const std::vector<const Points*>& arrays, const Poly& scalars, size_t k,
+                                                       size_t stride, size_t first = 0) {
+    std::vector<const ps_points*> pts;
+    std::vector<std::vector<uint8_t>> flat;
+    std::vector<uint8_t*> dst;
+    for (auto* a : arrays) {
+        pts.push_back(a->get());
+        flat.emplace_back((a->group() == PS_G1 ? 96 : 192) * k + 1);
+    }
+    for (auto& f : flat) dst.push_back(f.data());
+    check(ps_msm_batch_multi(c.get(), pts.data(), pts.size(), scalars.get(), k, stride, first, dst.data()));
+    std::vector<std::vector<Bytes>> out(arrays.size());
+    for (size_t i = 0; i < arrays.size(); i++) {
+        const size_t wb = arrays[i]->group() == PS_G1 ? 96 : 192;
+        for (size_t j = 0; j < k; j++) out[i].emplace_back(flat[i].begin() + wb * j, flat[i].begin() + wb * (j + 1));
+    }
+    return out;
+}
+// members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic
 inline void SetBatchChunk(Context& c, int members) { check(ps_msm_batch_set_chunk(c.get(), members)); }
 
 }  // namespace playsnark

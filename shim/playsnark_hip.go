@@ -1287,6 +1287,60 @@ func PHGR13ProveHIP(hp *HipPHGR13, solution Vector) PHGR13Proof {
 	}
 }
 
+// ToLagrange adds gsi's Lagrange form on the nodes n+1..2n-1 to the key (ps_phgr13_ek.lgsi), computed on the GPU from gsi
+// alone (ps_points_monomial_to_lagrange, once per key): hs is then a sum over the values of h, without interpolating it.
+// The proof bytes do not change.
+func (hp *HipPHGR13) ToLagrange() {
+	if hp.ek.lgsi != nil {
+		return
+	}
+	var lgsi *C.ps_points
+	call(func() C.int { return C.ps_points_monomial_to_lagrange(hipCtx, hp.qap.h, hp.ek.gsi, 1, &lgsi) })
+	hp.arrays = append(hp.arrays, lgsi)
+	hp.ek.lgsi = lgsi
+}
+
+// PHGR13ProveHIPBatch is PHGR13ProveHIP for many witnesses of ONE circuit under one key, in one call
+// (ps_phgr13_prove_batch): one pass of wire values and gate checks over all witnesses, the h sums as one batched sum and
+// the other seven elements of all proofs as one batched sum over seven arrays with one digit sort.  The route needs lgsi,
+// so a key that came from the reference's setup is converted first (ToLagrange, once per key).  Proof j is the proof
+// PHGR13ProveHIP makes of sols[j].  A witness that violates a gate panics with the reference's "apocalypse"
+// (qap.go:158-160).
+func PHGR13ProveHIPBatch(hp *HipPHGR13, sols []Vector) []PHGR13Proof {
+	k := len(sols)
+	if k == 0 {
+		return nil
+	}
+	hp.ToLagrange()
+	flat := make(Vector, 0, k*len(sols[0]))
+	for _, s := range sols {
+		if len(s) != len(sols[0]) {
+			panic("PHGR13ProveHIPBatch: the witnesses of one circuit have one length")
+		}
+		flat = append(flat, s...)
+	}
+	dsols := uploadSolution(flat)
+	defer C.ps_scalars_free(dsols)
+	raw := make([]C.ps_phgr13_proof, k)
+	call(func() C.int { return C.ps_phgr13_prove_batch(hipCtx, &hp.ek, hp.qap.h, dsols, C.size_t(k), &raw[0], nil) })
+	g1 := func(p *C.uint8_t) Commit { return pointFrom(C.PS_G1, bytesOf(unsafe.Pointer(p), g1Wire), zeroG1) }
+	out := make([]PHGR13Proof, k)
+	for j := range out {
+		o := &raw[j]
+		out[j] = PHGR13Proof{
+			vss:  g1(&o.vss[0]),
+			vass: g1(&o.vass[0]),
+			wss:  pointFrom(C.PS_G2, bytesOf(unsafe.Pointer(&o.wss[0]), g2Wire), zeroG2),
+			wass: g1(&o.wass[0]),
+			yss:  g1(&o.yss[0]),
+			yass: g1(&o.yass[0]),
+			hs:   g1(&o.hs[0]),
+			gz:   g1(&o.gz[0]),
+		}
+	}
+	return out
+}
+
 // PHGR13VerifyHIP replaces `func PHGR13Verify(vk PHGR13VerifKey, qap QAP, p PHGR13Proof, io Vector) bool`
 // (pinochio.go:281-378).
 func PHGR13VerifyHIP(hp *HipPHGR13, p PHGR13Proof, io Vector) bool {
