@@ -57,7 +57,7 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
  *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
  *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch;
- *      then ps_msm_batch_multi and ps_phgr13_prove_batch. */
+ *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -176,11 +176,24 @@ int ps_msm_multi(ps_ctx* ctx, const ps_points* const* points, size_t k, const ps
  * out[k] = sum_i scalars[k*n + i] * points[i],  n = ps_points_len(points),  ps_scalars_len(scalars) == k*n (PS_ERR_LENGTH
  * otherwise).  out: k * 96 (G1) / k * 192 (G2) bytes, the encoding ps_msm writes.  Byte-identical to k calls of ps_msm over
  * slices of `scalars`.  k == 0 or n == 0: PS_OK, identities.  (algebra.go:348-359, k times over one blindedPoint.)
- * A window table on `points` is ignored (same bytes with and without); ps_msm_set_window is honoured.  Needs an empty MSM
- * queue (PS_ERR_ARG otherwise).  A batch too large for one pass runs as several, invisibly; ps_msm_batch_set_chunk bounds
- * the members of a pass (0 = automatic).  A batch of which not even one member fits a pass is summed by ps_msm per member. */
+ * A window table on `points` changes the route, never the bytes (ps_msm_batch_set_table); ps_msm_set_window is honoured and
+ * means the plain plan with that window.  Needs an empty MSM queue (PS_ERR_ARG otherwise).  A batch too large for one pass
+ * runs as several, invisibly; ps_msm_batch_set_chunk bounds the members of a pass (0 = automatic).  A batch of which not
+ * even one member fits a pass is summed by ps_msm per member. */
 int ps_msm_batch(ps_ctx* ctx, const ps_points* points, const ps_scalars* scalars, size_t k, uint8_t* out);
 int ps_msm_batch_set_chunk(ps_ctx* ctx, int members /* sums per pass; 0 = automatic */);
+/* Whether ps_msm_batch, ps_msm_batch_multi and the batch provers sum over the window tables of their points
+ * (ps_points_precompute; the provers' cached keys): all windows of a member then share ONE bucket set -- a pass has k sets
+ * instead of k * W, wider windows, fewer digits, and the set sum is the member's result with no fold behind it.
+ *   0  automatic (the default): every array of the call carries a usable table of one window size (a table whose windows
+ *      cover the scalars, no forced window, n < 2^26), a member has at least 512 points, and the plain plan is not cheaper by
+ *      the margin ps_msm applies (an int64 witness over a 20-bit table stays plain)
+ *   1  never: the plain pass, k * W bucket sets and a fold per member
+ *   2  wherever the tables are usable and one member fits a pass (tests, A/B runs)
+ * The bytes are the same on every route.  ps_msm_last_info reports window_table = 1, the table's window_bits and windows, and
+ * buckets = (members of the last pass) * 2^(window_bits - 1) after a tabled pass.  Another mode: PS_ERR_ARG.
+ * Added within revision 5 (found by symbol, no existing struct changed). */
+int ps_msm_batch_set_table(ps_ctx* ctx, int mode);
 /* The product of the two: k scalar vectors over `a` point arrays, ONE digit sort per pass shared by all arrays (as in
  * ps_msm_multi) and one bucket problem of k * W bucket sets per array (as in ps_msm_batch).
  * out[i][j] = sum_{t<n} scalars[j*stride + first + t] * points[i][t],  i < a, j < k,  n = the common length of the arrays.
@@ -191,9 +204,10 @@ int ps_msm_batch_set_chunk(ps_ctx* ctx, int members /* sums per pass; 0 = automa
  * members -- are never read.
  * a <= PS_MSM_MULTI_MAX; a NULL array or a NULL out[i] is PS_ERR_ARG.  Arrays of different lengths: PS_ERR_LENGTH
  * (algebra.go:350-352); so are first + n > stride and ps_scalars_len(scalars) != k*stride.  a == 0 or k == 0: PS_OK;
- * n == 0: PS_OK, identities.  Needs an empty MSM queue (PS_ERR_ARG otherwise).  Window tables on the arrays are ignored;
- * ps_msm_set_window, ps_msm_set_slice, ps_msm_set_tail and ps_msm_batch_set_chunk are honoured as in ps_msm_batch, and a
- * batch of which not even one member fits a pass is summed by ps_msm per (array, member).
+ * n == 0: PS_OK, identities.  Needs an empty MSM queue (PS_ERR_ARG otherwise).  Window tables are summed over when every
+ * array carries a usable one of the same window size (ps_msm_batch_set_table); ps_msm_set_window, ps_msm_set_slice,
+ * ps_msm_set_tail and ps_msm_batch_set_chunk are honoured as in ps_msm_batch, and a batch of which not even one member fits
+ * a pass is summed by ps_msm per (array, member).
  * Each array's point pass, fold and encoding run on a workspace of their own (four rotate), so the folds of different arrays
  * -- serial chains of ~250 doublings each -- run side by side; every workspace is idle again when the call returns, on every
  * path.  Added within revision 5 (found by symbol, no existing struct changed). */

@@ -38,6 +38,7 @@ SYMBOLS = [
     "ps_msm_batch", "ps_msm_batch_set_chunk", "ps_groth16_prove_batch",
     "ps_msm_batch_multi", "ps_phgr13_prove_batch",
     "ps_msm_set_accumulate", "ps_msm_last_accumulate",
+    "ps_msm_batch_set_table",
 ]
 
 
@@ -177,6 +178,8 @@ def _load():
     lib.ps_msm_multi.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.POINTER(vp)]
     lib.ps_msm_batch.argtypes = [vp, vp, vp, sz, C.c_char_p]
     lib.ps_msm_batch_set_chunk.argtypes = [vp, i]
+    if hasattr(lib, "ps_msm_batch_set_table"):  # found by symbol, as ps_msm_set_accumulate below
+        lib.ps_msm_batch_set_table.argtypes = [vp, i]
     lib.ps_msm_batch_multi.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz, C.POINTER(vp)]
     lib.ps_points_sum.argtypes = [i, C.c_char_p, sz, C.c_char_p]
     lib.ps_point_convert.argtypes = [i, i, i, C.c_char_p, C.c_char_p]

@@ -96,6 +96,11 @@ class Context:
         """Members per pass of msm_batch / Groth16ProveBatch (ps_msm_batch_set_chunk); 0: automatic."""
         _check(lib.ps_msm_batch_set_chunk(self._h, members))
 
+    def set_batch_table(self, mode: int):
+        """Batched sums over the points' window tables, one bucket set per member (ps_msm_batch_set_table): 0 automatic,
+        1 never (the plain pass with its fold), 2 wherever the tables are usable."""
+        _check(lib.ps_msm_batch_set_table(self._h, mode))
+
     def set_tail(self, mode: int):
         """0 automatic, 1 chains (the long sums' tail), 2 trees of lane-cooperative additions (the short sums' tail)."""
         _check(lib.ps_msm_set_tail(self._h, mode))

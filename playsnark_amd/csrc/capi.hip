@@ -98,6 +98,7 @@ struct ps_ctx {
     DevBuf perm, border;  // buckets in order of size (beside offs, made by the sort) and [class histogram][class cursors][verdict, largest class, non-empty buckets] (bucket_order.hpp)
     DevBuf mb_fold, mb_out;  // ps_msm_batch: the members' folded sums (XYZZ + the chain products of k_batch_to_affine), then affine + wire bytes
     int batch_chunk = 0;     // ps_msm_batch_set_chunk: members per pass, 0 = automatic
+    int batch_table = 0;     // ps_msm_batch_set_table: 0 the tabled pass where the rule admits it, 1 never, 2 wherever a table is usable
     hipEvent_t mb_ev[2] = {nullptr, nullptr};  // timed contexts: around the fold, the normalisation and the encoding of a batch's last pass
     // ps_groth16_prove_batch (prove_batch.inc): the witnesses in Montgomery form [k][m], the wire values [3][k][n], and r_j, s_j,
     // r_j s_j with the gate flags behind them; stage events of the last timed call
@@ -1186,10 +1187,11 @@ static bool table_ref(const ps_points* pts, size_t n, int wbits, int W, TableRef
 // wait_acc: event the accumulation waits for; acc_done: recorded right after it.
 // dev_sets (ps_msm_batch only; NULL for every other caller, whose launches it does not touch): the set sums stay on the
 // device -- *dev_sets points at the pl.sets weighted sums in `wins`, nothing is copied to the pinned slot, and the number
-// of sets is not bound by that slot.  `n` is then the length of the virtual scalar array (members x points).
+// of sets is not bound by that slot.  `n` is then the length of the virtual scalar array (members x points), and
+// `member_n` (0: n) the length of one member -- the index range whose window table a tabled batch reads.
 template <class F>
 static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, const MsmPlan& pl, bool timed, int slot,
-                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr) {
+                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr, size_t member_n = 0) {
     typedef typename KernelField<F>::type KF;      // Fp -> Fp, Fp2 -> lane-split Fp2s
     constexpr unsigned LN = FieldTraits<KF>::LANES;  // lanes per logical thread
     const u64 total = (u64)pl.W * n;
@@ -1208,7 +1210,7 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     const bool tab = pl.table;
     const u32 pstride = tab ? (u32)table_row_bytes(pts->group) : (u32)sizeof(Affine<F>);
     TableRef tref{};
-    if (tab && !table_ref(pts, n, pl.c, pl.W, &tref)) return fail(PS_ERR_ARG, "msm: internal: the plan names a window table the array does not carry");
+    if (tab && !table_ref(pts, member_n ? member_n : n, pl.c, pl.W, &tref)) return fail(PS_ERR_ARG, "msm: internal: the plan names a window table the array does not carry");
     const char* src = tab ? tref.base : (const char*)points_ptr(pts);
     const u32 idx_mask = tab ? (1u << ENTRY_W_SHIFT) - 1u : 0x7fffffffu;
     const u64 w_stride = tab ? tref.stride : 0ull;

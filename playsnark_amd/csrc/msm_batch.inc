@@ -21,11 +21,11 @@ static BatchLimits msm_batch_limits(const ps_ctx* c) {
 //   shortsum  kc * n * W < PS_QTAIL_MAX_ENTRIES: slices as short as keep one wave per SIMD busy, and
 //   lpb       msm_plan_lpb's quads per cut bucket for that G (0, the one-lane k_fixup, from G * 4 (G1) / 8 (G2) > 2^17)
 // all through msm_plan_tail / msm_plan_lpb with n := kc * n; ps_msm_set_tail and ps_msm_set_slice apply as to a single sum.
-// No window table: a table forces one bucket set and tags the window into the entry.
+// Over a window table (`one` is msm_plan_table's: c and W the table's) a member is ONE bucket set: kc sets, G = kc * NB, the
+// same kc * n * W digits, and the same rules on them.
 static MsmPlan msm_batch_plan(const ps_ctx* c, const MsmPlan& one, size_t n, size_t kc, int group) {
     MsmPlan pl = one;
-    pl.table = false;
-    pl.sets = (int)(kc * (size_t)one.W);
+    pl.sets = (int)(one.table ? kc : kc * (size_t)one.W);
     pl.G = (u64)pl.sets * pl.NB;
     const u64 total = (u64)kc * n * (u64)pl.W;
     pl.M = 32;
@@ -36,6 +36,29 @@ static MsmPlan msm_batch_plan(const ps_ctx* c, const MsmPlan& one, size_t n, siz
     if (c->forced_slice) pl.M = c->forced_slice;
     if (pl.shortsum) msm_plan_lpb(pl, kc * n, group);
     return pl;
+}
+
+// ps_msm_batch_set_table: when a batch sums over the points' window tables (one bucket set per member, no fold).
+//   0  automatic: every array of the call carries a usable table of one window size (table_usable: a table, no forced window,
+//      n < 2^26, the scalars' windows within the table's -- msm_plan_checked's rule), a member has at least
+//      PS_BATCH_TABLE_MIN_POINTS points, and the plain plan is not cheaper by PS_TABLE_COST_MARGIN per member in the cost
+//      model (an int64 witness over a 20-bit table: 2^19 buckets to reduce for four windows -- msm_plan_checked's rule again)
+//   1  never (the plain pass)
+//   2  wherever the tables are usable
+// Returns the tables' window size, 0 for the plain pass.
+#ifndef PS_BATCH_TABLE_MIN_POINTS
+#define PS_BATCH_TABLE_MIN_POINTS 512  // shorter members have not been measured over tables (PHGR13's lgsi at 2^10 constraints: 1 023 points)
+#endif
+static int msm_batch_table_window(const ps_ctx* c, const ps_points* const* pts, size_t a, size_t n, int max_bits) {
+    if (c->batch_table == 1 || a == 0) return 0;
+    for (size_t i = 0; i < a; i++)
+        if (!table_usable(c, pts[i], n, max_bits) || pts[i]->st->table_c != pts[0]->st->table_c) return 0;
+    const int tc = pts[0]->st->table_c;
+    if (c->batch_table == 2) return tc;
+    if (n < PS_BATCH_TABLE_MIN_POINTS) return 0;
+    const MsmPlan plain = msm_plan(n, max_bits, 0);
+    const double cost_plain = (double)n * plain.W * 10.0 + (double)plain.G * 42.0;
+    return cost_plain < PS_TABLE_COST_MARGIN * table_plan_cost(n, max_bits, tc) ? 0 : tc;
 }
 
 // The two-level sort of msm_sort over the virtual array of kc * n scalars (msm_batch.hpp): member j's n scalars start at
@@ -75,13 +98,16 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, s
     if (may_have_big_bins) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 4 * G, st));
     const dim3 cgrid((unsigned)((N + (size_t)COUNT_PER_THREAD * DIGITS_THREADS - 1) / ((size_t)COUNT_PER_THREAD * DIGITS_THREADS)));
     const dim3 dgrid((unsigned)((N + DIGITS_CHUNK - 1) / DIGITS_CHUNK), (unsigned)pl.W);
-    hipLaunchKernelGGL(k_sort_count_batch, cgrid, dim3(DIGITS_THREADS), 0, st, scal, (u32)n, (u32)stride, (u32)N, pl.c, pl.W, pl.NB, cadd, fold_neg,
-                       ncoarse, fb, (u32*)c->ranks.p, coarse_cnt);
+    // over a window table the key is member * NB + digit and the entry names its window (msm_batch.hpp)
+    const auto k_count = pl.table ? k_sort_count_batch_tab : k_sort_count_batch;
+    const auto k_partition = pl.table ? k_sort_partition_batch_tab : k_sort_partition_batch;
+    hipLaunchKernelGGL(k_count, cgrid, dim3(DIGITS_THREADS), 0, st, scal, (u32)n, (u32)stride, (u32)N,
+                       pl.c, pl.W, pl.NB, cadd, fold_neg, ncoarse, fb, (u32*)c->ranks.p, coarse_cnt);
     PS_BATCH_MARK();  // 1: after digits + coarse histogram
     hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_MAX_COARSE), 0, st, (const u32*)coarse_cnt, ncoarse, coarse_off, coarse_cur,
                        (u32*)c->offs.p + G, tile_base);
-    hipLaunchKernelGGL(k_sort_partition_batch, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st, (const u32*)c->ranks.p, (u32)n,
-                       (u32)N, pl.W, pl.NB, fb, coarse_cur, (unsigned short*)c->keys.p, (u32*)c->vals.p);
+    hipLaunchKernelGGL(k_partition, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st,
+                       (const u32*)c->ranks.p, (u32)n, (u32)N, pl.W, pl.NB, fb, coarse_cur, (unsigned short*)c->keys.p, (u32*)c->vals.p);
     PS_BATCH_MARK();  // 2: after scan + partition
     hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p, (const u32*)c->vals.p,
                        (const u32*)coarse_off, (u32)G, fb, (u32*)c->offs.p, (u32*)c->sorted.p);
@@ -106,9 +132,9 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, s
 // (more arrays than workspaces) keeps every array's bytes until the copies at the end of the pass.
 struct BatchOut { size_t affine_bytes, slot_bytes; };
 
-// One array's share of a pass: the point pass over the sort that `c` owns (sorted / offs), the fold per member, the
-// normalisation and the encoding -- all on workspace wc's stream and in wc's buffers (wc == c: ps_msm_batch).  The kc * wb
-// wire bytes are left in slot `slot` of wc->mb_out.
+// One array's share of a pass: the point pass over the sort that `c` owns (sorted / offs), the fold per member (plain pass;
+// over a window table the set sums ARE the members' sums), the normalisation and the encoding -- all on workspace wc's
+// stream and in wc's buffers (wc == c: ps_msm_batch).  The kc * wb wire bytes are left in slot `slot` of wc->mb_out.
 template <class F>
 static int msm_batch_points(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, size_t kc, const MsmPlan& pl, bool timed,
                             const BatchOut& lay, size_t slot) {
@@ -117,14 +143,21 @@ static int msm_batch_points(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t 
     hipStream_t st = wc->stream;
     int rc;
     Xyzz<F>* dsets = nullptr;
-    if ((rc = msm_points_t<F>(c, wc, pts, kc * n, pl, timed, 0, nullptr, nullptr, true, &dsets))) return rc;
+    if ((rc = msm_points_t<F>(c, wc, pts, kc * n, pl, timed, 0, nullptr, nullptr, true, &dsets, n))) return rc;
     if (timed) {
         for (auto& e : c->mb_ev) if (!e) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipEventRecord(c->mb_ev[0], st));
     }
-    hipLaunchKernelGGL(k_batch_fold<KF>, dim3(nblocks(kc * LN)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, pl.W, pl.c,
-                       (Xyzz<F>*)wc->mb_fold.p);
-    batch_to_affine<F>(wc, (char*)wc->mb_fold.p, kc, (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+    if (pl.table) {
+        // batch_to_affine with the points where k_reduce_weights left them; mb_fold holds the chain products alone
+        const u32 T = (u32)std::min<size_t>(65536, std::max<size_t>(1, kc / 16));
+        hipLaunchKernelGGL(k_batch_to_affine<F>, dim3(nblocks(T)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, T, (Fp*)wc->mb_fold.p,
+                           (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+    } else {
+        hipLaunchKernelGGL(k_batch_fold<KF>, dim3(nblocks(kc * LN)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, pl.W, pl.c,
+                           (Xyzz<F>*)wc->mb_fold.p);
+        batch_to_affine<F>(wc, (char*)wc->mb_fold.p, kc, (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+    }
     uint8_t* d_bytes = (uint8_t*)wc->mb_out.p + lay.affine_bytes + slot * lay.slot_bytes;
     if (pts->group == PS_G1)
         hipLaunchKernelGGL(k_points_to_bytes_g1, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp>*)wc->mb_out.p, (u32)kc, d_bytes);
@@ -192,7 +225,7 @@ static int msm_batch_pass(ps_ctx* c, ps_ctx* const* ring, const ps_points* const
     // the results of this pass are read and the tails' buffers free before the next pass reuses them (same streams), and the
     // workspaces' other users order themselves behind ev_tail_done as behind any sum
     for (size_t j = 0; j < used; j++) HIP_TRY(hipEventRecord(ring[j]->ev_tail_done, ring[j]->stream));
-    c->last_info = ps_msm_info{pl.c, pl.W, 0, pl.G, pl.M, 0};
+    c->last_info = ps_msm_info{pl.c, pl.W, 0, pl.G, pl.M, pl.table ? 1 : 0};
     return PS_OK;
 }
 
@@ -216,12 +249,25 @@ static int msm_batch_run(ps_ctx* c, const ps_points* const* pts, size_t a, const
     for (size_t i = 0; i < a; i++) (pts[i]->group == PS_G1 ? any_g1 : any_g2) = true;
     const int plan_group = any_g2 ? PS_G2 : PS_G1;  // the tail is sized for the group whose points take more lanes (msm_plan_checked)
     HIP_TRY(hipSetDevice(c->device));
-    const MsmPlan one = msm_plan(n, sc->max_bits, c->forced_c);
     const u64 pb = batch_multi_point_bytes(any_g1, any_g2, sizeof(Xyzz<Fp>), sizeof(Xyzz<Fp2>));
-    const BatchShape shape{(u64)n, (u64)one.W, (u64)one.NB, pb, (u64)(c->forced_slice ? c->forced_slice : 2)};
+    const u64 min_slice = (u64)(c->forced_slice ? c->forced_slice : 2);
     std::vector<BatchPass> passes;
-    if (!batch_multi_passes((u64)k, shape, msm_batch_limits(c), (u64)stride, &passes)) {
-        // not even one member fits a pass (n * W >= 2^31, or a forced window whose W * NB buckets exceed the sort's): one by one
+    MsmPlan one{};
+    bool fits = false;
+    // over the tables where the route is admitted; a table whose window leaves no room for even one member in a pass (22 bits:
+    // 2^21 buckets) falls through to the plain route
+    if (const int tc = msm_batch_table_window(c, pts, a, n, sc->max_bits)) {
+        one = msm_plan_table(n, sc->max_bits, tc);
+        const BatchShape shape{(u64)n, (u64)one.W, (u64)one.NB, pb, min_slice, 1};
+        fits = batch_multi_passes((u64)k, shape, msm_batch_limits(c), (u64)stride, &passes);
+    }
+    if (!fits) {
+        one = msm_plan(n, sc->max_bits, c->forced_c);
+        const BatchShape shape{(u64)n, (u64)one.W, (u64)one.NB, pb, min_slice};
+        fits = batch_multi_passes((u64)k, shape, msm_batch_limits(c), (u64)stride, &passes);
+    }
+    if (!fits) {
+        // not even one member fits a plain pass (n * W >= 2^31, or a forced window whose W * NB buckets exceed the sort's): one by one
         for (size_t i = 0; i < a; i++)
             for (size_t j = 0; j < k; j++) {
                 Scope scope;
@@ -251,6 +297,13 @@ static int msm_batch_run(ps_ctx* c, const ps_points* const* pts, size_t a, const
 extern "C" int ps_msm_batch_set_chunk(ps_ctx* c, int members) {
     if (!c || members < 0) return fail(PS_ERR_ARG, "ps_msm_batch_set_chunk: members per pass must be 0 (automatic) or positive");
     c->batch_chunk = members;
+    return PS_OK;
+}
+
+extern "C" int ps_msm_batch_set_table(ps_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2)
+        return fail(PS_ERR_ARG, "ps_msm_batch_set_table: mode must be 0 (automatic), 1 (never over window tables) or 2 (wherever a table is usable)");
+    c->batch_table = mode;
     return PS_OK;
 }
 
@@ -300,14 +353,16 @@ extern "C" int ps_msm_batch_multi(ps_ctx* c, const ps_points* const* pts, size_t
 }
 
 // Measurement hook (tools/prove_batch_sweep.py; not in the header).  Of the last timed call on the context (ps_ctx_set_timing):
-// ms[0] the fold, normalisation and encoding of the last pass of the last ps_msm_batch; of the last ps_groth16_prove_batch
+// ms[0] the fold (plain pass only), normalisation and encoding of the last pass of the last ps_msm_batch; of the last ps_groth16_prove_batch
 // ms[1] wire values + gate check + scalar rows, ms[2] the h values, ms[3..5] the sums B, A, C.  Stages that did not run: -1.
 extern "C" int ps_debug_batch_stage_ms(ps_ctx* c, float* ms) {
     if (!c || !ms) return fail(PS_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     for (int i = 0; i < 6; i++) ms[i] = -1.f;
     if (c->mb_ev[0] && c->mb_ev[1] && c->ev_valid) HIP_TRY(hipEventElapsedTime(&ms[0], c->mb_ev[0], c->mb_ev[1]));
-    if (c->pb_timed)
+    if (c->pb_timed) {
+        HIP_TRY(hipEventSynchronize(c->pb_ev[5]));  // recorded behind the call's last synchronisation
         for (int i = 0; i < 5; i++) HIP_TRY(hipEventElapsedTime(&ms[1 + i], c->pb_ev[i], c->pb_ev[i + 1]));
+    }
     return PS_OK;
 }

@@ -10,8 +10,9 @@
 //      (stride m, first diff: plain limbs already, nothing is copied, the IO part of a witness is never read)
 // all on the context stream but for the point passes and folds of step 3, which rotate over the context's workspaces.  The
 // solution sums do not depend on h; they are nevertheless started behind the h sum: the h values occupy the chip with NTT
-// passes, and a sort that shares the chip waits for CUs (prove_shares.inc, phgr13_share_sums).  The window tables of the
-// single prover are not built or used: a batch pass has no use for them (msm_batch.inc).
+// passes, and a sort that shares the chip waits for CUs (prove_shares.inc, phgr13_share_sums).  The window tables are
+// those of the single prover (prove_shares.inc: lgsi, the six solution arrays and the beta sum; a table that finds no room is
+// no error), and both sums run over them where ps_msm_batch_set_table admits it (msm_batch.inc).
 
 extern "C" int ps_phgr13_prove_batch(ps_ctx* c, const ps_phgr13_ek* ek, const ps_qap* q, const ps_scalars* sols, size_t k, ps_phgr13_proof* out,
                                      int* valid) {
@@ -38,6 +39,10 @@ extern "C" int ps_phgr13_prove_batch(ps_ctx* c, const ps_phgr13_ek* ek, const ps
     HIP_TRY(hipSetDevice(c->device));
     const auto t_start = std::chrono::steady_clock::now();
     if (nn && (rc = phgr13_beta_sum(c, ek))) return rc;
+    // the tables ps_phgr13_prove asks for, each by the length of the sum that reads it: the h sum of a batch runs over the
+    // whole of lgsi however few solution entries the circuit has (nn = 3 for a circuit of three IO variables)
+    if (nn && tables_wanted(c, nn) && (rc = phgr13_solution_tables(c, ek))) return rc;
+    if (tables_wanted(c, ek->lgsi->n) && (rc = phgr13_h_table(c, ek->lgsi))) return rc;
     ps_scalars* H = nullptr;  // the context's own (prover_vector): not freed here
     if ((rc = prover_vector(c, 3, k * (n - 1), &H))) return rc;
     if ((rc = c->pb_x.ensure(sizeof(Fr) * k * m)) || (rc = c->pb_y.ensure(sizeof(Fr) * 3 * k * n)) || (rc = c->pb_small.ensure(4 * k))) return rc;

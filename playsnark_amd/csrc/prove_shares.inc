@@ -148,17 +148,28 @@ static int phgr13_beta_sum(ps_ctx* c, const ps_phgr13_ek* ek) {
     return PS_OK;
 }
 
-// Once per key, for a prover that sums `cnt` (> 0) solution entries over ek's arrays: the beta sum, and -- evaluation-key
-// arrays are fixed across proofs -- the window tables of the seven arrays and of hp (gsi or lgsi).  Shared keys: a table is
-// built once, under the array's lock; no room for one: plain plan.  Views of these arrays get tables of their own.
+// The window tables of a PHGR13 key, built once whoever asks first (evaluation-key arrays are fixed across proofs; shared
+// keys: under the array's lock) and optional: no room for one is no error, the sums over that array take the plain plan.
+// Views of these arrays get tables of their own.  The seven solution arrays (the beta sum made: phgr13_beta_sum) ...
+static int phgr13_solution_tables(ps_ctx* c, const ps_phgr13_ek* ek) {
+    const ps_points* arr[7] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, c->phgr_bsum};
+    int rc = PS_OK;
+    for (int i = 0; i < 7 && !rc; i++) rc = points_ensure_table(c, arr[i], 0, true);
+    return rc;
+}
+// ... and hp (gsi or lgsi), from PS_TABLE_MIN_POINTS points on
+static int phgr13_h_table(ps_ctx* c, const ps_points* hp) {
+    return hp->n >= PS_TABLE_MIN_POINTS ? points_ensure_table(c, hp, 0, true) : PS_OK;
+}
+
+// Once per key, for a prover that sums `cnt` (> 0) solution entries over ek's arrays: the beta sum, and the window tables of
+// the seven arrays and of hp.
 static int phgr13_prepare(ps_ctx* c, const ps_phgr13_ek* ek, size_t cnt, const ps_points* hp) {
     if (!cnt) return PS_OK;
     int rc = phgr13_beta_sum(c, ek);
     if (rc || !tables_wanted(c, cnt)) return rc;
-    const ps_points* arr[7] = {ek->vs, ek->ws, ek->ys, ek->vas, ek->was, ek->yas, c->phgr_bsum};
-    for (int i = 0; i < 7 && !rc; i++) rc = points_ensure_table(c, arr[i], 0, true);
-    if (!rc && hp->n >= PS_TABLE_MIN_POINTS) rc = points_ensure_table(c, hp, 0, true);
-    return rc;
+    if ((rc = phgr13_solution_tables(c, ek))) return rc;
+    return phgr13_h_table(c, hp);
 }
 
 // After quotient_run on c: h[first, first + cnt) as plain limbs into the context's own vector (slot 3: not freed by the

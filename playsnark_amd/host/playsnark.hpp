@@ -463,5 +463,7 @@ inline std::vector<std::vector<Bytes>> SolCommitsBatch(Context& c, const std::ve
 }
 // members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic
 inline void SetBatchChunk(Context& c, int members) { check(ps_msm_batch_set_chunk(c.get(), members)); }
+// batched sums over the points' window tables (ps_msm_batch_set_table): 0 automatic, 1 never, 2 wherever the tables are usable
+inline void SetBatchTable(Context& c, int mode) { check(ps_msm_batch_set_table(c.get(), mode)); }
 
 }  // namespace playsnark

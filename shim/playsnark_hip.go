@@ -574,6 +574,12 @@ func Groth16ProveBatchHIP(hs *HipGroth16, sols []Vector) []Groth16Proof {
 	return out
 }
 
+// SetBatchTableHIP says whether the batched sums (BlindEvalBatchHIP, the batch provers) run over the window tables of their
+// points, one bucket set per member (ps_msm_batch_set_table): 0 automatic, 1 never, 2 wherever the tables are usable.
+func SetBatchTableHIP(mode int) {
+	call(func() C.int { return C.ps_msm_batch_set_table(hipCtx, C.int(mode)) })
+}
+
 // BlindEvalBatchHIP is BlindEvalHIP for k polynomials over ONE array of blinded points, as one bucket problem on the
 // device (ps_msm_batch): out[j] = polys[j].BlindEval(zero, crs).
 func BlindEvalBatchHIP(polys []Poly, zero Commit, crs *C.ps_points) []Commit {

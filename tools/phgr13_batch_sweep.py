@@ -11,6 +11,9 @@ calls that end in a device synchronise.
   multi   at one (n, K): ps_msm_batch_multi over the key's seven arrays (six G1, one G2; stride m, first diff) against seven
           ps_msm_batch calls over the same members packed back to back -- what the shared sort and the side-by-side folds are
           worth -- and against one ps_msm_multi per member (the single prover's sum)
+--modes M [M ...]: ps_msm_batch_set_table modes of the batch prover (0 automatic, 1 never over window tables, 2 wherever a
+table is usable), alternated with each other and with the loop inside every repetition; `--modes 1 0` is the A/B of the tabled
+pass (profiles/phgr13_prove_batch_table.txt).
 Witnesses: the tiled synthetic circuit with up to 8 values of x0, repeated to K (the work does not depend on whether
 witnesses repeat: every member has its own bucket sets)."""
 import argparse
@@ -35,8 +38,31 @@ def _timed(fn):
     return (time.perf_counter() - t) * 1e3
 
 
+def _set_mode(ctx, mode):
+    """ps_msm_batch_set_table; an older build named by PLAYSNARK_HIP_LIB has no such entry and only the plain pass (mode 1)."""
+    if hasattr(_lib.lib, "ps_msm_batch_set_table"):
+        ctx.set_batch_table(mode)
+    elif mode != 1:
+        raise SystemExit("this library build has no ps_msm_batch_set_table: --modes 1 only")
+
+
 def _stat(v):
     return f"{statistics.median(v):9.4f} ({min(v):.4f} .. {max(v):.4f})"
+
+
+def _ab_modes(ctx, modes, batch, loop, reps):
+    """{mode: times of the batch}, times of the loop: every repetition runs the batch once per mode, then the loop."""
+    tb, tl = {m: [] for m in modes}, []
+    for rep in range(reps + 1):  # the first round is the warm-up
+        for m in modes:
+            _set_mode(ctx, m)
+            t = _timed(batch)
+            if rep:
+                tb[m].append(t)
+        t = _timed(loop)
+        if rep:
+            tl.append(t)
+    return tb, tl
 
 
 def _ab(batch, loop, reps):
@@ -52,7 +78,7 @@ def _fields(p):
     return tuple(getattr(p, f) for f in api.PHGR13Proof.FIELDS)
 
 
-def rows_for(ctx, rng, log2n, ks, reps, multi_k):
+def rows_for(ctx, rng, log2n, ks, reps, multi_k, modes):
     n = 1 << log2n
     distinct = min(8, max(ks))
     made = [rs.synthetic_circuit(n, x0=3 + 2 * j) for j in range(distinct)]
@@ -73,17 +99,22 @@ def rows_for(ctx, rng, log2n, ks, reps, multi_k):
         def loop():
             out["l"] = [api.PHGR13Prove(ek, q, singles[j % distinct]) for j in range(kl)]
 
-        tb, tl = _ab(batch, loop, reps)
-        same = all(_fields(out["b"][j]) == _fields(out["l"][j]) for j in range(kl))
-        batch()
-        ph = ctx.last_prove_phase_ms()
-        info = ctx.last_msm_info()
-        pb, pl = [t / k for t in tb], [t / kl for t in tl]
-        wins = all(b < min(pl) for b in pb)
-        print(f"prove 2^{log2n:<2d} K={k:<4d} batch ms/proof {_stat(pb)} | loop ms/proof {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
-              f" | every batch rep below every loop rep {wins} | same bytes {same} | last batch, host ms: wires+hvals {ph['quotient']:.3f}"
-              f" hs {ph['prep_or_h_sum']:.3f} sums {ph['sums']:.3f} total {ph['total']:.3f}"
-              f" (sums: c = {info['window_bits']}, {info['buckets']} buckets in the last pass, slices of {info['slice']})", flush=True)
+        tb, tl = _ab_modes(ctx, modes, batch, loop, reps)
+        pl = [t / kl for t in tl]
+        for mode in modes:
+            _set_mode(ctx, mode)
+            batch()
+            same = all(_fields(out["b"][j]) == _fields(out["l"][j]) for j in range(kl))
+            ph = ctx.last_prove_phase_ms()
+            info = ctx.last_msm_info()
+            pb = [t / k for t in tb[mode]]
+            wins = all(b < min(pl) for b in pb)
+            print(f"prove 2^{log2n:<2d} K={k:<4d} mode {mode} batch ms/proof {_stat(pb)} | loop ms/proof {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
+                  f" | every batch rep below every loop rep {wins} | same bytes {same} | last batch, host ms: wires+hvals {ph['quotient']:.3f}"
+                  f" hs {ph['prep_or_h_sum']:.3f} sums {ph['sums']:.3f} total {ph['total']:.3f}"
+                  f" (sums: table {info['window_table']}, c = {info['window_bits']}, {info['buckets']} buckets in the last pass, slices of {info['slice']};"
+                  f" lgsi table window {ek.lgsi.table_window})", flush=True)
+        _set_mode(ctx, modes[-1])
         if k == multi_k:
             arrays = [getattr(ek, f) for f in ARRAYS]
             nn = len(arrays[0])
@@ -119,13 +150,14 @@ def main():
     ap.add_argument("--log2n", type=int, nargs="*", default=[10, 12, 14, 16])
     ap.add_argument("--k", type=int, nargs="*", default=[1, 8, 64, 256])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--modes", type=int, nargs="+", default=[0], choices=[0, 1, 2], help="ps_msm_batch_set_table modes to alternate")
     ap.add_argument("--multi-at", type=int, nargs=2, default=[10, 64], metavar=("LOG2N", "K"), help="where the sum alone is compared")
     args = ap.parse_args()
     ctx = api.Context(0)
     rng = pr.SplitMix64(0x9468713)
-    print(f"# library {os.path.basename(_lib.library_path())}; {args.reps} repetitions, median (min .. max); loops over at most {LOOP_MAX} members", flush=True)
+    print(f"# library {os.path.basename(_lib.library_path())}; {args.reps} repetitions, median (min .. max); ps_msm_batch_set_table modes {args.modes}; loops over at most {LOOP_MAX} members", flush=True)
     for ln in args.log2n:
-        rows_for(ctx, rng, ln, args.k, args.reps, args.multi_at[1] if ln == args.multi_at[0] else -1)
+        rows_for(ctx, rng, ln, args.k, args.reps, args.multi_at[1] if ln == args.multi_at[0] else -1, args.modes)
     ctx.close()
 
 

@@ -11,6 +11,10 @@ calls that end in a device synchronise.
             (k_batch_fold, k_batch_to_affine, encoding)
   msm     ps_msm_batch of K vectors of n uniform 254-bit scalars over n points, G1 and G2, ms per member, against a loop of
           ps_msm over slices (min(K, 64) members)
+--modes M [M ...]: ps_msm_batch_set_table modes of the batch (0 automatic, 1 never over window tables -- the plain pass --, 2
+wherever a table is usable), alternated with each other and with the loop inside every repetition; one column set per mode.
+`--modes 1 0` is the A/B of the tabled pass (profiles/prove_batch_table.txt); `--tables` precomputes the automatic window
+table on the points of the msm rows (the provers' keys carry theirs anyway).
 Witnesses: the tiled synthetic circuit with up to 8 values of x0, repeated to K (the work does not depend on whether
 witnesses repeat: every member has its own bucket sets)."""
 import argparse
@@ -37,20 +41,34 @@ def _timed(fn):
     return (time.perf_counter() - t) * 1e3
 
 
+def _set_mode(ctx, mode):
+    """ps_msm_batch_set_table; an older build named by PLAYSNARK_HIP_LIB has no such entry and only the plain pass (mode 1)."""
+    if hasattr(_lib.lib, "ps_msm_batch_set_table"):
+        ctx.set_batch_table(mode)
+    elif mode != 1:
+        raise SystemExit("this library build has no ps_msm_batch_set_table: --modes 1 only")
+
+
 def _stat(v):
     return f"{statistics.median(v):9.4f} ({min(v):.4f} .. {max(v):.4f})"
 
 
-def _ab(batch, loop, reps):
-    batch(); loop()  # warm: buffers sized, code objects loaded
-    tb, tl = [], []
-    for _ in range(reps):
-        tb.append(_timed(batch))
-        tl.append(_timed(loop))
+def _ab(ctx, modes, batch, loop, reps):
+    """{mode: times of the batch}, times of the loop: every repetition runs the batch once per mode, then the loop."""
+    tb, tl = {m: [] for m in modes}, []
+    for rep in range(reps + 1):  # the first round is the warm-up: buffers sized, code objects loaded, tables built
+        for m in modes:
+            _set_mode(ctx, m)
+            t = _timed(batch)
+            if rep:
+                tb[m].append(t)
+        t = _timed(loop)
+        if rep:
+            tl.append(t)
     return tb, tl
 
 
-def prove_rows(ctx, rng, log2n, ks, reps):
+def prove_rows(ctx, rng, log2n, ks, reps, modes):
     n = 1 << log2n
     distinct = min(8, max(ks))
     made = [rs.synthetic_circuit(n, x0=3 + 2 * j) for j in range(distinct)]
@@ -71,29 +89,35 @@ def prove_rows(ctx, rng, log2n, ks, reps):
         def loop():
             out["l"] = [api.Groth16Prove(tr, q, singles[j % distinct], rr[j], ss[j]) for j in range(kl)]
 
-        tb, tl = _ab(batch, loop, reps)
-        same = all((out["b"][j].A, out["b"][j].B, out["b"][j].C) == (out["l"][j].A, out["l"][j].B, out["l"][j].C) for j in range(kl))
-        ctx.set_timing(True)
-        batch()
-        ms = (C.c_float * 6)()
-        _lib.lib.ps_debug_batch_stage_ms(ctx._h, ms)
-        st = ctx.last_stage_ms()
-        ctx.set_timing(False)
-        pb, pl = [t / k for t in tb], [t / kl for t in tl]
-        print(f"prove 2^{log2n:<2d} K={k:<4d} batch ms/proof {_stat(pb)} | loop ms/proof {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
-              f" | same bytes {same} | timed batch, ms: wires {ms[1]:.3f} hvals {ms[2]:.3f} B {ms[3]:.3f} A {ms[4]:.3f} C {ms[5]:.3f}; last pass of C:"
-              f" sort {st['digits'] + st['scan'] + st['scatter']:.3f} acc {st['accumulate']:.3f} tail {st['fixup'] + st['reduce']:.3f} fold {ms[0]:.3f}"
-              f" (c = {ctx.last_msm_info()['window_bits']}, {ctx.last_msm_info()['buckets']} buckets, slices of {ctx.last_msm_info()['slice']})", flush=True)
+        tb, tl = _ab(ctx, modes, batch, loop, reps)
+        pl = [t / kl for t in tl]
+        for mode in modes:
+            _set_mode(ctx, mode)
+            ctx.set_timing(True)
+            batch()
+            same = all((out["b"][j].A, out["b"][j].B, out["b"][j].C) == (out["l"][j].A, out["l"][j].B, out["l"][j].C) for j in range(kl))
+            ms = (C.c_float * 6)()
+            _lib.lib.ps_debug_batch_stage_ms(ctx._h, ms)
+            st = ctx.last_stage_ms()
+            ctx.set_timing(False)
+            info = ctx.last_msm_info()
+            pb = [t / k for t in tb[mode]]
+            print(f"prove 2^{log2n:<2d} K={k:<4d} mode {mode} batch ms/proof {_stat(pb)} | loop ms/proof {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
+                  f" | same bytes {same} | timed batch, ms: wires {ms[1]:.3f} hvals {ms[2]:.3f} B {ms[3]:.3f} A {ms[4]:.3f} C {ms[5]:.3f}; last pass of C:"
+                  f" sort {st['digits'] + st['scan'] + st['scatter']:.3f} acc {st['accumulate']:.3f} tail {st['fixup'] + st['reduce']:.3f} fold+encode {ms[0]:.3f}"
+                  f" (table {info['window_table']}, c = {info['window_bits']}, {info['buckets']} buckets, slices of {info['slice']})", flush=True)
         sols.free()
     for s in singles:
         s.free()
     q.free()
 
 
-def msm_rows(ctx, rng, log2n, ks, reps, group, gname):
+def msm_rows(ctx, rng, log2n, ks, reps, group, gname, modes, tables):
     n = 1 << log2n
     gen = np.random.default_rng(log2n)
     pts = api.Points.from_scalars(ctx, group, api.Poly.upload(ctx, [rng.fr() for _ in range(n)]))
+    if tables:
+        pts.precompute()
     for k in ks:
         raw = gen.integers(0, 256, size=(k * n, 32), dtype=np.uint8)
         raw[:, 0] &= 0x3F  # below r
@@ -108,12 +132,15 @@ def msm_rows(ctx, rng, log2n, ks, reps, group, gname):
         def loop():
             out["l"] = [s.BlindEval(pts) for s in slices]
 
-        tb, tl = _ab(batch, loop, reps)
-        batch()  # (the loop ran last: the plan of the batch's last pass)
-        info = ctx.last_msm_info()
-        pb, pl = [t / k for t in tb], [t / kl for t in tl]
-        print(f"msm {gname} 2^{log2n:<2d} K={k:<4d} batch ms/member {_stat(pb)} | loop ms/member {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
-              f" | same bytes {out['b'][:kl] == out['l']} | last pass: c = {info['window_bits']}, {info['buckets']} buckets, slices of {info['slice']}", flush=True)
+        tb, tl = _ab(ctx, modes, batch, loop, reps)
+        pl = [t / kl for t in tl]
+        for mode in modes:
+            _set_mode(ctx, mode)
+            batch()  # (the loop ran last: the plan of the batch's last pass)
+            info = ctx.last_msm_info()
+            pb = [t / k for t in tb[mode]]
+            print(f"msm {gname} 2^{log2n:<2d} K={k:<4d} mode {mode} batch ms/member {_stat(pb)} | loop ms/member {_stat(pl)} | loop/batch {statistics.median(pl) / statistics.median(pb):6.2f}x"
+                  f" | same bytes {out['b'][:kl] == out['l']} | last pass: table {info['window_table']}, c = {info['window_bits']}, {info['buckets']} buckets, slices of {info['slice']}", flush=True)
         for s in slices:
             s.free()
         sc.free()
@@ -126,16 +153,20 @@ def main():
     ap.add_argument("--k", type=int, nargs="*", default=[1, 8, 64, 256])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-msm", action="store_true")
+    ap.add_argument("--skip-prove", action="store_true")
+    ap.add_argument("--modes", type=int, nargs="+", default=[0], choices=[0, 1, 2], help="ps_msm_batch_set_table modes to alternate")
+    ap.add_argument("--tables", action="store_true", help="window tables on the points of the msm rows")
     args = ap.parse_args()
     ctx = api.Context(0)
     rng = pr.SplitMix64(0xBA7C4)
-    print(f"# library {os.path.basename(_lib.library_path())}; {args.reps} repetitions, median (min .. max); loops over at most {LOOP_MAX} members", flush=True)
-    for ln in args.log2n:
-        prove_rows(ctx, rng, ln, args.k, args.reps)
+    print(f"# library {os.path.basename(_lib.library_path())}; {args.reps} repetitions, median (min .. max); ps_msm_batch_set_table modes {args.modes}; loops over at most {LOOP_MAX} members", flush=True)
+    if not args.skip_prove:
+        for ln in args.log2n:
+            prove_rows(ctx, rng, ln, args.k, args.reps, args.modes)
     if not args.skip_msm:
         for ln in args.log2n:
-            msm_rows(ctx, rng, ln, args.k, args.reps, api.G1, "G1")
-            msm_rows(ctx, rng, ln, args.k, args.reps, api.G2, "G2")
+            msm_rows(ctx, rng, ln, args.k, args.reps, api.G1, "G1", args.modes, args.tables)
+            msm_rows(ctx, rng, ln, args.k, args.reps, api.G2, "G2", args.modes, args.tables)
     ctx.close()
 
 
