@@ -50,7 +50,9 @@ static int fail(int code, const std::string& msg) {
 #include "scope.hpp"  // Scope, KeepError: what a call makes along the way, released on every way out
 
 extern "C" const char* ps_last_error(void) { return g_last_error.c_str(); }
-extern "C" const char* ps_version(void) { return "playsnark_hip 0.4 (gfx950), ABI 4"; }
+#define PS_STR_(x) #x
+#define PS_STR(x) PS_STR_(x)
+extern "C" const char* ps_version(void) { return "playsnark_hip 0.4 (gfx950), ABI " PS_STR(PS_ABI_VERSION); }
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 extern "C" int ps_device_count(void) {
     int n = 0;
@@ -61,14 +63,16 @@ extern "C" int ps_device_count(void) {
 // ---------------------------------------------------------------------------------------
 // handles
 // ---------------------------------------------------------------------------------------
-struct DevBuf {
+struct DevBuf {  // a device buffer its holder owns: grown on demand, freed with the holder
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return PS_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         size_t want = bytes + bytes / 8 + 256;
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) return fail(PS_ERR_HIP, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
@@ -84,7 +88,10 @@ struct DevBuf {
 
 constexpr size_t PS_PINNED_SLOT = 64 * sizeof(Xyzz<Fp2>) + 16;  // what the host folds: window sums (W <= 64) or one set's partial results (<= 21), then the entry count of a short sum
 
-struct ps_ctx {
+// What one sum runs on: two streams, the events that order them, the device buffers of the sort and of the point pass, the
+// pinned buffer its results come back in, and the stage events of a timed sum.  A context is its own first workspace
+// (ps_ctx below derives from this) and keeps PS_WORKERS more for sums that run beside each other.
+struct MsmWorkspace {
     int device = 0;
     hipStream_t stream = nullptr;
     // The latency-bound tail of a sum (fix-up, reduction, copy of the window sums) runs on its own
@@ -93,10 +100,57 @@ struct ps_ctx {
     hipStream_t tail = nullptr;
     hipEvent_t ev_acc_local = nullptr, ev_tail_done = nullptr, ev_sort_local = nullptr;
     bool tail_used = false;
-    // MSM workspace
     DevBuf counts, offs, bsum, keys, ranks, vals, sorted, buckets, parts, segs, wins, heavy, hparts, coarse;
     DevBuf perm, border;  // buckets in order of size (beside offs, made by the sort) and [class histogram][class cursors][verdict, largest class, non-empty buckets] (bucket_order.hpp)
     DevBuf mb_fold, mb_out;  // ps_msm_batch: the members' folded sums (XYZZ + the chain products of k_batch_to_affine), then affine + wire bytes
+    void* h_pinned = nullptr;        // pinned host scratch for window sums
+    size_t h_pinned_cap = 0;
+    // per-stage timing of the sum that ran here last (HIP events on the streams its kernels ran on; ps_ctx_set_timing)
+    hipEvent_t ev[PS_MSM_STAGES + 1] = {};
+    bool ev_valid = false;
+    ~MsmWorkspace() { destroy(); }  // (not copyable: its DevBufs are not)
+    bool created() const { return stream != nullptr; }
+    int create(int dev) {  // all of it or, on an error, nothing
+        const int rc = [&]() -> int {
+            device = dev;
+            HIP_TRY(hipSetDevice(device));
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            int least = 0, greatest = 0;
+            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIP_TRY(hipStreamCreateWithPriority(&tail, hipStreamNonBlocking, greatest));
+            HIP_TRY(hipEventCreateWithFlags(&ev_acc_local, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&ev_tail_done, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&ev_sort_local, hipEventDisableTiming));
+            h_pinned_cap = PS_MSM_MULTI_MAX * PS_PINNED_SLOT + 64;
+            HIP_TRY(hipHostMalloc(&h_pinned, h_pinned_cap));
+            for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+            return PS_OK;
+        }();
+        if (rc) destroy();
+        return rc;
+    }
+    int sync() {
+        HIP_TRY(hipSetDevice(device));
+        for (hipStream_t s : {stream, tail}) HIP_TRY(hipStreamSynchronize(s));
+        return PS_OK;
+    }
+    // waits for what is in flight, then releases whatever of the above exists (a create that failed half way); the buffers go with the object
+    void destroy() {
+        for (hipStream_t s : {stream, tail}) if (s) (void)hipStreamSynchronize(s);
+        for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        for (hipEvent_t* e : {&ev_acc_local, &ev_tail_done, &ev_sort_local}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+        if (h_pinned) (void)hipHostFree(h_pinned);
+        h_pinned = nullptr;
+        for (hipStream_t* s : {&tail, &stream}) if (*s) { (void)hipStreamDestroy(*s); *s = nullptr; }
+    }
+};
+
+// The two orders in which sums take a context's workers (which sum lands on which stream is measured behaviour):
+constexpr int PS_WORKERS = 6;
+constexpr int PS_RING_WORKERS[4] = {2, 0, 1, 3};                   // the point passes of a multi-sum, behind the context itself if it takes part (msm_multi_ring)
+constexpr int PS_LAUNCH_WORKERS[PS_WORKERS] = {0, 1, 2, 3, 4, 5};  // sums in flight, behind the context itself if it is allowed (msm_launch_impl)
+
+struct ps_ctx : MsmWorkspace {
     int batch_chunk = 0;     // ps_msm_batch_set_chunk: members per pass, 0 = automatic
     int batch_table = 0;     // ps_msm_batch_set_table: 0 the tabled pass where the rule admits it, 1 never, 2 wherever a table is usable
     hipEvent_t mb_ev[2] = {nullptr, nullptr};  // timed contexts: around the fold, the normalisation and the encoding of a batch's last pass
@@ -127,20 +181,18 @@ struct ps_ctx {
     DevBuf fb_table[2];              // fixed-base tables (G1, G2)
     bool fb_ready[2] = {false, false};
     u32* d_flag = nullptr;           // small device scratch word (bad-point counter etc.)
-    void* h_pinned = nullptr;        // pinned host scratch for window sums
-    size_t h_pinned_cap = 0;
-    // asynchronous sums: a FIFO of at most PS_MSM_QUEUE (ps_msm_launch, ..., then ps_msm_finish pops
-    // the oldest).  Each pending sum has its own workspace (the context itself, then `pipe`, `pipe2`:
-    // own streams + buffers); accumulations are chained in launch order, so a later sum's sort and
-    // accumulation run beside the earlier ones' latency-bound fix-up / reduction / host fold.
-    struct PendingMsm { int group; MsmPlan plan; ps_ctx* wc; };
+    // workspaces beside the context's own, made on first use: the point passes of a multi-sum and the sums in flight take them in the two orders above
+    MsmWorkspace workers[PS_WORKERS];
+    // asynchronous sums: a FIFO of at most PS_MSM_QUEUE (ps_msm_launch, ..., then ps_msm_finish pops the oldest).  Each
+    // pending sum has a workspace to itself (`ws`: the context, or one of `workers`) and carries the plan it was launched
+    // with; accumulations are chained in launch order, so a later sum's sort and accumulation run beside the earlier
+    // ones' latency-bound fix-up / reduction / host fold.
+    struct PendingMsm { int group; MsmPlan plan; MsmWorkspace* ws; };
     PendingMsm q[PS_MSM_QUEUE];
     int q_head = 0, q_len = 0;
-    bool pending = false;            // q_len > 0
-    ps_ctx *pipe = nullptr, *pipe2 = nullptr, *pipe3 = nullptr, *pipe4 = nullptr, *pipe5 = nullptr;
     hipEvent_t ev_fork = nullptr;
-    ps_ctx* last_chain = nullptr;    // workspace of the sum launched last (its ev_acc_local = accumulation done)
-    ps_ctx* last_timed = nullptr;
+    MsmWorkspace* last_chain = nullptr;  // workspace of the sum launched last (its ev_acc_local = accumulation done)
+    MsmWorkspace* last_timed = nullptr;  // workspace of the sum finished last (its ev[] = the stage times), nullptr: the context
     float phase_ms[PS_PROVE_PHASES] = {0, 0, 0, 0};  // host wall clock of the last prover call
     bool use_tables = true;          // the provers build window tables for their CRS arrays (ps_ctx_set_tables)
     long long table_budget = -1;     // bytes a prover may spend on ONE window table; negative: what hipMemGetInfo leaves (ps_ctx_set_table_budget)
@@ -153,9 +205,7 @@ struct ps_ctx {
     int forced_acc = 0;              // ps_msm_set_accumulate: 0 automatic, 1 slices, 2 whole buckets in order of size
     int last_acc = 0;                // ps_msm_last_accumulate: the point pass of the sum finished last (0: none yet)
     QuotientCache* qcache = nullptr;
-    // Groth16 fused driver: secondary context (own stream + workspace) for the concurrent G2 MSM,
-    // and the concatenated CRS arrays of the last proving key
-    ps_ctx* aux = nullptr;
+    // Groth16 fused driver: the concatenated CRS arrays of the last proving key
     unsigned long long g16_key[4] = {0, 0, 0, 0};
     uint8_t g16_fixed[96 * 3 + 192 * 2] = {0};
     ps_points *g16_pa = nullptr, *g16_pb = nullptr, *g16_pc = nullptr;
@@ -163,14 +213,10 @@ struct ps_ctx {
     bool g16_split = false;          // ... and whether PC was made for the split form of C (prove.inc, groth16_prove_impl)
     size_t g16_b1_min_n = (size_t)1 << 19;  // Lagrange-form keys of this many constraints or more: B in G1 as a sum of its own (PS_G16_B1_MIN_N)
     bool g16_multi_hsplit = true;    // ps_groth16_prove_multi, Lagrange-form local keys, three or more devices: the three convolutions of the values route on devices 0, 1, 2 (PS_G16_MULTI_HSPLIT)
-    hipEvent_t g16_ready = nullptr;
     // PHGR13 driver: vbs + wbs + ybs summed pointwise once per evaluation key (gz, pinochio.go:239-242)
     unsigned long long phgr_key[3] = {0, 0, 0};
     ps_points* phgr_bsum = nullptr;
-    // optional per-stage timing (HIP events on `stream`, the stream the kernels run on)
-    bool timing = false;
-    hipEvent_t ev[PS_MSM_STAGES + 1] = {};
-    bool ev_valid = false;
+    bool timing = false;             // ps_ctx_set_timing: sums record their stage events (in the workspace they run on)
     hipEvent_t ev_multi[PS_MSM_MULTI_MAX] = {};  // one per result of ps_msm_multi (created on first use)
     hipEvent_t ev_acc[PS_MSM_MULTI_MAX] = {};    // ... and one per accumulation kernel
     hipEvent_t ev_sorted = nullptr;
@@ -285,34 +331,19 @@ extern "C" int ps_ctx_create(int device, ps_ctx** out) {
     ps_ctx* c = new ps_ctx();
     if (const char* e = getenv("PS_G16_B1_MIN_N")) c->g16_b1_min_n = (size_t)strtoull(e, nullptr, 10);  // tests / measurements
     if (const char* e = getenv("PS_G16_MULTI_HSPLIT")) c->g16_multi_hsplit = strtol(e, nullptr, 10) != 0;  // likewise
-    c->device = device;
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    {
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&c->tail, hipStreamNonBlocking, greatest));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_acc_local, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_tail_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_sort_local, hipEventDisableTiming));
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_flag, 64));
-    c->h_pinned_cap = PS_MSM_MULTI_MAX * PS_PINNED_SLOT + 64;
-    HIP_TRY(hipHostMalloc(&c->h_pinned, c->h_pinned_cap));
-    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
+    int rc = c->create(device);
+    if (!rc && hipMalloc((void**)&c->d_flag, 64) != hipSuccess) rc = fail(PS_ERR_HIP, "ps_ctx_create: hipMalloc failed");
+    if (rc) { KeepError keep; ps_ctx_destroy(c); return rc; }
     *out = c;
     return PS_OK;
 }
 
+// The workspaces (the context's own and its workers) and every DevBuf release what they hold as the object goes; listed here is the rest.
 extern "C" void ps_ctx_destroy(ps_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->tail) (void)hipStreamSynchronize(c->tail);
-    for (DevBuf* b : {&c->counts, &c->offs, &c->bsum, &c->keys, &c->ranks, &c->sorted, &c->buckets, &c->parts,
-                      &c->segs, &c->wins, &c->heavy, &c->hparts, &c->vals, &c->coarse, &c->perm, &c->border, &c->staging, &c->affine_tmp, &c->mb_fold, &c->mb_out, &c->pb_x, &c->pb_y, &c->pb_small, &c->fb_table[0], &c->fb_table[1],
-                      &c->vb_f12, &c->vb_xyzz, &c->vb_rho, &c->vb_cols,
-                      &c->lc_f12, &c->lc_pts, &c->lc_rows, &c->lc_iolp, &c->lc_work})
-        b->release();
+    if (c->created()) (void)c->sync();
+    for (MsmWorkspace& w : c->workers) if (w.created()) (void)w.sync();
     quotient_cache_free(c->qcache);
     if (c->up_scalars) ps_scalars_free(c->up_scalars);
     for (ps_scalars* v : c->pv_scalars)
@@ -320,16 +351,8 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     if (c->g16_pa) ps_points_free(c->g16_pa);
     if (c->g16_pb) ps_points_free(c->g16_pb);
     if (c->g16_pc) ps_points_free(c->g16_pc);
-    if (c->g16_ready) (void)hipEventDestroy(c->g16_ready);
     if (c->phgr_bsum) ps_points_free(c->phgr_bsum);
-    if (c->aux) ps_ctx_destroy(c->aux);
-    if (c->pipe) ps_ctx_destroy(c->pipe);
-    if (c->pipe2) ps_ctx_destroy(c->pipe2);
-    if (c->pipe3) ps_ctx_destroy(c->pipe3);
-    if (c->pipe4) ps_ctx_destroy(c->pipe4);
-    if (c->pipe5) ps_ctx_destroy(c->pipe5);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_multi) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->mb_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->pb_ev) if (e) (void)hipEventDestroy(e);
@@ -338,22 +361,10 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     if (c->d_flag) (void)hipFree(c->d_flag);
     if (c->d_small) (void)hipFree(c->d_small);
     if (c->ev_q) (void)hipEventDestroy(c->ev_q);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    if (c->ev_acc_local) (void)hipEventDestroy(c->ev_acc_local);
-    if (c->ev_tail_done) (void)hipEventDestroy(c->ev_tail_done);
-    if (c->ev_sort_local) (void)hipEventDestroy(c->ev_sort_local);
-    if (c->tail) (void)hipStreamDestroy(c->tail);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
-extern "C" int ps_ctx_sync(ps_ctx* c) {
-    if (!c) return fail(PS_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->tail));
-    return PS_OK;
-}
+extern "C" int ps_ctx_sync(ps_ctx* c) { return c ? c->sync() : fail(PS_ERR_ARG, "ctx is NULL"); }
 extern "C" void* ps_ctx_stream(ps_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 // ---------------------------------------------------------------------------------------
@@ -542,7 +553,7 @@ extern "C" int ps_points_upload(ps_ctx* c, int group, const uint8_t* pts, size_t
     return scope.finish(PS_OK);
 }
 
-// XYZZ -> affine for n points on c->stream (k_batch_to_affine): `tmp` holds the XYZZ points followed by the chain products.
+// XYZZ -> affine for n points on stream `st` (k_batch_to_affine): `tmp` holds the XYZZ points followed by the chain products.
 // A context buffer, not hipMallocAsync.  Round 2 saw points 256.. of a 300-point array come back as the identity with
 // staging memory from the stream-ordered pool; round 3 reproduced and isolated it (tools/malloc_async_probe.py against a
 // -DPS_AFFINE_TMP_ASYNC build, profiles/r03_malloc_async_probe.txt): allocation, both kernels and the free are on ONE
@@ -556,9 +567,9 @@ extern "C" int ps_points_upload(ps_ctx* c, int group, const uint8_t* pts, size_t
 // Threads: at least 16 points per inversion, at most 2^16 chains.
 static size_t batch_affine_tmp_bytes(size_t n, size_t xyzz_bytes) { return n * (xyzz_bytes + sizeof(Fp)); }
 template <class F>
-static void batch_to_affine(ps_ctx* c, char* tmp, size_t n, char* out, u32 out_stride) {
+static void batch_to_affine(hipStream_t st, char* tmp, size_t n, char* out, u32 out_stride) {
     const u32 T = (u32)std::min<size_t>(65536, std::max<size_t>(1, n / 16));
-    hipLaunchKernelGGL(k_batch_to_affine<F>, dim3(nblocks(T)), dim3(256), 0, c->stream, (const Xyzz<F>*)tmp, (u32)n, T,
+    hipLaunchKernelGGL(k_batch_to_affine<F>, dim3(nblocks(T)), dim3(256), 0, st, (const Xyzz<F>*)tmp, (u32)n, T,
                        (Fp*)(tmp + n * sizeof(Xyzz<F>)), out, out_stride);
 }
 
@@ -583,7 +594,7 @@ static int fixed_base(ps_ctx* c, int gi, const ps_scalars* k, ps_points* out) {
         if (rc) return rc;
         if ((rc = c->affine_tmp.ensure(batch_affine_tmp_bytes(32 * 256, sizeof(Xyzz<F>))))) return rc;
         hipLaunchKernelGGL(k_fixed_base_table<KF>, dim3(32 * LN), dim3(256), 0, c->stream, (Xyzz<F>*)c->affine_tmp.p);
-        batch_to_affine<F>(c, (char*)c->affine_tmp.p, 32 * 256, (char*)c->fb_table[gi].p, (u32)sizeof(Affine<F>));
+        batch_to_affine<F>(c->stream, (char*)c->affine_tmp.p, 32 * 256, (char*)c->fb_table[gi].p, (u32)sizeof(Affine<F>));
         HIP_TRY(hipGetLastError());
         c->fb_ready[gi] = true;
     }
@@ -614,7 +625,7 @@ static int fixed_base(ps_ctx* c, int gi, const ps_scalars* k, ps_points* out) {
             fprintf(stderr, "[probe] after k_fixed_base_mul: %zu of %zu points have ZZ == 0 in memory (first %zu), tmp = %p\n", zero, (size_t)k->n, first, (void*)tmp);
         }
 #endif
-        batch_to_affine<F>(c, tmp, k->n, (char*)out->st->p, (u32)sizeof(Affine<F>));
+        batch_to_affine<F>(c->stream, tmp, k->n, (char*)out->st->p, (u32)sizeof(Affine<F>));
         HIP_TRY(hipGetLastError());
 #if defined(PS_AFFINE_TMP_ASYNC)
         HIP_TRY(hipFreeAsync(tmp, c->stream));
@@ -729,7 +740,7 @@ static int build_table(ps_ctx* c, const void* points, size_t n, void* table, int
         for (int w = 1; w < W; w++) {
             hipLaunchKernelGGL(k_table_next<KF>, dim3(nblocks(n * LN)), dim3(256), 0, c->stream, (const char*)(tab + (size_t)(w - 1) * n * rb),
                                rb, (u32)n, wbits, (Xyzz<F>*)tmp);
-            batch_to_affine<F>(c, tmp, n, tab + (size_t)w * n * rb, rb);
+            batch_to_affine<F>(c->stream, tmp, n, tab + (size_t)w * n * rb, rb);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1050,28 +1061,28 @@ extern "C" int ps_points_sum(int group, const uint8_t* pts, size_t k, uint8_t* o
 // The pipeline is split in two: the sort (digits, scan, scatter) depends on the scalars only, the
 // point pass (accumulate, fixup, reduce) on one point array.  ps_msm_multi runs one sort for several
 // point arrays that share a scalar vector (computeSolCommit x9, pinochio.go:231-241).
-#define PS_STAGE_MARK() do { if (timed) HIP_TRY(hipEventRecord(c->ev[evi++], st)); } while (0)
+#define PS_STAGE_MARK(w) do { if (timed) HIP_TRY(hipEventRecord((w)->ev[evi++], st)); } while (0)
 // `st`: the stream the sort runs on.  With sums in flight that is the workspace's HIGH-PRIORITY stream: the sort of sum i+1
 // shares the chip with the accumulation of sum i, whose waves hold 468 of a SIMD's 512 registers -- on the normal-priority
 // stream its workgroups were dispatched behind the accumulation's own (k_sort_partition: 2.0-2.6 ms instead of 0.09 in a
 // kernel trace of 2^20-point sums), the next accumulation waited for it, and the step was 2.78 ms for 2.30 ms of accumulation.
-static int msm_sort(ps_ctx* c, const ps_scalars* sc, const MsmPlan& pl, bool timed, hipStream_t st) {
+static int msm_sort(MsmWorkspace* ws, const ps_scalars* sc, const MsmPlan& pl, bool timed, hipStream_t st) {
     const size_t n = sc->n;
     const u64 total = (u64)pl.W * n;  // upper bound on entries
     const u64 G = pl.G;
     const u32 scan_tiles = (u32)((G + SCAN_TILE - 1) / SCAN_TILE);
     int rc;
-    if ((rc = c->counts.ensure(4 * G))) return rc;
-    if ((rc = c->offs.ensure(4 * (G + 1)))) return rc;
-    if ((rc = c->bsum.ensure(4 * (size_t)scan_tiles + 4))) return rc;
-    if ((rc = c->keys.ensure(4 * total))) return rc;
-    if ((rc = c->ranks.ensure(4 * total))) return rc;
-    if ((rc = c->vals.ensure(4 * total))) return rc;
-    if ((rc = c->sorted.ensure(4 * total + 4))) return rc;
-    if (c->tail_used) HIP_TRY(hipStreamWaitEvent(st, c->ev_tail_done, 0));  // the last tail still reads offs
+    if ((rc = ws->counts.ensure(4 * G))) return rc;
+    if ((rc = ws->offs.ensure(4 * (G + 1)))) return rc;
+    if ((rc = ws->bsum.ensure(4 * (size_t)scan_tiles + 4))) return rc;
+    if ((rc = ws->keys.ensure(4 * total))) return rc;
+    if ((rc = ws->ranks.ensure(4 * total))) return rc;
+    if ((rc = ws->vals.ensure(4 * total))) return rc;
+    if ((rc = ws->sorted.ensure(4 * total + 4))) return rc;
+    if (ws->tail_used) HIP_TRY(hipStreamWaitEvent(st, ws->ev_tail_done, 0));  // the last tail still reads offs
     if (storage_wait_ready(sc->st, st)) return fail(PS_ERR_HIP, "msm: event wait failed");  // asynchronously produced scalars
     int evi = 0;
-    PS_STAGE_MARK();  // 0: start
+    PS_STAGE_MARK(ws);  // 0: start
     DigitConst cadd{};  // C = sum_{w < W-1} 2^(c*w + c-1)
     for (int w = 0; w + 1 < pl.W; w++) {
         int bit = w * pl.c + pl.c - 1;
@@ -1086,75 +1097,75 @@ static int msm_sort(ps_ctx* c, const ps_scalars* sc, const MsmPlan& pl, bool tim
         if (const char* e = getenv("PS_T_FB")) fb = std::max(fb, std::min(atoi(e), 10));
 #endif
         const u32 ncoarse = (u32)((G + (1ull << fb) - 1) >> fb);
-        if ((rc = c->coarse.ensure(4 * (4 * (size_t)SORT_MAX_COARSE + 8)))) return rc;
-        u32* coarse_cnt = (u32*)c->coarse.p;
+        if ((rc = ws->coarse.ensure(4 * (4 * (size_t)SORT_MAX_COARSE + 8)))) return rc;
+        u32* coarse_cnt = (u32*)ws->coarse.p;
         u32* coarse_off = coarse_cnt + SORT_MAX_COARSE + 1;
         u32* coarse_cur = coarse_off + SORT_MAX_COARSE + 1;
         u32* tile_base = coarse_cur + SORT_MAX_COARSE + 1;
         HIP_TRY(hipMemsetAsync(coarse_cnt, 0, 4 * SORT_MAX_COARSE, st));
         const bool may_have_big_bins = total > SORT_BIG;  // a bin of more than SORT_BIG entries needs that many digits
-        if (may_have_big_bins) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 4 * G, st));  // per-bucket counters of the big bins (k_sort_big_*)
+        if (may_have_big_bins) HIP_TRY(hipMemsetAsync(ws->counts.p, 0, 4 * G, st));  // per-bucket counters of the big bins (k_sort_big_*)
         const dim3 cgrid((unsigned)((n + (size_t)COUNT_PER_THREAD * DIGITS_THREADS - 1) / ((size_t)COUNT_PER_THREAD * DIGITS_THREADS)));
         hipLaunchKernelGGL(k_sort_count, cgrid, dim3(DIGITS_THREADS), 0, st, scalars_ptr(sc), (u32)n, pl.c, pl.W, pl.NB, cadd, fold_neg,
-                           single, ncoarse, fb, (u32*)c->ranks.p, coarse_cnt);
-        PS_STAGE_MARK();  // 1: after digits + coarse histogram
+                           single, ncoarse, fb, (u32*)ws->ranks.p, coarse_cnt);
+        PS_STAGE_MARK(ws);  // 1: after digits + coarse histogram
         hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_MAX_COARSE), 0, st, (const u32*)coarse_cnt, ncoarse, coarse_off, coarse_cur,
-                           (u32*)c->offs.p + G, tile_base);
-        hipLaunchKernelGGL(k_sort_partition, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st, (const u32*)c->ranks.p,
-                           (u32)n, pl.NB, single, fb, coarse_cur, (unsigned short*)c->keys.p, (u32*)c->vals.p);
-        PS_STAGE_MARK();  // 2: after scan + partition
-        hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p, (const u32*)c->vals.p,
-                           (const u32*)coarse_off, (u32)G, fb, (u32*)c->offs.p, (u32*)c->sorted.p);
+                           (u32*)ws->offs.p + G, tile_base);
+        hipLaunchKernelGGL(k_sort_partition, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st, (const u32*)ws->ranks.p,
+                           (u32)n, pl.NB, single, fb, coarse_cur, (unsigned short*)ws->keys.p, (u32*)ws->vals.p);
+        PS_STAGE_MARK(ws);  // 2: after scan + partition
+        hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p, (const u32*)ws->vals.p,
+                           (const u32*)coarse_off, (u32)G, fb, (u32*)ws->offs.p, (u32*)ws->sorted.p);
         // bins with more than SORT_BIG entries, tile by tile (no tiles: the three kernels return at once; short sums, which
         // are bound by the number of launches, skip them)
         const unsigned big_grid = (unsigned)std::min<u64>(2048, total / SORT_TILE + 1);
         if (may_have_big_bins) {
-        hipLaunchKernelGGL(k_sort_big_count, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p, (const u32*)coarse_off,
-                           (const u32*)tile_base, ncoarse, fb, (u32*)c->counts.p);
-        hipLaunchKernelGGL(k_sort_big_scan, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const u32*)coarse_off, (u32)G, fb, (u32*)c->counts.p,
-                           (u32*)c->offs.p);
-        hipLaunchKernelGGL(k_sort_big_scatter, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p,
-                           (const u32*)c->vals.p, (const u32*)coarse_off, (const u32*)tile_base, ncoarse, fb, (u32*)c->counts.p,
-                           (u32*)c->sorted.p);
+        hipLaunchKernelGGL(k_sort_big_count, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p, (const u32*)coarse_off,
+                           (const u32*)tile_base, ncoarse, fb, (u32*)ws->counts.p);
+        hipLaunchKernelGGL(k_sort_big_scan, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const u32*)coarse_off, (u32)G, fb, (u32*)ws->counts.p,
+                           (u32*)ws->offs.p);
+        hipLaunchKernelGGL(k_sort_big_scatter, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p,
+                           (const u32*)ws->vals.p, (const u32*)coarse_off, (const u32*)tile_base, ncoarse, fb, (u32*)ws->counts.p,
+                           (u32*)ws->sorted.p);
         }
     } else {
-        HIP_TRY(hipMemsetAsync(c->counts.p, 0, 4 * G, st));
+        HIP_TRY(hipMemsetAsync(ws->counts.p, 0, 4 * G, st));
         {
             int bin_shift = 4;  // 16 counters = one 64-byte line
             while ((pl.NB >> bin_shift) > (u32)DIGITS_BINS) bin_shift++;
             hipLaunchKernelGGL(k_digits_grouped, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st, scalars_ptr(sc),
-                               (u32)n, pl.c, pl.W, pl.NB, cadd, bin_shift, fold_neg, single, (u32*)c->counts.p, (u32*)c->keys.p,
-                               (u32*)c->vals.p, (u32*)c->ranks.p);
+                               (u32)n, pl.c, pl.W, pl.NB, cadd, bin_shift, fold_neg, single, (u32*)ws->counts.p, (u32*)ws->keys.p,
+                               (u32*)ws->vals.p, (u32*)ws->ranks.p);
         }
-        PS_STAGE_MARK();  // 1: after memset + digits
-        hipLaunchKernelGGL(k_scan_blocks, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, st, (const u32*)c->counts.p, (u32*)c->offs.p,
-                           (u32*)c->bsum.p, (u64)G);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, (u32*)c->bsum.p, scan_tiles, (u32*)c->offs.p + G);
-        hipLaunchKernelGGL(k_scan_add, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, st, (u32*)c->offs.p, (const u32*)c->bsum.p, (u64)G);
-        PS_STAGE_MARK();  // 2: after scan
-        hipLaunchKernelGGL(k_scatter, dim3(nblocks(total)), dim3(256), 0, st, (const u32*)c->keys.p, (const u32*)c->vals.p,
-                           (const u32*)c->ranks.p, (const u32*)c->offs.p, total, (u32*)c->sorted.p);
+        PS_STAGE_MARK(ws);  // 1: after memset + digits
+        hipLaunchKernelGGL(k_scan_blocks, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, st, (const u32*)ws->counts.p, (u32*)ws->offs.p,
+                           (u32*)ws->bsum.p, (u64)G);
+        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, (u32*)ws->bsum.p, scan_tiles, (u32*)ws->offs.p + G);
+        hipLaunchKernelGGL(k_scan_add, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, st, (u32*)ws->offs.p, (const u32*)ws->bsum.p, (u64)G);
+        PS_STAGE_MARK(ws);  // 2: after scan
+        hipLaunchKernelGGL(k_scatter, dim3(nblocks(total)), dim3(256), 0, st, (const u32*)ws->keys.p, (const u32*)ws->vals.p,
+                           (const u32*)ws->ranks.p, (const u32*)ws->offs.p, total, (u32*)ws->sorted.p);
     }
     if (pl.acc != ACC_SLICES) {
         // buckets in order of size and the verdict word for the whole-bucket point pass (msm.hpp section 4b); the verdict
         // travels to the host like the entry count below, ahead of the results
-        if ((rc = c->perm.ensure(4 * G))) return rc;
-        if ((rc = c->border.ensure(4 * (2 * (size_t)BO_CLASSES + 4)))) return rc;
-        u32* hist = (u32*)c->border.p;
+        if ((rc = ws->perm.ensure(4 * G))) return rc;
+        if ((rc = ws->border.ensure(4 * (2 * (size_t)BO_CLASSES + 4)))) return rc;
+        u32* hist = (u32*)ws->border.p;
         u32* cursors = hist + BO_CLASSES;
         u32* verdict = cursors + BO_CLASSES;
         const unsigned tiles = (unsigned)((G + BO_PLACE_TILE - 1) / BO_PLACE_TILE);
         HIP_TRY(hipMemsetAsync(hist, 0, 4 * BO_CLASSES, st));
-        hipLaunchKernelGGL(k_bo_count, dim3(tiles), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, hist);
-        hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(BO_CLASSES), 0, st, (const u32*)hist, (const u32*)c->offs.p, (u32)G, (u32)pl.acc, cursors,
+        hipLaunchKernelGGL(k_bo_count, dim3(tiles), dim3(256), 0, st, (const u32*)ws->offs.p, (u32)G, hist);
+        hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(BO_CLASSES), 0, st, (const u32*)hist, (const u32*)ws->offs.p, (u32)G, (u32)pl.acc, cursors,
                            verdict);
-        hipLaunchKernelGGL(k_bo_place, dim3(tiles), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, cursors, (u32*)c->perm.p);
-        HIP_TRY(hipMemcpyAsync((char*)c->h_pinned + c->h_pinned_cap - 16, verdict, 4, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_bo_place, dim3(tiles), dim3(256), 0, st, (const u32*)ws->offs.p, (u32)G, cursors, (u32*)ws->perm.p);
+        HIP_TRY(hipMemcpyAsync((char*)ws->h_pinned + ws->h_pinned_cap - 16, verdict, 4, hipMemcpyDeviceToHost, st));
     }
-    PS_STAGE_MARK();  // 3: after scatter
+    PS_STAGE_MARK(ws);  // 3: after scatter
     HIP_TRY(hipGetLastError());
     // entry count for introspection (read back with the window sums; a short sum's last kernel appends it to its results)
-    if (!pl.qtail) HIP_TRY(hipMemcpyAsync((char*)c->h_pinned + c->h_pinned_cap - 8, (u32*)c->offs.p + G, 4, hipMemcpyDeviceToHost, st));
+    if (!pl.qtail) HIP_TRY(hipMemcpyAsync((char*)ws->h_pinned + ws->h_pinned_cap - 8, (u32*)ws->offs.p + G, 4, hipMemcpyDeviceToHost, st));
     return PS_OK;
 }
 
@@ -1180,17 +1191,19 @@ static bool table_ref(const ps_points* pts, size_t n, int wbits, int W, TableRef
     return false;
 }
 
-// Window sums of one point array over the sorted entries of `c`, copied to pinned slot `slot` of `c`.
-// The work buffers and the stream are those of `wc` (c itself, or c->aux when ps_msm_multi
-// alternates two workspaces so that the latency-bound tail of one sum -- fix-up and reduction, ~1.3 ms
-// of short dependency chains on a mostly idle chip -- runs under the next sum's accumulation).
+// The point pass of one array.  sw: the workspace whose sort this pass reads (sorted, offs, perm, the verdict word in border)
+// and whose pinned slot `slot` receives the result; a timed pass records its stages in sw's events, behind the sort's.
+// rw: the workspace whose streams and buffers the pass runs on.
+// One sum has both in one workspace (sw == rw).  The sums over one sort (ps_msm_multi, the provers' solution sums, the
+// arrays of a batch) read ring[0]'s sort from rotating workspaces, so that the latency-bound tail of one sum -- fix-up and
+// reduction, ~1.3 ms of short dependency chains on a mostly idle chip -- runs under the next sum's accumulation.
 // wait_acc: event the accumulation waits for; acc_done: recorded right after it.
 // dev_sets (ps_msm_batch only; NULL for every other caller, whose launches it does not touch): the set sums stay on the
 // device -- *dev_sets points at the pl.sets weighted sums in `wins`, nothing is copied to the pinned slot, and the number
 // of sets is not bound by that slot.  `n` is then the length of the virtual scalar array (members x points), and
 // `member_n` (0: n) the length of one member -- the index range whose window table a tabled batch reads.
 template <class F>
-static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, const MsmPlan& pl, bool timed, int slot,
+static int msm_points_t(MsmWorkspace* sw, MsmWorkspace* rw, const ps_points* pts, size_t n, const MsmPlan& pl, bool timed, int slot,
                         hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr, size_t member_n = 0) {
     typedef typename KernelField<F>::type KF;      // Fp -> Fp, Fp2 -> lane-split Fp2s
     constexpr unsigned LN = FieldTraits<KF>::LANES;  // lanes per logical thread
@@ -1215,10 +1228,10 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     const u32 idx_mask = tab ? (1u << ENTRY_W_SHIFT) - 1u : 0x7fffffffu;
     const u64 w_stride = tab ? tref.stride : 0ull;
     int rc;
-    if ((rc = wc->buckets.ensure(sizeof(Xyzz<F>) * G))) return rc;
-    if ((rc = wc->parts.ensure(sizeof(Xyzz<F>) * 2 * (size_t)nthreads_acc))) return rc;
-    if ((rc = wc->segs.ensure(sizeof(Xyzz<F>) * (2 * (size_t)nseg_total + 5 * (size_t)per_role + (size_t)nres * rp.nblk)))) return rc;
-    if ((rc = wc->wins.ensure(sizeof(Xyzz<F>) * ((size_t)nres + (size_t)pl.sets) + 16))) return rc;
+    if ((rc = rw->buckets.ensure(sizeof(Xyzz<F>) * G))) return rc;
+    if ((rc = rw->parts.ensure(sizeof(Xyzz<F>) * 2 * (size_t)nthreads_acc))) return rc;
+    if ((rc = rw->segs.ensure(sizeof(Xyzz<F>) * (2 * (size_t)nseg_total + 5 * (size_t)per_role + (size_t)nres * rp.nblk)))) return rc;
+    if ((rc = rw->wins.ensure(sizeof(Xyzz<F>) * ((size_t)nres + (size_t)pl.sets) + 16))) return rc;
     // a heavy bucket spans >= HEAVY_SPAN slices for the one-lane fix-up, >= QFIX_HEAVY x (quads per bucket) for the quad fix-up
     const bool qfix = pl.shortsum && pl.lpb >= 1;
     const u32 qlpb = qfix ? std::min<u32>((u32)pl.lpb, 256 / QTraits<KF>::GL) : 0;
@@ -1234,37 +1247,37 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
     // a bucket on chain_list holds a whole slice of its own and shares the slices at its ends with at most one other each
     const size_t max_chain = split_fixup ? (size_t)nthreads_acc / 2 + 2 : 0;
     // heavy: [heavy count][chain count][heavy list: max_heavy][job_base: max_heavy + 1][chain list: max_chain]; hparts: one point per job
-    if ((rc = wc->heavy.ensure(4 * (2 * max_heavy + 3 + max_chain)))) return rc;
+    if ((rc = rw->heavy.ensure(4 * (2 * max_heavy + 3 + max_chain)))) return rc;
     const u32 heavy_npb = 256 / QTraits<KF>::GL;  // a job is at least one block's worth of slices (heavy_chunk_of)
     const size_t max_jobs = (size_t)nthreads_acc / heavy_npb + max_heavy + 1;
-    if ((rc = wc->hparts.ensure(sizeof(Xyzz<F>) * max_jobs))) return rc;
+    if ((rc = rw->hparts.ensure(sizeof(Xyzz<F>) * max_jobs))) return rc;
     if (!dev_sets && sizeof(Xyzz<F>) * (pl.sets > 1 ? (size_t)pl.sets : (size_t)nres) + 16 > PS_PINNED_SLOT) return fail(PS_ERR_ARG, "too many windows");
-    hipStream_t st = wc->stream;
+    hipStream_t st = rw->stream;
     int evi = 4;  // ev[3] = after the scatter (msm_sort); ev[4] = the accumulation may start
-    if (wc->tail_used) HIP_TRY(hipStreamWaitEvent(st, wc->ev_tail_done, 0));  // buffers of the previous sum
+    if (rw->tail_used) HIP_TRY(hipStreamWaitEvent(st, rw->ev_tail_done, 0));  // buffers of the previous sum
     if (storage_wait_ready(pts->st, st)) return fail(PS_ERR_HIP, "msm: event wait failed");  // asynchronously produced points
     if (wait_acc) HIP_TRY(hipStreamWaitEvent(st, wait_acc, 0));
-    PS_STAGE_MARK();  // 4: buffers cleared and the previous sum's accumulation done ("queue")
+    PS_STAGE_MARK(sw);  // 4: buffers cleared and the previous sum's accumulation done ("queue")
     constexpr bool PF = LN == 1 || PS_G2_ACC_WAVES == 1;  // next point prefetched (the lane-pair G2 kernel at two waves per SIMD has no registers to spare)
     // Whole buckets in order of size (msm.hpp section 4b) where the plan asks for them: forced, only that path is launched;
     // automatic, both are enqueued and the verdict word the sort left on the device lets one of them return at once.
     // ps_msm_batch (dev_sets) keeps the slices.
     const u32 acc_mode = dev_sets ? (u32)ACC_SLICES : (u32)pl.acc;
-    const u32* verdict = acc_mode == ACC_SLICES ? nullptr : (const u32*)c->border.p + 2 * BO_CLASSES;
+    const u32* verdict = acc_mode == ACC_SLICES ? nullptr : (const u32*)sw->border.p + 2 * BO_CLASSES;
     if (acc_mode != ACC_SLICES)
-        hipLaunchKernelGGL((k_bucket_sum<KF, PF>), dim3(nblocks(G * LN)), dim3(256), 0, st, src, (const u32*)c->sorted.p,
-                           (const u32*)c->offs.p, (const u32*)c->perm.p, (u32)G, idx_mask, w_stride, pstride, (Xyzz<F>*)wc->buckets.p,
-                           (u32*)wc->heavy.p, verdict);
+        hipLaunchKernelGGL((k_bucket_sum<KF, PF>), dim3(nblocks(G * LN)), dim3(256), 0, st, src, (const u32*)sw->sorted.p,
+                           (const u32*)sw->offs.p, (const u32*)sw->perm.p, (u32)G, idx_mask, w_stride, pstride, (Xyzz<F>*)rw->buckets.p,
+                           (u32*)rw->heavy.p, verdict);
     if (acc_mode != ACC_BUCKETS)
     hipLaunchKernelGGL((k_accumulate<KF, PF>), dim3(nblocks((size_t)nthreads_acc * LN)), dim3(256), 0, st, src,
-                       (const u32*)c->sorted.p, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, idx_mask, w_stride, pstride,
-                       (Xyzz<F>*)wc->buckets.p, (Xyzz<F>*)wc->parts.p, (u32*)wc->heavy.p, verdict);
+                       (const u32*)sw->sorted.p, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, idx_mask, w_stride, pstride,
+                       (Xyzz<F>*)rw->buckets.p, (Xyzz<F>*)rw->parts.p, (u32*)rw->heavy.p, verdict);
     if (acc_done) HIP_TRY(hipEventRecord(acc_done, st));
-    PS_STAGE_MARK();  // 5: after accumulate
-    HIP_TRY(hipEventRecord(wc->ev_acc_local, st));
+    PS_STAGE_MARK(sw);  // 5: after accumulate
+    HIP_TRY(hipEventRecord(rw->ev_acc_local, st));
     if (!inline_tail) {  // a lone short sum keeps one stream: the hop to the tail stream costs it ~10 us and buys nothing
-        st = wc->tail;   // ---- the rest runs on the high-priority tail stream ----
-        HIP_TRY(hipStreamWaitEvent(st, wc->ev_acc_local, 0));
+        st = rw->tail;   // ---- the rest runs on the high-priority tail stream ----
+        HIP_TRY(hipStreamWaitEvent(st, rw->ev_acc_local, 0));
     }
     if (acc_mode == ACC_BUCKETS) {
         // every bucket is final: no fix-up of any kind
@@ -1272,41 +1285,41 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
         // the plan of a multi-sum is shared by arrays of both groups (PHGR13: six G1 sums and a G2 one over one sort): the
         // quads of a bucket must fit THIS group's 256-thread block (64 G1 points, 32 G2 points)
         const u32 lpb = qlpb;
-        hipLaunchKernelGGL(k_qfixup<KF>, dim3(nblocks(G * (u64)lpb * QTraits<KF>::GL)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M,
-                           nthreads_acc, lpb, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2);
+        hipLaunchKernelGGL(k_qfixup<KF>, dim3(nblocks(G * (u64)lpb * QTraits<KF>::GL)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M,
+                           nthreads_acc, lpb, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2);
     } else if (split_fixup) {
-        u32* ccount = (u32*)wc->heavy.p + 1;
-        u32* clist = (u32*)wc->heavy.p + 2 + 2 * max_heavy + 1;
-        hipLaunchKernelGGL(k_fixup_classify<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
-                           (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2, ccount, clist, verdict);
+        u32* ccount = (u32*)rw->heavy.p + 1;
+        u32* clist = (u32*)rw->heavy.p + 2 + 2 * max_heavy + 1;
+        hipLaunchKernelGGL(k_fixup_classify<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc,
+                           (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2, ccount, clist, verdict);
         if (nthreads_acc > 1)  // one logical thread per slice boundary
-            hipLaunchKernelGGL(k_fixup_pair<KF>, dim3(nblocks((size_t)(nthreads_acc - 1) * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G,
-                               pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, verdict);
+            hipLaunchKernelGGL(k_fixup_pair<KF>, dim3(nblocks((size_t)(nthreads_acc - 1) * LN)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G,
+                               pl.M, nthreads_acc, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, verdict);
         // a quad per listed bucket; the list's length stays on the device, so the grid is that of the longest list, within
         // one round of blocks
         constexpr u32 chain_npb = 256 / QTraits<KF>::GL;
         hipLaunchKernelGGL(k_qfixup_chain<KF>, dim3((unsigned)std::min<size_t>((max_chain + chain_npb - 1) / chain_npb, 512)), dim3(256), 0, st,
-                           (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p,
+                           (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p,
                            (const u32*)ccount, (const u32*)clist);
     } else
-    hipLaunchKernelGGL(k_fixup<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
-                       (const Xyzz<F>*)wc->parts.p, (Xyzz<F>*)wc->buckets.p, (u32*)wc->heavy.p, (u32*)wc->heavy.p + 2);
+    hipLaunchKernelGGL(k_fixup<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc,
+                       (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2);
     if (acc_mode != ACC_BUCKETS) {
-        const u32* hcount = (const u32*)wc->heavy.p;
+        const u32* hcount = (const u32*)rw->heavy.p;
         const u32* hlist = hcount + 2;
-        u32* job_base = (u32*)wc->heavy.p + 2 + max_heavy;
-        hipLaunchKernelGGL(k_heavy_jobs, dim3(1), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc, hcount, hlist, job_base, heavy_npb);
+        u32* job_base = (u32*)rw->heavy.p + 2 + max_heavy;
+        hipLaunchKernelGGL(k_heavy_jobs, dim3(1), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, hcount, hlist, job_base, heavy_npb);
         // two levels of quad trees for every plan (qtail.hpp): the one-lane kernels of rounds 1-2 (jobs of 1024 slices, strided
         // chains, an 8-level LDS tree of 14-36 us additions) took 0.43 ms for the 2^19 ones of a boolean witness at 2^20 points
-        hipLaunchKernelGGL(k_qfixup_heavy_part<KF>, dim3(1024), dim3(256), 0, st, (const u32*)c->offs.p, (u32)G, pl.M, nthreads_acc,
-                           (const Xyzz<F>*)wc->parts.p,
-                           hcount, hlist, (const u32*)job_base, (Xyzz<F>*)wc->hparts.p);
-        hipLaunchKernelGGL(k_qfixup_heavy<KF>, dim3(256), dim3(256), 0, st, (const Xyzz<F>*)wc->hparts.p, (Xyzz<F>*)wc->buckets.p, hcount,
+        hipLaunchKernelGGL(k_qfixup_heavy_part<KF>, dim3(1024), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc,
+                           (const Xyzz<F>*)rw->parts.p,
+                           hcount, hlist, (const u32*)job_base, (Xyzz<F>*)rw->hparts.p);
+        hipLaunchKernelGGL(k_qfixup_heavy<KF>, dim3(256), dim3(256), 0, st, (const Xyzz<F>*)rw->hparts.p, (Xyzz<F>*)rw->buckets.p, hcount,
                            hlist, (const u32*)job_base);
     }
-    PS_STAGE_MARK();  // 6: after fixup
+    PS_STAGE_MARK(sw);  // 6: after fixup
     {
-        Xyzz<F>* accs = (Xyzz<F>*)wc->segs.p;
+        Xyzz<F>* accs = (Xyzz<F>*)rw->segs.p;
         Xyzz<F>* runs = accs + nseg_total;
         Xyzz<F>* lvl = runs + nseg_total;
         Xyzz<F>* pieces = lvl + 5 * (size_t)per_role;
@@ -1326,19 +1339,19 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
                 if (pl.busy) if (const char* e = getenv("PS_T_NP_BUSY")) np = std::max<u32>(64 / QGL, std::min<u32>(np, (u32)atoi(e)));
 #endif
                 hipLaunchKernelGGL(k_qreduce_rowcol<KF>, dim3((rows + cols) * (u32)pl.sets), dim3(np * QGL), np * QGL * sizeof(Fp), st,
-                                   (const Xyzz<F>*)wc->buckets.p, cb, s, R, C, (const Xyzz<F>*)nullptr, (Xyzz<F>*)nullptr);
+                                   (const Xyzz<F>*)rw->buckets.p, cb, s, R, C, (const Xyzz<F>*)nullptr, (Xyzz<F>*)nullptr);
             }
             const u32 terms = std::max(rows, cols / 2);
             const u32 np = std::min<u32>(QNP, std::max<u32>(terms, 64 / QGL));
             hipLaunchKernelGGL(k_qreduce_bits<KF>, dim3(nres), dim3(np * QGL), np * QGL * sizeof(Fp), st,
-                               s > 0 ? (const Xyzz<F>*)R : (const Xyzz<F>*)wc->buckets.p, (const Xyzz<F>*)C, cb, s, (Xyzz<F>*)wc->wins.p,
-                               (const u32*)c->offs.p + G, (u32*)((Xyzz<F>*)wc->wins.p + (pl.sets > 1 ? nres + (size_t)pl.sets : (size_t)nres)),
+                               s > 0 ? (const Xyzz<F>*)R : (const Xyzz<F>*)rw->buckets.p, (const Xyzz<F>*)C, cb, s, (Xyzz<F>*)rw->wins.p,
+                               (const u32*)sw->offs.p + G, (u32*)((Xyzz<F>*)rw->wins.p + (pl.sets > 1 ? nres + (size_t)pl.sets : (size_t)nres)),
                                (const Xyzz<F>*)nullptr);
         } else if (rp.small) {
             hipLaunchKernelGGL(k_reduce_small<KF>, dim3(nres), dim3(RED_SUM_LANES * LN), RED_SUM_LANES * sizeof(Xyzz<F>), st,
-                               (const Xyzz<F>*)wc->buckets.p, pl.NB, rp.njobs, (Xyzz<F>*)wc->wins.p);
+                               (const Xyzz<F>*)rw->buckets.p, pl.NB, rp.njobs, (Xyzz<F>*)rw->wins.p);
         } else {
-            hipLaunchKernelGGL(k_reduce_l1<KF>, dim3(nblocks((size_t)nseg_total * LN)), dim3(256), 0, st, (const Xyzz<F>*)wc->buckets.p,
+            hipLaunchKernelGGL(k_reduce_l1<KF>, dim3(nblocks((size_t)nseg_total * LN)), dim3(256), 0, st, (const Xyzz<F>*)rw->buckets.p,
                                nseg_total, accs, runs);
             if (pl.hybrid && rp.segs >= 64) {
                 // Behind the 8-bucket running sums the parallelism is gone (2^16 segments at 2^20 points) and what is left is
@@ -1359,31 +1372,31 @@ static int msm_points_t(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, c
                                    (const Xyzz<F>*)runs, cb2, s2, R_run, C_run, (const Xyzz<F>*)accs, R_acc);
                 const u32 np2 = std::min<u32>(QNP, std::max<u32>(std::max(rows2, cols2 / 2), 64 / QGL));
                 hipLaunchKernelGGL(k_qreduce_bits<KF>, dim3(nres), dim3(np2 * QGL), np2 * QGL * sizeof(Fp), st, (const Xyzz<F>*)R_run,
-                                   (const Xyzz<F>*)C_run, cb2, s2, (Xyzz<F>*)wc->wins.p, (const u32*)nullptr, (u32*)nullptr, (const Xyzz<F>*)R_acc);
+                                   (const Xyzz<F>*)C_run, cb2, s2, (Xyzz<F>*)rw->wins.p, (const u32*)nullptr, (u32*)nullptr, (const Xyzz<F>*)R_acc);
             } else {
             hipLaunchKernelGGL(k_reduce_pyr<KF>, dim3(nblocks(5 * (size_t)per_role * LN)), dim3(256), 0, st, (const Xyzz<F>*)accs,
                                (const Xyzz<F>*)runs, rp.segs, rp.m, (u32)pl.sets, lvl);
             hipLaunchKernelGGL(k_reduce_sum<KF>, dim3(nres * rp.nblk), dim3(RED_SUM_LANES * LN), RED_SUM_LANES * sizeof(Xyzz<F>), st,
-                               (const Xyzz<F>*)lvl, rp.m, (u32)pl.sets, rp.njobs, rp.nblk, rp.nblk > 1 ? pieces : (Xyzz<F>*)wc->wins.p);
+                               (const Xyzz<F>*)lvl, rp.m, (u32)pl.sets, rp.njobs, rp.nblk, rp.nblk > 1 ? pieces : (Xyzz<F>*)rw->wins.p);
             if (rp.nblk > 1)
                 hipLaunchKernelGGL(k_reduce_fin<KF>, dim3(nres), dim3(RED_SUM_LANES * LN), RED_SUM_LANES * sizeof(Xyzz<F>), st,
-                                   (const Xyzz<F>*)pieces, rp.nblk, (Xyzz<F>*)wc->wins.p);
+                                   (const Xyzz<F>*)pieces, rp.nblk, (Xyzz<F>*)rw->wins.p);
             }
         }
         if (pl.sets > 1 || dev_sets)  // per-set weights on the device; the set sums follow the partial results in `wins`
             hipLaunchKernelGGL(k_reduce_weights<KF>, dim3((unsigned)pl.sets), dim3(RED_SUM_LANES * LN), RED_SUM_LANES * sizeof(Xyzz<F>), st,
-                               (const Xyzz<F>*)wc->wins.p, rp.njobs, (rp.small && !pl.qtail) ? 1 : 0, pl.qtail ? 0 : RED_SEG_LOG,
-                               (Xyzz<F>*)wc->wins.p + nres);
+                               (const Xyzz<F>*)rw->wins.p, rp.njobs, (rp.small && !pl.qtail) ? 1 : 0, pl.qtail ? 0 : RED_SEG_LOG,
+                               (Xyzz<F>*)rw->wins.p + nres);
     }
-    PS_STAGE_MARK();  // 7: after reduction
+    PS_STAGE_MARK(sw);  // 7: after reduction
     HIP_TRY(hipGetLastError());
     // one set: its partial results (the host applies the weights); several: the set sums
-    if (dev_sets) *dev_sets = (Xyzz<F>*)wc->wins.p + nres;
+    if (dev_sets) *dev_sets = (Xyzz<F>*)rw->wins.p + nres;
     else
-    HIP_TRY(hipMemcpyAsync((char*)c->h_pinned + (size_t)slot * PS_PINNED_SLOT, (const Xyzz<F>*)wc->wins.p + (pl.sets > 1 ? nres : 0),
+    HIP_TRY(hipMemcpyAsync((char*)sw->h_pinned + (size_t)slot * PS_PINNED_SLOT, (const Xyzz<F>*)rw->wins.p + (pl.sets > 1 ? nres : 0),
                            sizeof(Xyzz<F>) * (pl.sets > 1 ? (size_t)pl.sets : (size_t)nres) + (pl.qtail ? 4 : 0), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(wc->ev_tail_done, st));
-    wc->tail_used = true;
+    HIP_TRY(hipEventRecord(rw->ev_tail_done, st));
+    rw->tail_used = true;
     return PS_OK;
 }
 #undef PS_STAGE_MARK
@@ -1515,25 +1528,25 @@ static int msm_plan_checked(ps_ctx* c, const ps_points* const* pts, size_t k, si
 #ifndef PS_CHAIN_MIN_ENTRIES
 #define PS_CHAIN_MIN_ENTRIES (1ull << 21)  // sums with fewer digits than this are not chained behind the previous accumulation
 #endif
-static int msm_launch_any(ps_ctx* wc, const ps_points* pts, const ps_scalars* sc, const MsmPlan& pl, hipEvent_t wait_acc,
+static int msm_launch_any(MsmWorkspace* ws, const ps_points* pts, const ps_scalars* sc, const MsmPlan& pl, bool timed, hipEvent_t wait_acc,
                           hipEvent_t acc_done, bool inline_tail) {
-    hipStream_t ss = inline_tail ? wc->stream : wc->tail;  // a lone short sum keeps one stream
-    int rc = msm_sort(wc, sc, pl, wc->timing, ss);
+    hipStream_t ss = inline_tail ? ws->stream : ws->tail;  // a lone short sum keeps one stream
+    int rc = msm_sort(ws, sc, pl, timed, ss);
     if (rc) return rc;
-    if (ss != wc->stream) {
-        HIP_TRY(hipEventRecord(wc->ev_sort_local, ss));
-        HIP_TRY(hipStreamWaitEvent(wc->stream, wc->ev_sort_local, 0));
+    if (ss != ws->stream) {
+        HIP_TRY(hipEventRecord(ws->ev_sort_local, ss));
+        HIP_TRY(hipStreamWaitEvent(ws->stream, ws->ev_sort_local, 0));
     }
-    rc = pts->group == PS_G1 ? msm_points_t<Fp>(wc, wc, pts, sc->n, pl, wc->timing, 0, wait_acc, acc_done, inline_tail)
-                             : msm_points_t<Fp2>(wc, wc, pts, sc->n, pl, wc->timing, 0, wait_acc, acc_done, inline_tail);
-    wc->ev_valid = wc->timing && !rc;
+    rc = pts->group == PS_G1 ? msm_points_t<Fp>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail)
+                             : msm_points_t<Fp2>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail);
+    ws->ev_valid = timed && !rc;
     return rc;
 }
 
 template <class F>
-static void msm_fold_host(ps_ctx* c, const MsmPlan& pl, int slot, uint8_t* out) {
+static void msm_fold_host(const MsmWorkspace* ws, const MsmPlan& pl, int slot, uint8_t* out) {
     typedef typename HostField<F>::type H;  // six 64-bit words: the chain below costs the CPU 0.05 ms instead of 0.35
-    const Xyzz<F>* res = (const Xyzz<F>*)((const char*)c->h_pinned + (size_t)slot * PS_PINNED_SLOT);
+    const Xyzz<F>* res = (const Xyzz<F>*)((const char*)ws->h_pinned + (size_t)slot * PS_PINNED_SLOT);
     Xyzz<H> acc = xyzz_identity<H>();
     if (pl.sets == 1) {
         // the reduction leaves A, Q0, Q1, Q2, T_0 .. T_{kb-1} (msm.hpp section 6): sum = A + 8 (Q0 + 2 Q1 + 4 Q2 + 8 sum_k 2^k T_k)
@@ -1567,15 +1580,15 @@ static void msm_fold_host(ps_ctx* c, const MsmPlan& pl, int slot, uint8_t* out) 
 }
 
 // digits that were not zero (introspection): behind the results of slot 0 for a short sum, else in the pinned buffer's tail
-static u32 msm_entries(const ps_ctx* c, const MsmPlan& pl, int group) {
-    if (!pl.qtail) return *(const u32*)((const char*)c->h_pinned + c->h_pinned_cap - 8);
+static u32 msm_entries(const MsmWorkspace* ws, const MsmPlan& pl, int group) {
+    if (!pl.qtail) return *(const u32*)((const char*)ws->h_pinned + ws->h_pinned_cap - 8);
     const size_t pt = group == PS_G1 ? sizeof(Xyzz<Fp>) : sizeof(Xyzz<Fp2>);
-    return *(const u32*)((const char*)c->h_pinned + pt * (pl.sets > 1 ? (size_t)pl.sets : (size_t)pl.c));
+    return *(const u32*)((const char*)ws->h_pinned + pt * (pl.sets > 1 ? (size_t)pl.sets : (size_t)pl.c));
 }
 
 // the point pass a finished sum took: what the plan fixed, or the verdict word that came back ahead of the results
-static int msm_acc_path(const ps_ctx* c, const MsmPlan& pl) {
-    return pl.acc != ACC_AUTO ? pl.acc : (int)*(const u32*)((const char*)c->h_pinned + c->h_pinned_cap - 16);
+static int msm_acc_path(const MsmWorkspace* ws, const MsmPlan& pl) {
+    return pl.acc != ACC_AUTO ? pl.acc : (int)*(const u32*)((const char*)ws->h_pinned + ws->h_pinned_cap - 16);
 }
 
 static void write_identity(int group, uint8_t* out) {  // zero.Clone(), algebra.go:353
@@ -1587,11 +1600,11 @@ static void write_identity(int group, uint8_t* out) {  // zero.Clone(), algebra.
 // `ring` (entries may coincide when k is small), accumulation i+1 chained behind accumulation i so that it runs beside
 // the fix-up and reduction of sum i.  Four workspaces: a tail that shares the chip with the following accumulations is
 // starved of CUs and may outlast two of them (measured: 8 ms for a G2 tail under three G1 accumulations), and the sum
-// that reuses its buffers must not wait for it.  Events live on `c`.
+// that reuses its buffers must not wait for it.  The events that order the workspaces live on the context `c`.
 constexpr int PS_MULTI_RING = 4;
-static int msm_multi_sort(ps_ctx* c, ps_ctx* const* ring, const ps_scalars* sc, const MsmPlan& pl, bool fork) {
+static int msm_multi_sort(ps_ctx* c, MsmWorkspace* const* ring, const ps_scalars* sc, const MsmPlan& pl, bool fork) {
     int rc;
-    ps_ctx* w0 = ring[0];
+    MsmWorkspace* w0 = ring[0];
     if (fork) {  // inputs prepared on the context stream are visible to the stream the sort runs on
         if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
@@ -1609,13 +1622,13 @@ static int msm_multi_sort(ps_ctx* c, ps_ctx* const* ring, const ps_scalars* sc, 
     return PS_OK;
 }
 // first_wait: a point pass launched before this call that the first accumulation is chained behind
-static int msm_multi_points(ps_ctx* c, ps_ctx* const* ring, const ps_points* const* pts, size_t k, const ps_scalars* sc,
+static int msm_multi_points(ps_ctx* c, MsmWorkspace* const* ring, const ps_points* const* pts, size_t k, const ps_scalars* sc,
                             const MsmPlan& pl, hipEvent_t first_wait) {
-    ps_ctx* w0 = ring[0];
+    MsmWorkspace* w0 = ring[0];
     for (size_t i = 0; i < k; i++) {
         if (!c->ev_multi[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_multi[i], hipEventDisableTiming));
         if (!c->ev_acc[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_acc[i], hipEventDisableTiming));
-        ps_ctx* wc = ring[i % PS_MULTI_RING];
+        MsmWorkspace* rw = ring[i % PS_MULTI_RING];
         // The accumulations of a multi-sum are NOT chained behind each other (round 4; PS_MULTI_CHAIN_MIN_ENTRIES): all of them
         // are enqueued at once, on rotating workspaces, and when they share the chip the workgroups of the next one fill the
         // SIMDs the previous one's last, ragged round leaves idle.  A/B on one box, PHGR13Prove at 2^20 constraints (seven
@@ -1623,34 +1636,37 @@ static int msm_multi_points(ps_ctx* c, ps_ctx* const* ring, const ps_points* con
         // the chain: 2^20-point G1 sums 2.97 ms per step chained, 3.03-3.08 unchained.)
         const bool chained = (u64)pl.W * sc->n >= PS_MULTI_CHAIN_MIN_ENTRIES;
         hipEvent_t wait = !chained ? nullptr : i ? c->ev_acc[i - 1] : first_wait;
-        int rc = pts[i]->group == PS_G1 ? msm_points_t<Fp>(w0, wc, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i])
-                                        : msm_points_t<Fp2>(w0, wc, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i]);
+        int rc = pts[i]->group == PS_G1 ? msm_points_t<Fp>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i])
+                                        : msm_points_t<Fp2>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i]);
         if (rc) {
-            for (int j = 0; j < PS_MULTI_RING; j++) (void)ps_ctx_sync(ring[j]);
+            for (int j = 0; j < PS_MULTI_RING; j++) (void)ring[j]->sync();
             return rc;
         }
-        HIP_TRY(hipEventRecord(c->ev_multi[i], wc->tail));
+        HIP_TRY(hipEventRecord(c->ev_multi[i], rw->tail));
     }
     return PS_OK;
 }
-// the workspaces of a multi-sum on context c: `self` puts the context itself first (ps_msm_multi), otherwise only workers
-static int msm_multi_ring(ps_ctx* c, bool self, size_t k, ps_ctx** ring) {
-    ps_ctx** slots[4] = {&c->aux, &c->pipe, &c->pipe2, &c->pipe3};
+// worker i of context c, made on first use
+static int ctx_worker(ps_ctx* c, int i, MsmWorkspace** out) {
+    *out = &c->workers[i];
+    return (*out)->created() ? PS_OK : (*out)->create(c->device);
+}
+// the workspaces of k sums over one sort on context c, the ring repeating them when they are fewer than its entries: `self` puts
+// the context itself first (ps_msm_multi, the batches), otherwise only workers (the provers), in the order of PS_RING_WORKERS
+static int msm_multi_ring(ps_ctx* c, bool self, size_t k, MsmWorkspace** ring) {
     int have = 0;
     if (self) ring[have++] = c;
     for (int j = 0; have < PS_MULTI_RING && (size_t)have < std::max<size_t>(k, 1); j++) {
-        if (!*slots[j]) {
-            int rc = ps_ctx_create(c->device, slots[j]);
-            if (rc) return rc;
-        }
-        ring[have++] = *slots[j];
+        int rc = ctx_worker(c, PS_RING_WORKERS[j], &ring[have]);
+        if (rc) return rc;
+        have++;
     }
     for (int j = have; j < PS_MULTI_RING; j++) ring[j] = ring[j % have];
     return PS_OK;
 }
 
 // fold result i on the host while the GPU works on i+1...; out == nullptr just drains
-static int msm_multi_finish(ps_ctx* c, ps_ctx* w0, const ps_points* const* pts, size_t k, const MsmPlan& pl, uint8_t* const* out) {
+static int msm_multi_finish(ps_ctx* c, const MsmWorkspace* w0, const ps_points* const* pts, size_t k, const MsmPlan& pl, uint8_t* const* out) {
     for (size_t i = 0; i < k; i++) {
         HIP_TRY(hipEventSynchronize(c->ev_multi[i]));
         if (!out) continue;
@@ -1680,7 +1696,7 @@ extern "C" int ps_msm_multi(ps_ctx* c, const ps_points* const* pts, size_t k, co
     if (rc) return rc;
     for (size_t i = 0; i < k; i++)
         if (!out[i]) return fail(PS_ERR_ARG, "ps_msm_multi: NULL argument");
-    if (c->pending) return fail(PS_ERR_ARG, "ps_msm_multi: an MSM is already pending on this context");
+    if (c->q_len) return fail(PS_ERR_ARG, "ps_msm_multi: an MSM is already pending on this context");
     if (sc->n == 0) {
         for (size_t i = 0; i < k; i++) write_identity(pts[i]->group, out[i]);
         return PS_OK;
@@ -1688,16 +1704,15 @@ extern "C" int ps_msm_multi(ps_ctx* c, const ps_points* const* pts, size_t k, co
     HIP_TRY(hipSetDevice(c->device));
     MsmPlan pl;
     if ((rc = msm_plan_checked(c, pts, k, sc->n, sc->max_bits, &pl))) return rc;
-    if (c->aux && c->aux->pending) return fail(PS_ERR_ARG, "ps_msm_multi: the auxiliary context is busy");
-    ps_ctx* ring[PS_MULTI_RING];
+    MsmWorkspace* ring[PS_MULTI_RING];
     if ((rc = msm_multi_ring(c, true, k, ring))) return rc;
     if ((rc = msm_multi_sort(c, ring, sc, pl, true))) return rc;
     if ((rc = msm_multi_points(c, ring, pts, k, sc, pl, nullptr))) return rc;
     return msm_multi_finish(c, c, pts, k, pl, out);
 }
 
-// allow_self = false keeps the context's own stream out of the rotation (the provers run the quotient on it while
-// the sums run on the three worker contexts pipe, pipe2, aux)
+// allow_self = false keeps the context's own workspace out of the rotation (the provers run the quotient on its stream while
+// their sums run on workers)
 static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc, bool allow_self) {
     if (!c || !pts || !sc) return fail(PS_ERR_ARG, "ps_msm: NULL argument");
     if (pts->n != sc->n)  // algebra.go:350-352
@@ -1705,30 +1720,19 @@ static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc
                                        std::to_string(pts->n));
     if (c->q_len == PS_MSM_QUEUE) return fail(PS_ERR_ARG, "ps_msm_launch: PS_MSM_QUEUE sums are already pending on this context");
     HIP_TRY(hipSetDevice(c->device));
-    // a workspace no pending sum is using: the context itself first
-    static_assert(PS_MSM_QUEUE >= 1 && PS_MSM_QUEUE <= 6, "workspaces exist for at most six pending sums");
-    ps_ctx** slots[7] = {nullptr, &c->pipe, &c->pipe2, &c->aux, &c->pipe3, &c->pipe4, &c->pipe5};
-    ps_ctx* wc = nullptr;
-    for (int w = allow_self ? 0 : 1; w < (allow_self ? PS_MSM_QUEUE : PS_MSM_QUEUE + 1) && !wc; w++) {
-        ps_ctx* cand = w == 0 ? c : *slots[w];
+    // a workspace no pending sum is using: the context itself first if allowed, then the workers in the order of PS_LAUNCH_WORKERS
+    static_assert(PS_MSM_QUEUE >= 1 && PS_MSM_QUEUE <= PS_WORKERS, "workspaces exist for at most six pending sums");
+    MsmWorkspace* ws = nullptr;
+    for (int w = allow_self ? 0 : 1; w < (allow_self ? PS_MSM_QUEUE : PS_MSM_QUEUE + 1) && !ws; w++) {
+        MsmWorkspace* cand = w == 0 ? c : &c->workers[PS_LAUNCH_WORKERS[w - 1]];
         bool busy = false;
-        for (int j = 0; j < c->q_len; j++) busy = busy || (cand && c->q[(c->q_head + j) % PS_MSM_QUEUE].wc == cand);
+        for (int j = 0; j < c->q_len; j++) busy = busy || c->q[(c->q_head + j) % PS_MSM_QUEUE].ws == cand;
         if (busy) continue;
-        if (!cand) {
-            int rc = ps_ctx_create(c->device, slots[w]);
-            if (rc) return rc;
-            cand = *slots[w];
-        }
-        wc = cand;
+        int rc = w == 0 ? PS_OK : ctx_worker(c, PS_LAUNCH_WORKERS[w - 1], &cand);
+        if (rc) return rc;
+        ws = cand;
     }
-    if (!wc) return fail(PS_ERR_ARG, "ps_msm_launch: no free workspace");
-    if (wc != c) {
-        wc->timing = c->timing;
-        wc->forced_c = c->forced_c;
-        wc->forced_slice = c->forced_slice;
-        wc->forced_tail = c->forced_tail;
-        wc->forced_acc = c->forced_acc;
-    }
+    if (!ws) return fail(PS_ERR_ARG, "ps_msm_launch: no free workspace");
     // Inputs enqueued on the context stream before the FIRST launch of a burst are visible to the worker
     // streams: the fork event is recorded while the queue is empty, ahead of that launch's own kernels
     // (recording it later would order a worker's sort behind the running accumulation).  Arrays that a
@@ -1739,27 +1743,26 @@ static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc
     if (c->q_len == 0) HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
     ps_ctx::PendingMsm& e = c->q[(c->q_head + c->q_len) % PS_MSM_QUEUE];
     if (sc->n == 0) {
-        e = {pts->group, MsmPlan{}, wc};
+        e = {pts->group, MsmPlan{}, ws};
     } else {
         MsmPlan pl;
         int rc0 = msm_plan_checked(c, &pts, 1, sc->n, sc->max_bits, &pl);
         if (rc0) return rc0;
-        if (wc != c) HIP_TRY(hipStreamWaitEvent(wc->stream, c->ev_fork, 0));
+        if (ws != c) HIP_TRY(hipStreamWaitEvent(ws->stream, c->ev_fork, 0));
         const bool lone = pl.shortsum && c->q_len == 0;
-        if (!lone) HIP_TRY(hipStreamWaitEvent(wc->tail, c->ev_fork, 0));  // the sort runs on the workspace's high-priority stream
+        if (!lone) HIP_TRY(hipStreamWaitEvent(ws->tail, c->ev_fork, 0));  // the sort runs on the workspace's high-priority stream
         // chain the accumulations: this one starts when the previously launched one is done
         // ... unless the sum is short: accumulations of a few hundred thousand entries do not fill the chip, and chained
         // they are three launch latencies in a row (A/B on one box: Groth16 on 2^10 constraints 1.62 -> 1.54 ms, PHGR13 on 2^14 4.25 -> 3.9 ms;
         // below that the host's ~25 launches per sum are the bound)
         const bool chained = (u64)pl.W * sc->n >= PS_CHAIN_MIN_ENTRIES;
-        hipEvent_t wait = (chained && c->last_chain && c->last_chain != wc) ? c->last_chain->ev_acc_local : nullptr;
-        int rc = msm_launch_any(wc, pts, sc, pl, wait, nullptr, lone);
+        hipEvent_t wait = (chained && c->last_chain && c->last_chain != ws) ? c->last_chain->ev_acc_local : nullptr;
+        int rc = msm_launch_any(ws, pts, sc, pl, c->timing, wait, nullptr, lone);
         if (rc) return rc;
-        c->last_chain = wc;
-        e = {pts->group, pl, wc};
+        c->last_chain = ws;
+        e = {pts->group, pl, ws};
     }
     c->q_len++;
-    c->pending = true;
     return PS_OK;
 }
 extern "C" int ps_msm_launch(ps_ctx* c, const ps_points* pts, const ps_scalars* sc) { return msm_launch_impl(c, pts, sc, true); }
@@ -1770,19 +1773,18 @@ extern "C" int ps_msm_finish(ps_ctx* c, uint8_t* out) {
     const ps_ctx::PendingMsm e = c->q[c->q_head];
     c->q_head = (c->q_head + 1) % PS_MSM_QUEUE;
     c->q_len--;
-    c->pending = c->q_len > 0;
     const MsmPlan& pl = e.plan;
     if (pl.W == 0) {  // empty sum: the identity
         write_identity(e.group, out);
         return PS_OK;
     }
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(e.wc->ev_tail_done));  // the copy of the results: the last thing the sum enqueued (tail stream, or its own stream for a lone short sum)
-    if (e.group == PS_G1) msm_fold_host<Fp>(e.wc, pl, 0, out);
-    else msm_fold_host<Fp2>(e.wc, pl, 0, out);
-    c->last_info = ps_msm_info{pl.c, pl.W, msm_entries(e.wc, pl, e.group), pl.G, pl.M, pl.table ? 1 : 0};
-    c->last_acc = msm_acc_path(e.wc, pl);
-    c->last_timed = e.wc;
+    HIP_TRY(hipEventSynchronize(e.ws->ev_tail_done));  // the copy of the results: the last thing the sum enqueued (tail stream, or its own stream for a lone short sum)
+    if (e.group == PS_G1) msm_fold_host<Fp>(e.ws, pl, 0, out);
+    else msm_fold_host<Fp2>(e.ws, pl, 0, out);
+    c->last_info = ps_msm_info{pl.c, pl.W, msm_entries(e.ws, pl, e.group), pl.G, pl.M, pl.table ? 1 : 0};
+    c->last_acc = msm_acc_path(e.ws, pl);
+    c->last_timed = e.ws;
     return PS_OK;
 }
 
@@ -1868,13 +1870,12 @@ extern "C" int ps_ctx_set_timing(ps_ctx* c, int enable) {
     if (!c) return fail(PS_ERR_ARG, "ctx is NULL");
     c->timing = enable != 0;
     c->ev_valid = false;
-    for (ps_ctx* w : {c->pipe, c->pipe2, c->aux, c->pipe3, c->pipe4, c->pipe5})
-        if (w) { w->timing = c->timing; w->ev_valid = false; }
+    for (MsmWorkspace& w : c->workers) w.ev_valid = false;
     return PS_OK;
 }
 extern "C" int ps_msm_last_stage_ms(ps_ctx* c, float* ms) {
     if (!c || !ms) return fail(PS_ERR_ARG, "NULL argument");
-    const ps_ctx* t = c->last_timed ? c->last_timed : c;  // the workspace of the sum finished last
+    const MsmWorkspace* t = c->last_timed ? c->last_timed : c;  // the workspace of the sum finished last
     if (!t->ev_valid) return fail(PS_ERR_ARG, "no timed MSM on this context (ps_ctx_set_timing)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipEventSynchronize(t->ev[PS_MSM_STAGES]));

@@ -84,7 +84,7 @@ static int monomial_to_lagrange_t(ps_ctx* c, const ps_qap* q, const ps_points* m
     ec_ntt<F, true>(tb, st, A, 2 * npu, lognp + 1);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)cnt * LN)), dim3(256), 0, st, A, (u32)cnt, (const Fr*)qt.invfact, ~0ull);
     // canonical affine points (the chain products of the batch normalisation go behind the cnt points: A holds 2 np)
-    batch_to_affine<F>(c, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    batch_to_affine<F>(c->stream, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "kernels", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(who, "run", e);
     return scope.finish(PS_OK);
@@ -121,7 +121,7 @@ static int points_scale_each_t(ps_ctx* c, const ps_points* pts, const Fr* k_mont
     if (storage_wait_ready(pts->st, st)) return fail_hip(who, "event wait", hipErrorUnknown);
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, (Xyzz<F>*)buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (Xyzz<F>*)buf, (u32)n, k_mont, ~0ull);
-    batch_to_affine<F>(c, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    batch_to_affine<F>(c->stream, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return fail_hip(who, "kernels", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(who, "run", e);
     return scope.finish(PS_OK);

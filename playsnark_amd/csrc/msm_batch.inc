@@ -63,23 +63,23 @@ static int msm_batch_table_window(const ps_ctx* c, const ps_points* const* pts, 
 
 // The two-level sort of msm_sort over the virtual array of kc * n scalars (msm_batch.hpp): member j's n scalars start at
 // scalar index j * stride of `scal` (ps_msm_batch: stride == n, the members back to back).
-static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, size_t kc, int fold_neg, const MsmPlan& pl, bool timed,
+static int msm_batch_sort(MsmWorkspace* ws, const u32* scal, size_t n, size_t stride, size_t kc, int fold_neg, const MsmPlan& pl, bool timed,
                           hipStream_t st) {
     const u64 N = (u64)kc * n;
     const u64 total = (u64)pl.W * N;  // upper bound on entries
     const u64 G = pl.G;
     if (G > SORT_MAX_BUCKETS || total >= (1ull << 31)) return fail(PS_ERR_ARG, "ps_msm_batch: internal: pass outside the sort's limits");
     int rc;
-    if ((rc = c->counts.ensure(4 * G))) return rc;
-    if ((rc = c->offs.ensure(4 * (G + 1)))) return rc;
-    if ((rc = c->keys.ensure(4 * total))) return rc;
-    if ((rc = c->ranks.ensure(4 * total))) return rc;
-    if ((rc = c->vals.ensure(4 * total))) return rc;
-    if ((rc = c->sorted.ensure(4 * total + 4))) return rc;
-    if ((rc = c->coarse.ensure(4 * (4 * (size_t)SORT_MAX_COARSE + 8)))) return rc;
-    if (c->tail_used) HIP_TRY(hipStreamWaitEvent(st, c->ev_tail_done, 0));  // the last tail still reads offs
+    if ((rc = ws->counts.ensure(4 * G))) return rc;
+    if ((rc = ws->offs.ensure(4 * (G + 1)))) return rc;
+    if ((rc = ws->keys.ensure(4 * total))) return rc;
+    if ((rc = ws->ranks.ensure(4 * total))) return rc;
+    if ((rc = ws->vals.ensure(4 * total))) return rc;
+    if ((rc = ws->sorted.ensure(4 * total + 4))) return rc;
+    if ((rc = ws->coarse.ensure(4 * (4 * (size_t)SORT_MAX_COARSE + 8)))) return rc;
+    if (ws->tail_used) HIP_TRY(hipStreamWaitEvent(st, ws->ev_tail_done, 0));  // the last tail still reads offs
     int evi = 0;
-#define PS_BATCH_MARK() do { if (timed) HIP_TRY(hipEventRecord(c->ev[evi++], st)); } while (0)
+#define PS_BATCH_MARK() do { if (timed) HIP_TRY(hipEventRecord(ws->ev[evi++], st)); } while (0)
     PS_BATCH_MARK();  // 0: start
     DigitConst cadd{};
     for (int w = 0; w + 1 < pl.W; w++) {
@@ -89,37 +89,37 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, s
     int fb = 5;  // fine bits: as few as keep the coarse bins within SORT_MAX_COARSE
     while (((G + (1ull << fb) - 1) >> fb) > SORT_MAX_COARSE) fb++;
     const u32 ncoarse = (u32)((G + (1ull << fb) - 1) >> fb);
-    u32* coarse_cnt = (u32*)c->coarse.p;
+    u32* coarse_cnt = (u32*)ws->coarse.p;
     u32* coarse_off = coarse_cnt + SORT_MAX_COARSE + 1;
     u32* coarse_cur = coarse_off + SORT_MAX_COARSE + 1;
     u32* tile_base = coarse_cur + SORT_MAX_COARSE + 1;
     HIP_TRY(hipMemsetAsync(coarse_cnt, 0, 4 * SORT_MAX_COARSE, st));
     const bool may_have_big_bins = total > SORT_BIG;
-    if (may_have_big_bins) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 4 * G, st));
+    if (may_have_big_bins) HIP_TRY(hipMemsetAsync(ws->counts.p, 0, 4 * G, st));
     const dim3 cgrid((unsigned)((N + (size_t)COUNT_PER_THREAD * DIGITS_THREADS - 1) / ((size_t)COUNT_PER_THREAD * DIGITS_THREADS)));
     const dim3 dgrid((unsigned)((N + DIGITS_CHUNK - 1) / DIGITS_CHUNK), (unsigned)pl.W);
     // over a window table the key is member * NB + digit and the entry names its window (msm_batch.hpp)
     const auto k_count = pl.table ? k_sort_count_batch_tab : k_sort_count_batch;
     const auto k_partition = pl.table ? k_sort_partition_batch_tab : k_sort_partition_batch;
     hipLaunchKernelGGL(k_count, cgrid, dim3(DIGITS_THREADS), 0, st, scal, (u32)n, (u32)stride, (u32)N,
-                       pl.c, pl.W, pl.NB, cadd, fold_neg, ncoarse, fb, (u32*)c->ranks.p, coarse_cnt);
+                       pl.c, pl.W, pl.NB, cadd, fold_neg, ncoarse, fb, (u32*)ws->ranks.p, coarse_cnt);
     PS_BATCH_MARK();  // 1: after digits + coarse histogram
     hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_MAX_COARSE), 0, st, (const u32*)coarse_cnt, ncoarse, coarse_off, coarse_cur,
-                       (u32*)c->offs.p + G, tile_base);
+                       (u32*)ws->offs.p + G, tile_base);
     hipLaunchKernelGGL(k_partition, dgrid, dim3(DIGITS_THREADS), 2 * DIGITS_CHUNK * sizeof(u32), st,
-                       (const u32*)c->ranks.p, (u32)n, (u32)N, pl.W, pl.NB, fb, coarse_cur, (unsigned short*)c->keys.p, (u32*)c->vals.p);
+                       (const u32*)ws->ranks.p, (u32)n, (u32)N, pl.W, pl.NB, fb, coarse_cur, (unsigned short*)ws->keys.p, (u32*)ws->vals.p);
     PS_BATCH_MARK();  // 2: after scan + partition
-    hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p, (const u32*)c->vals.p,
-                       (const u32*)coarse_off, (u32)G, fb, (u32*)c->offs.p, (u32*)c->sorted.p);
+    hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p, (const u32*)ws->vals.p,
+                       (const u32*)coarse_off, (u32)G, fb, (u32*)ws->offs.p, (u32*)ws->sorted.p);
     if (may_have_big_bins) {
         const unsigned big_grid = (unsigned)std::min<u64>(2048, total / SORT_TILE + 1);
-        hipLaunchKernelGGL(k_sort_big_count, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p, (const u32*)coarse_off,
-                           (const u32*)tile_base, ncoarse, fb, (u32*)c->counts.p);
-        hipLaunchKernelGGL(k_sort_big_scan, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const u32*)coarse_off, (u32)G, fb, (u32*)c->counts.p,
-                           (u32*)c->offs.p);
-        hipLaunchKernelGGL(k_sort_big_scatter, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)c->keys.p,
-                           (const u32*)c->vals.p, (const u32*)coarse_off, (const u32*)tile_base, ncoarse, fb, (u32*)c->counts.p,
-                           (u32*)c->sorted.p);
+        hipLaunchKernelGGL(k_sort_big_count, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p, (const u32*)coarse_off,
+                           (const u32*)tile_base, ncoarse, fb, (u32*)ws->counts.p);
+        hipLaunchKernelGGL(k_sort_big_scan, dim3(ncoarse), dim3(SORT_FINE), 0, st, (const u32*)coarse_off, (u32)G, fb, (u32*)ws->counts.p,
+                           (u32*)ws->offs.p);
+        hipLaunchKernelGGL(k_sort_big_scatter, dim3(big_grid), dim3(SORT_FINE), 0, st, (const unsigned short*)ws->keys.p,
+                           (const u32*)ws->vals.p, (const u32*)coarse_off, (const u32*)tile_base, ncoarse, fb, (u32*)ws->counts.p,
+                           (u32*)ws->sorted.p);
     }
     PS_BATCH_MARK();  // 3: after the fine sort
 #undef PS_BATCH_MARK
@@ -132,18 +132,18 @@ static int msm_batch_sort(ps_ctx* c, const u32* scal, size_t n, size_t stride, s
 // (more arrays than workspaces) keeps every array's bytes until the copies at the end of the pass.
 struct BatchOut { size_t affine_bytes, slot_bytes; };
 
-// One array's share of a pass: the point pass over the sort that `c` owns (sorted / offs), the fold per member (plain pass;
-// over a window table the set sums ARE the members' sums), the normalisation and the encoding -- all on workspace wc's
-// stream and in wc's buffers (wc == c: ps_msm_batch).  The kc * wb wire bytes are left in slot `slot` of wc->mb_out.
+// One array's share of a pass: the point pass over the sort that the context `c` owns (sorted / offs), the fold per member
+// (plain pass; over a window table the set sums ARE the members' sums), the normalisation and the encoding -- all on workspace
+// rw's stream and in rw's buffers (rw == c: ps_msm_batch).  The kc * wb wire bytes are left in slot `slot` of rw->mb_out.
 template <class F>
-static int msm_batch_points(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t n, size_t kc, const MsmPlan& pl, bool timed,
+static int msm_batch_points(ps_ctx* c, MsmWorkspace* rw, const ps_points* pts, size_t n, size_t kc, const MsmPlan& pl, bool timed,
                             const BatchOut& lay, size_t slot) {
     typedef typename KernelField<F>::type KF;
     constexpr unsigned LN = FieldTraits<KF>::LANES;
-    hipStream_t st = wc->stream;
+    hipStream_t st = rw->stream;
     int rc;
     Xyzz<F>* dsets = nullptr;
-    if ((rc = msm_points_t<F>(c, wc, pts, kc * n, pl, timed, 0, nullptr, nullptr, true, &dsets, n))) return rc;
+    if ((rc = msm_points_t<F>(c, rw, pts, kc * n, pl, timed, 0, nullptr, nullptr, true, &dsets, n))) return rc;
     if (timed) {
         for (auto& e : c->mb_ev) if (!e) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipEventRecord(c->mb_ev[0], st));
@@ -151,18 +151,18 @@ static int msm_batch_points(ps_ctx* c, ps_ctx* wc, const ps_points* pts, size_t 
     if (pl.table) {
         // batch_to_affine with the points where k_reduce_weights left them; mb_fold holds the chain products alone
         const u32 T = (u32)std::min<size_t>(65536, std::max<size_t>(1, kc / 16));
-        hipLaunchKernelGGL(k_batch_to_affine<F>, dim3(nblocks(T)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, T, (Fp*)wc->mb_fold.p,
-                           (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+        hipLaunchKernelGGL(k_batch_to_affine<F>, dim3(nblocks(T)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, T, (Fp*)rw->mb_fold.p,
+                           (char*)rw->mb_out.p, (u32)sizeof(Affine<F>));
     } else {
         hipLaunchKernelGGL(k_batch_fold<KF>, dim3(nblocks(kc * LN)), dim3(256), 0, st, (const Xyzz<F>*)dsets, (u32)kc, pl.W, pl.c,
-                           (Xyzz<F>*)wc->mb_fold.p);
-        batch_to_affine<F>(wc, (char*)wc->mb_fold.p, kc, (char*)wc->mb_out.p, (u32)sizeof(Affine<F>));
+                           (Xyzz<F>*)rw->mb_fold.p);
+        batch_to_affine<F>(st, (char*)rw->mb_fold.p, kc, (char*)rw->mb_out.p, (u32)sizeof(Affine<F>));
     }
-    uint8_t* d_bytes = (uint8_t*)wc->mb_out.p + lay.affine_bytes + slot * lay.slot_bytes;
+    uint8_t* d_bytes = (uint8_t*)rw->mb_out.p + lay.affine_bytes + slot * lay.slot_bytes;
     if (pts->group == PS_G1)
-        hipLaunchKernelGGL(k_points_to_bytes_g1, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp>*)wc->mb_out.p, (u32)kc, d_bytes);
+        hipLaunchKernelGGL(k_points_to_bytes_g1, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp>*)rw->mb_out.p, (u32)kc, d_bytes);
     else
-        hipLaunchKernelGGL(k_points_to_bytes_g2, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp2>*)wc->mb_out.p, (u32)kc, d_bytes);
+        hipLaunchKernelGGL(k_points_to_bytes_g2, dim3(nblocks(kc)), dim3(256), 0, st, (const Affine<Fp2>*)rw->mb_out.p, (u32)kc, d_bytes);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(c->mb_ev[1], st));
     return PS_OK;
@@ -177,7 +177,7 @@ static inline size_t msm_batch_used(size_t a) { return std::min<size_t>(a, PS_MU
 // arrays (serial chains of ~250 doublings) sit on different streams and run side by side; a workspace that serves a second
 // array takes it up behind its own fold, in stream order.  Every array's launches are enqueued before the first copy: a
 // copy to pageable memory holds the host until its stream has drained.  The caller synchronises behind the last pass.
-static int msm_batch_pass(ps_ctx* c, ps_ctx* const* ring, const ps_points* const* pts, size_t a, const u32* scal, size_t n, size_t stride,
+static int msm_batch_pass(ps_ctx* c, MsmWorkspace* const* ring, const ps_points* const* pts, size_t a, const u32* scal, size_t n, size_t stride,
                           size_t first, size_t kc, int fold_neg, const MsmPlan& one, int plan_group, uint8_t* const* out) {
     const MsmPlan pl = msm_batch_plan(c, one, n, kc, plan_group);
     const size_t used = msm_batch_used(a);
@@ -209,18 +209,18 @@ static int msm_batch_pass(ps_ctx* c, ps_ctx* const* ring, const ps_points* const
             if (ring[j] != c) HIP_TRY(hipStreamWaitEvent(ring[j]->stream, c->ev_sorted, 0));
     }
     for (size_t i = 0; i < a; i++) {
-        ps_ctx* wc = ring[i % PS_MULTI_RING];
-        rc = pts[i]->group == PS_G1 ? msm_batch_points<Fp>(c, wc, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING)
-                                    : msm_batch_points<Fp2>(c, wc, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING);
+        MsmWorkspace* rw = ring[i % PS_MULTI_RING];
+        rc = pts[i]->group == PS_G1 ? msm_batch_points<Fp>(c, rw, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING)
+                                    : msm_batch_points<Fp2>(c, rw, pts[i], n, kc, pl, timed, lay, i / PS_MULTI_RING);
         if (rc) return rc;
     }
     c->ev_valid = timed;
     c->last_timed = c;
     for (size_t i = 0; i < a; i++) {
-        ps_ctx* wc = ring[i % PS_MULTI_RING];
+        MsmWorkspace* rw = ring[i % PS_MULTI_RING];
         const size_t wb = wire_bytes(pts[i]->group);
-        const uint8_t* d_bytes = (const uint8_t*)wc->mb_out.p + lay.affine_bytes + (i / PS_MULTI_RING) * lay.slot_bytes;
-        HIP_TRY(hipMemcpyAsync(out[i] + first * wb, d_bytes, kc * wb, hipMemcpyDeviceToHost, wc->stream));
+        const uint8_t* d_bytes = (const uint8_t*)rw->mb_out.p + lay.affine_bytes + (i / PS_MULTI_RING) * lay.slot_bytes;
+        HIP_TRY(hipMemcpyAsync(out[i] + first * wb, d_bytes, kc * wb, hipMemcpyDeviceToHost, rw->stream));
     }
     // the results of this pass are read and the tails' buffers free before the next pass reuses them (same streams), and the
     // workspaces' other users order themselves behind ev_tail_done as behind any sum
@@ -230,7 +230,7 @@ static int msm_batch_pass(ps_ctx* c, ps_ctx* const* ring, const ps_points* const
 }
 
 // every workspace the call used is idle when it returns, whatever happened: the next call on the context starts clean
-static int msm_batch_drain(ps_ctx* const* ring, size_t a) {
+static int msm_batch_drain(MsmWorkspace* const* ring, size_t a) {
     hipError_t first = hipSuccess;
     for (size_t j = 0; j < msm_batch_used(a); j++) {
         const hipError_t e = hipStreamSynchronize(ring[j]->stream);
@@ -278,7 +278,7 @@ static int msm_batch_run(ps_ctx* c, const ps_points* const* pts, size_t a, const
             }
         return PS_OK;
     }
-    ps_ctx* ring[PS_MULTI_RING];
+    MsmWorkspace* ring[PS_MULTI_RING];
     int rc = msm_multi_ring(c, true, a, ring);
     if (rc) return rc;
     if (storage_wait_ready(sc->st, c->stream)) return fail(PS_ERR_HIP, "ps_msm_batch: event wait failed");  // asynchronously produced scalars
@@ -329,8 +329,7 @@ extern "C" int ps_msm_batch_multi(ps_ctx* c, const ps_points* const* pts, size_t
     if (a > PS_MSM_MULTI_MAX) return fail(PS_ERR_ARG, "ps_msm_batch_multi: more than PS_MSM_MULTI_MAX point arrays");
     for (size_t i = 0; i < a; i++)
         if (!pts[i] || (k && !out[i])) return fail(PS_ERR_ARG, "ps_msm_batch_multi: NULL argument");
-    if (c->q_len || c->pending || (c->aux && c->aux->pending))
-        return fail(PS_ERR_ARG, "ps_msm_batch_multi: sums are pending on this context (ps_msm_finish them first)");
+    if (c->q_len) return fail(PS_ERR_ARG, "ps_msm_batch_multi: sums are pending on this context (ps_msm_finish them first)");
     if (a == 0) return PS_OK;
     const size_t n = pts[0]->n;
     for (size_t i = 1; i < a; i++)

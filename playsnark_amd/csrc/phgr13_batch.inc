@@ -33,7 +33,7 @@ extern "C" int ps_phgr13_prove_batch(ps_ctx* c, const ps_phgr13_ek* ek, const ps
     if (m && k > (size_t)-1 / m) return fail(PS_ERR_ARG, "ps_phgr13_prove_batch: batch too long (split it)");
     if (sols->n != k * m) return fail(PS_ERR_ARG, "different number of solution variables than left polynomials");  // sanityCheck, qap.go:177-189
     if (n < 2) return fail(PS_ERR_ARG, "ps_phgr13_prove_batch: needs at least 2 gates");
-    if (ctx_busy(c) || c->q_len) return fail(PS_ERR_ARG, "ps_phgr13_prove_batch: an MSM is pending on this context");
+    if (ctx_busy(c)) return fail(PS_ERR_ARG, "ps_phgr13_prove_batch: an MSM is pending on this context");
     if (k == 0) return PS_OK;
     if ((u64)k * m >= (1ull << 31) || (u64)k * (n - 1) >= (1ull << 31)) return fail(PS_ERR_ARG, "ps_phgr13_prove_batch: batch too long (split it)");
     HIP_TRY(hipSetDevice(c->device));

@@ -739,7 +739,7 @@ static inline const u32* small_slot(const ps_ctx* c, int i) { return (const u32*
 
 // Groth16Prove as three sums (see the header of this section):
 //   SA = [A | r | 1] . PA,   SB = [B | s | 1] . PB (G2),   SC = [sol_nio | h | sA + rB | rs | s | r] . PC
-// The quotient runs first, alone, on the context's high-priority stream; the sums follow on the worker contexts.
+// The quotient runs first, alone, on the context's high-priority stream; the sums follow on the workers (the workspaces beside the context's own).
 // Running them beside each other was measured and dropped (n = 2^20): sums that need no polynomial started at once made
 // the quotient 2.4 x slower (11.9 -> 29 ms) for the same total -- the NTT passes are VALU-bound by instructions, the
 // bucket accumulations by multiplications, so neither has idle issue slots to lend -- and even the digit sorts alone
@@ -829,7 +829,7 @@ static int g16_quotient_stage(ps_ctx* c, const ps_qap* q, const ps_scalars* sol,
 #endif
 static_assert(PS_PROVER_QUEUE <= PS_MSM_QUEUE, "the provers use the context's queue");
 // ---- shared by every prover (here and in prove_shares.inc) ----
-static bool ctx_busy(const ps_ctx* c) { return c->pending || (c->aux && c->aux->pending); }
+static bool ctx_busy(const ps_ctx* c) { return c->q_len > 0; }
 static float ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
 }

@@ -204,7 +204,7 @@ typedef std::function<int(ps_scalars**)> Phgr13GetH;
 
 // The sums of one share on context c.  Order of work (measured at n = 2^20, see groth16_prove_impl): the quotient has run
 // first and alone -- its NTT passes and the bucket accumulations are both VALU-bound, sharing the chip only stretches the
-// quotient --, then the h(s) sum on the context itself and the seven solution sums (one digit sort) on worker contexts, every
+// quotient --, then the h(s) sum on the context itself and the seven solution sums (one digit sort) on workers, every
 // point pass chained behind the previous one.
 // h_first: h is at hand (the quotient ran on this context).  The digit sort of the seven sums first (on a worker stream; no
 // fork event: nothing it reads is still being produced), then the h(s) sum -- ghs := hx.BlindEval(zeroG1, ek.gsi),
@@ -217,7 +217,7 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     if (ctx_busy(c)) return fail(PS_ERR_ARG, "PHGR13 share: an MSM is pending on this context");
     uint8_t* dst[7] = {out->vss, out->wss, out->yss, out->vass, out->wass, out->yass, out->gz};
     const size_t cnt = sh.sv->n;
-    ps_ctx* ring[PS_MULTI_RING] = {nullptr, nullptr, nullptr, nullptr};
+    MsmWorkspace* ring[PS_MULTI_RING] = {nullptr, nullptr, nullptr, nullptr};
     MsmPlan mpl{};
     Scope scope;
     ps_scalars** h = scope.scalars();
@@ -249,9 +249,8 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     }
     if (!rc && !h_first) rc = launch_h();
     if (rc) {  // what is in flight finishes before its buffers can be reused
-        for (ps_ctx* w : ring)
-            if (w) (void)ps_ctx_sync(w);
-        (void)ps_ctx_sync(c);
+        for (MsmWorkspace* w : ring) if (w) (void)w->sync();
+        (void)c->sync();
     }
     uint8_t dump[96];
     if (h_launched) {
@@ -294,8 +293,8 @@ extern "C" int ps_phgr13_prove(ps_ctx* c, const ps_phgr13_ek* ek, const ps_qap* 
     const bool multi = same_len && nn > 0;  // what NewPHGR13TrustedSetup produces: the share prover, as rank 0 of 1
     int rc = phgr13_prepare(c, ek, multi ? nn : 0, gsi);
     if (rc) return rc;
-    if (multi) {  // the worker contexts exist before the quotient runs (a fresh context makes them here, not inside phase 1)
-        ps_ctx* ring[PS_MULTI_RING];
+    if (multi) {  // the workers exist before the quotient runs (a fresh context makes them here, not inside phase 1)
+        MsmWorkspace* ring[PS_MULTI_RING];
         if ((rc = msm_multi_ring(c, false, 7, ring))) return rc;
         if (ctx_busy(c)) return fail(PS_ERR_ARG, "ps_phgr13_prove: an MSM is pending on this context");
     }
@@ -588,7 +587,7 @@ static int g16_lagrange_share(ps_ctx* c, const G16LocalShare& sh, const uint8_t*
     if (!rc) rc = ps_scalars_slice(sol, diff + fq, cq, sn);
     if (rc) return rc;
     // the share's own kernels run on the context's high-priority stream, as the quotient of groth16_prove_impl does: the sums
-    // launched right behind them (worker contexts) must not hold back what every other device may be waiting for
+    // launched right behind them (workers) must not hold back what every other device may be waiting for
     hipStream_t qs = c->tail;
     SumQueue sums{c, false};
     uint8_t part[5][192];

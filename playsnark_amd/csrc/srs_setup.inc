@@ -45,7 +45,7 @@ static int column_sums_t(ps_ctx* c, const ps_qap* q, int which, const ps_points*
             if ((e = hipMemsetAsync(buf + sizeof(Xyzz<F>) * t.long_wide_h[k], 0, sizeof(Xyzz<F>), st)) != hipSuccess)
                 return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: hipMemsetAsync: ") + hipGetErrorString(e));
     }
-    batch_to_affine<F>(c, buf, m, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    batch_to_affine<F>(c->stream, buf, m, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: kernels: ") + hipGetErrorString(e));
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_qap_column_sums: run: ") + hipGetErrorString(e));
     // A long row that holds a wide entry is a multi-scalar multiplication, sum_e v_e P[col_e], of thousands of full-width
@@ -103,7 +103,7 @@ static int points_scale_uniform_t(ps_ctx* c, const ps_points* pts, const Fr& k_m
     if (storage_wait_ready(pts->st, st)) return fail(PS_ERR_HIP, "scaling a point array: event wait failed");
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(pts), (u32)n, (u32)n, (Xyzz<F>*)buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, (Xyzz<F>*)buf, (u32)n, (const Fr*)km, 0ull);
-    batch_to_affine<F>(c, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    batch_to_affine<F>(c->stream, buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("scaling a point array: kernels: ") + hipGetErrorString(e));
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("scaling a point array: run: ") + hipGetErrorString(e));
     return scope.finish(PS_OK);
@@ -141,7 +141,7 @@ static int srs_xi_t(ps_ctx* c, const ps_qap* q, const ps_points* tau, ps_points*
     ec_ntt<F, false>(tb, st, A, S, p);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, A, S, (const Fr*)t1, ~0ull);
     ec_ntt<F, true>(tb, st, A, S, p);
-    batch_to_affine<F>(c, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    batch_to_affine<F>(c->stream, (char*)A, cnt, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
     if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: kernels: ") + hipGetErrorString(e));
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, std::string("ps_groth16_setup_from_srs: run: ") + hipGetErrorString(e));
     return scope.finish(PS_OK);

@@ -125,7 +125,7 @@ static int points_scale_g1(ps_ctx* c, const ps_points* pts, const Fr* k_mont, ps
     Xyzz<Fp>* buf = (Xyzz<Fp>*)c->vb_xyzz.p;
     hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, c->stream, (const Affine<Fp>*)points_ptr(pts), (u32)n, (u32)n, buf);
     hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks(n * LN)), dim3(256), 0, c->stream, buf, (u32)n, k_mont, ~0ull);
-    batch_to_affine<Fp>(c, (char*)buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<Fp>));
+    batch_to_affine<Fp>(c->stream, (char*)buf, n, (char*)(*out)->st->p, (u32)sizeof(Affine<Fp>));
     if (hipGetLastError() != hipSuccess) return fail(PS_ERR_HIP, "ps_groth16_verify_batch: scaling kernels failed to launch");
     return scope.finish(PS_OK);
 }

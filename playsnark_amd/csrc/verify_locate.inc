@@ -139,7 +139,7 @@ static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep
         HIP_TRY(hipMemsetAsync(norm, 0, sizeof(Xyzz<Fp>) * K, c->stream));  // X_S is the identity (ZZ = 0)
     }
     gather(t.pts + t.off[l], d_idx, K, WX, 0, WX, norm + K);
-    batch_to_affine<Fp>(c, (char*)norm, 2 * K, w + o_a, (u32)sizeof(Affine<Fp>));
+    batch_to_affine<Fp>(c->stream, (char*)norm, 2 * K, w + o_a, (u32)sizeof(Affine<Fp>));
     HIP_TRY(hipGetLastError());
     std::vector<D12> hf(K);
     std::vector<u32> hr(8 * K);

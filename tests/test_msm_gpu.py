@@ -926,3 +926,54 @@ def test_multi_sum_over_both_groups_shares_one_tail_plan(ps_api, ctx, co, pr, n,
                 assert ps_api.msm_multi(ctx, pts, dsc) == want, (n, table, mode)
     finally:
         ctx.set_tail(0)
+
+
+@pytest.fixture(scope="module")
+def worker_timing_jobs(co, pr):
+    """One G1 and one G2 sum of 300 points, (name, scalars, point bytes, the oracle's result bytes); computed once."""
+    rng = _rng(pr, 9300)
+    jobs = {}
+    for name, og in (("g1", co.G1), ("g2", co.G2)):
+        sc = [rng.fr() for _ in range(300)]
+        raw = og.gen_points(rng.fr(), rng.fr(), 300)
+        jobs[name] = (sc, raw, og.to_b(og.msm_pippenger(co.pack_fr(sc), raw, 300, 4)))
+    return jobs
+
+
+@pytest.mark.parametrize("first", ["g1", "g2"])
+def test_stage_times_of_sums_in_flight(ps_api, worker_timing_jobs, first):
+    """ps_msm_last_stage_ms after every finish of a full queue: the first sum of a burst runs on the context's own
+    workspace, the others on worker workspaces, and the stage times are those of the workspace the finished sum ran on.
+    Timed: every stage finite and >= 0 and the bytes the oracle's.  With timing switched off again a burst on the same
+    context leaves no stage times, on whichever workspace, as on a fresh context."""
+    import math
+
+    from playsnark_amd import _lib
+
+    cx = ps_api.Context(0)
+    try:
+        with pytest.raises(ps_api.PlaysnarkError, match="no timed MSM"):
+            cx.last_stage_ms()
+        order = (("g1", "g2") if first == "g1" else ("g2", "g1")) * (_lib.PS_MSM_QUEUE // 2)
+        assert len(order) == _lib.PS_MSM_QUEUE
+        gid = {"g1": ps_api.G1, "g2": ps_api.G2}
+        dev = {name: (ps_api.Points.upload(cx, gid[name], raw), ps_api.Poly.upload(cx, sc))
+               for name, (sc, raw, _) in worker_timing_jobs.items()}
+        cx.set_timing(True)
+        for name in order:
+            ps_api.msm_launch(cx, *dev[name])
+        for i, name in enumerate(order):
+            assert ps_api.msm_finish(cx, gid[name]) == worker_timing_jobs[name][2], (i, name)
+            ms = cx.last_stage_ms()
+            print("[stage ms]", first, i, name, ms)
+            assert set(ms) == set(cx.STAGES)
+            assert all(math.isfinite(v) and v >= 0 for v in ms.values()), (i, name, ms)
+        cx.set_timing(False)
+        for name in order:
+            ps_api.msm_launch(cx, *dev[name])
+        for i, name in enumerate(order):
+            assert ps_api.msm_finish(cx, gid[name]) == worker_timing_jobs[name][2], (i, name)
+            with pytest.raises(ps_api.PlaysnarkError, match="no timed MSM"):
+                cx.last_stage_ms()
+    finally:
+        cx.close()
