@@ -57,7 +57,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_groth16_srs_contribute (with the new ps_groth16_srs_share), ps_groth16_srs_check and ps_groth16_srs_check_update;
  *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
  *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch;
- *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table. */
+ *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table;
+ *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -717,6 +718,47 @@ int ps_groth16_verify_batch_locate(ps_ctx* ctx, const ps_groth16_vk* vk, const p
                                    size_t nproofs, const uint8_t* rho_be32, uint8_t* valid /* nproofs bytes: 1 / 0 */,
                                    size_t* ninvalid);
 int ps_groth16_verify_batch_locate_info(ps_ctx* ctx, ps_verify_locate_info* out); /* of the last locate call on ctx */
+
+/* PHGR13Verify (pinochio.go:281-378) for nproofs proofs under ONE key, by random linear combination.  With diff =
+ * len(vk->vs_io), io proof-major (io_ij, len(io) != nproofs * diff: PS_ERR_LENGTH), gv_i = sum_j io_ij vs_j + vss_i and
+ * S_X = sum_i rho_i X_i for a proof element X, the five products of ps_phgr13_verify become
+ *     E0 division  prod_i e(rho_i gv_i, wss_i) * prod_k e(P_k, ws_k) * e(-S_hs, yts) * e(-(S_yss + sum_j t_j ys_j), G2) == 1
+ *                  P_k = sum_i io_ik (rho_i gv_i),  t_j = sum_i rho_i io_ij
+ *     E1 v         e(S_vass, G2) * e(-S_vss, av) == 1
+ *     E2 w         e(S_wass, G2) * e(-aw, S_wss) == 1
+ *     E3 y         e(S_yass, G2) * e(-S_yss, ay) == 1
+ *     E4 linear    e(S_gz, gamma) * e(-(S_vss + S_yss), bgamma2) * e(-bgamma, S_wss) == 1
+ * -- nproofs + diff Miller loops on the device (E0 with the G2 commitment of the inputs expanded by bilinearity: no G2
+ * arithmetic per proof), the eight S_X as one ps_msm_multi, eleven host Miller loops, and FIVE final exponentiations: each
+ * product is checked on its own.  *ok = 1 iff all five hold; all five are always evaluated.
+ * Soundness: each E_c is linear in rho and GT has prime order, so if some proof violates equation c, E_c still holds only
+ * with probability <= nproofs / 2^bits(rho) over the choice of rho, as for ps_groth16_verify_batch.  rho_be32: nproofs x
+ * 32 B, canonical (PS_ERR_ENCODING), non-zero (PS_ERR_ARG), drawn by the caller AFTER the proofs are fixed; 128 random bits
+ * each are enough.  The five are NOT merged into one product: under equal weights the errors of two equations of one proof
+ * could cancel (vass + D with wass - D).
+ * Every point is untrusted, as in ps_phgr13_verify: encoding, curve and subgroup, PS_ERR_ENCODING otherwise, and
+ * ps_last_error() names the proof index and the element of a bad proof point.  A malformed proof fails the CALL: there is
+ * no per-proof verdict (a rejected batch can be halved by the caller).  vs_io, ws_io, ys_io of different lengths:
+ * PS_ERR_LENGTH.  diff = 0 is legal.  nproofs = 0: *ok = 1.  nproofs = 1 with rho = 1 gives the verdict of ps_phgr13_verify.
+ * Needs an empty MSM queue (PS_ERR_ARG), like every one-call form.
+ * Caps, checked before any device work: nproofs <= 2^20 and nproofs * (diff + 1) < 2^24; PS_ERR_ARG beyond, with a message
+ * that says to split the batch (the verdicts of the parts AND together).
+ * Device memory, kept by the context: per proof 1 008 B of Miller values and 800 B of points and weights, and per proof and
+ * per public input 448 B for the two XYZZ buffers of the scaled key points and 104 B of scalars (7.5 GB + 1.7 GB at the
+ * second cap); for the duration of the call also the proofs and both sides of the device's loops (1 344 B per proof) and
+ * the transposed inputs (32 B per proof and input).  A context that cannot get them fails with PS_ERR_HIP.
+ * Cost: a call costs 45-55 ms up to ~256 proofs (subgroup tests, scaling and Miller loops are latency chains of one lane each): a lone proof is
+ * 10 times slower than ps_phgr13_verify (53 against 4.6 ms at diff = 6), the batch wins from 16 proofs on (the crossover lies between 1 and 16), is 70 times
+ * faster at 1 024 and costs 21.3 us per proof at 4 096 with diff = 6, 15.1 us with diff = 63 (225 and 701 times the loop;
+ * profiles/phgr13_verify_batch.txt). */
+typedef struct {
+    uint32_t failed;        /* bit c set: equation E_c did not hold (0 division, 1 v, 2 w, 3 y, 4 linear); 0 after *ok = 1 */
+    uint32_t device_loops;  /* Miller loops run on the device: nproofs + diff */
+    uint32_t reserved[2];
+} ps_phgr13_batch_info;
+int ps_phgr13_verify_batch(ps_ctx* ctx, const ps_phgr13_vk* vk, const ps_scalars* io, const ps_phgr13_proof* proofs,
+                           size_t nproofs, const uint8_t* rho_be32, int* ok);
+int ps_phgr13_verify_batch_info(ps_ctx* ctx, ps_phgr13_batch_info* out); /* of the last batch call on ctx */
 
 #ifdef __cplusplus
 }

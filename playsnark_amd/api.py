@@ -1106,3 +1106,44 @@ def PHGR13Verify(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys
     ok = C.c_int(0)
     _check(lib.ps_phgr13_verify(ctx._h, C.byref(vk), io._h, C.byref(raw), C.byref(ok)))
     return bool(ok.value)
+
+
+PHGR13_EQUATIONS = ("division", "v", "w", "y", "linear")  # bit c of PHGR13VerifyBatchInfo()["failed"]: equation E_c
+
+
+def PHGR13VerifyBatch(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, proofs: Sequence["PHGR13Proof"],
+                      ios: Sequence[Poly], rhos: Sequence[int]) -> bool:
+    """PHGR13Verify (pinochio.go:281) for many proofs under one key (ps_phgr13_verify_batch): the five pairing products of
+    the single verifier, each weighted by `rhos` (non-zero, below r, drawn AFTER the proofs are fixed; 128 random bits each
+    are enough) and each checked on its own.  ios[i] are proof i's public inputs (a Poly each, or ONE Poly of
+    len(proofs) * len(vs_io) scalars, proof-major).  Returns the verdict; PHGR13VerifyBatchInfo(ctx) says which of the five
+    equations failed.  A malformed proof raises; there is no per-proof verdict."""
+    vk = _lib.Phgr13Vk()
+    for name in ("av", "aw", "ay", "gamma", "bgamma", "bgamma2", "yts"):
+        C.memmove(getattr(vk, name), vk_points[name], len(vk_points[name]))
+    vk.vs_io, vk.ws_io, vk.ys_io = vs_io._h, ws_io._h, ys_io._h
+    n = len(proofs)
+    if isinstance(ios, Poly):
+        io = ios
+    else:
+        if len(ios) != n:
+            raise LengthMismatch(f"{len(ios)} public-input vectors for {n} proofs")
+        io = Poly.upload(ctx, b"".join(v.download_bytes() for v in ios))
+    raw = (_lib.Phgr13Proof * max(n, 1))()
+    for i, p in enumerate(proofs):
+        for f in PHGR13Proof.FIELDS:
+            C.memmove(getattr(raw[i], f), getattr(p, f), len(getattr(p, f)))
+    if len(rhos) != n:
+        raise LengthMismatch(f"{len(rhos)} weights for {n} proofs")
+    rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
+    ok = C.c_int(0)
+    _check(lib.ps_phgr13_verify_batch(ctx._h, C.byref(vk), io._h, raw, n, rho, C.byref(ok)))
+    return bool(ok.value)
+
+
+def PHGR13VerifyBatchInfo(ctx: Context) -> dict:
+    """Of the last PHGR13VerifyBatch on ctx (ps_phgr13_verify_batch_info): {"failed": bit mask of the equations that did not
+    hold (PHGR13_EQUATIONS), "device_loops": Miller loops run on the device}."""
+    info = _lib.Phgr13BatchInfo()
+    _check(lib.ps_phgr13_verify_batch_info(ctx._h, C.byref(info)))
+    return {"failed": info.failed, "device_loops": info.device_loops}

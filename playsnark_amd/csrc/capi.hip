@@ -168,6 +168,10 @@ struct ps_ctx : MsmWorkspace {
     DevBuf lc_f12, lc_pts, lc_rows, lc_iolp, lc_work;
     ps_verify_locate_info lc_info{0, 0, 0, 0};  // of the last locate call (ps_groth16_verify_batch_locate_info)
     float lc_ms[3] = {0, 0, 0};                 // ... and its descent's wall clock (ps_debug_verify_locate_ms)
+    // ps_phgr13_verify_batch (verify_phgr13_batch.inc): the rows rho_i (1, io_i) and their io part, plain and in Montgomery form
+    DevBuf pvb_rows;
+    ps_phgr13_batch_info pvb_info{0, 0, {0, 0}};  // of the last call (ps_phgr13_verify_batch_info)
+    float pvb_ms[5] = {0, 0, 0, 0, 0};                   // ... and its stages when timed (ps_debug_phgr13_verify_batch_stage_ms)
     u32 simds = 0;                   // SIMDs of the device (how far k_miller_batch spreads a small batch), 0: not asked yet
     // ps_msm_be32 / ps_msm_i64 (seam S1: one upload per BlindEval call): the converted scalars of the call live in a vector
     // the context keeps, so a call does not pay a hipMalloc and a hipFree (which synchronises the device) of 32 bytes per
@@ -2059,6 +2063,7 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "locate_dev.hpp"
 #include "verify_batch.inc"
 #include "verify_locate.inc"
+#include "verify_phgr13_batch.inc"
 #include "srs_setup.inc"
 #include "srs_phase1.inc"
 #include "crs_check.inc"

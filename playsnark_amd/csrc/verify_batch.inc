@@ -28,15 +28,16 @@ static int ctx_simds(ps_ctx* c, u32* out) {
 constexpr int PS_VB_STAGES = 6;
 struct VbClock {
     ps_ctx* c;
+    float* ms;  // the stage times of the entry point this clock serves (c->vb_ms; c->pvb_ms for ps_phgr13_verify_batch)
     std::chrono::steady_clock::time_point t0;
-    explicit VbClock(ps_ctx* ctx) : c(ctx), t0(std::chrono::steady_clock::now()) {
-        if (c->timing) for (float& v : c->vb_ms) v = 0;
+    VbClock(ps_ctx* ctx, float* stage_ms, int stages) : c(ctx), ms(stage_ms), t0(std::chrono::steady_clock::now()) {
+        if (c->timing) for (int i = 0; i < stages; i++) ms[i] = 0;
     }
     void mark(int stage) {  // everything enqueued so far belongs to `stage`
         if (!c->timing) return;
         (void)hipStreamSynchronize(c->stream);
         const auto t1 = std::chrono::steady_clock::now();
-        c->vb_ms[stage] += std::chrono::duration<float, std::milli>(t1 - t0).count();
+        ms[stage] += std::chrono::duration<float, std::milli>(t1 - t0).count();
         t0 = t1;
     }
 };
@@ -178,6 +179,38 @@ static void words_add_mod_r(u32* acc, const u32* x) {  // both below r < 2^255
     if (!borrow) memcpy(acc, d, sizeof(d));
 }
 
+// The weights of a batch: every rho_i canonical (PS_ERR_ENCODING) and non-zero (PS_ERR_ARG); sum = their sum mod r
+static int batch_weights(const std::string& fn, const uint8_t* rho_be32, size_t n, u32* sum) {
+    memset(sum, 0, 32);
+    for (size_t i = 0; i < n; i++) {
+        u32 w[8];
+        if (!be32_to_words(w, rho_be32 + 32 * i)) return fail(PS_ERR_ENCODING, fn + ": rho[" + std::to_string(i) + "] is not below r");
+        u32 any = 0;
+        for (int k = 0; k < 8; k++) any |= w[k];
+        if (!any) return fail(PS_ERR_ARG, fn + ": rho[" + std::to_string(i) + "] is zero (the proof would not be checked)");
+        words_add_mod_r(sum, w);
+    }
+    return PS_OK;
+}
+
+// out = sum_j t_j pts_j with t_j = sum_i w_i io_ij over `rows` rows of pts->n plain scalars: ONE sum over the key's points
+// instead of one per proof (pts->n == 0: the identity).  t lives in the caller's scope: freeing it here would synchronise
+// the device, and the Miller loops enqueued before this sum are meant to run beside what follows it.
+static int weighted_io_sum(ps_ctx* c, const std::string& fn, Scope& scope, const Fr* w_mont, const ps_scalars* io, size_t rows, const ps_points* pts,
+                           uint8_t* out) {
+    const size_t diff = pts->n;
+    if (!diff) { write_identity(pts->group, out); return PS_OK; }
+    if (storage_wait_ready(io->st, c->stream)) return fail(PS_ERR_HIP, fn + ": event wait failed");
+    ps_scalars** t = scope.scalars();
+    const u32* tw = nullptr;
+    int rc = weighted_columns(c, w_mont, scalars_ptr(io), rows, diff, &tw);
+    if (rc) return rc;
+    if ((rc = scalars_alloc(c, diff, t))) return rc;
+    if (hipMemcpyAsync((*t)->st->p, tw, 32 * diff, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || storage_mark_ready((*t)->st, c->stream))
+        return fail(PS_ERR_HIP, fn + ": copy of the column sums failed");
+    return ps_msm(c, pts, *t, out);
+}
+
 template <class F>
 static size_t first_bad_encoding(const std::vector<uint8_t>& raw, size_t n, size_t wb) {
     for (size_t i = 0; i < n; i++) {
@@ -204,7 +237,7 @@ static int locate_miller_levels(ps_ctx* c, const Affine<Fp>* g1, const Affine<Fp
 // caller has checked its pointers and set *ok = 0.
 static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, const char* max_what, const ps_groth16_vk* vk, const ps_scalars* io,
                              const uint8_t* proofs, size_t nproofs, const uint8_t* rho_be32, int* ok, VbKeep* keep) {
-    VbClock clk(c);
+    VbClock clk(c, c->vb_ms, PS_VB_STAGES);
     if (c->q_len) return fail(PS_ERR_ARG, fn + ": sums are pending on this context (ps_msm_finish them first)");
     if (nproofs > max_n) return fail(PS_ERR_ARG, fn + ": more than " + max_what + " proofs in one batch");
     const size_t N = nproofs, diff = vk->io_lp->n;
@@ -213,19 +246,12 @@ static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, con
                                        std::to_string(diff) + " each");
     if (N == 0) { *ok = 1; return PS_OK; }
     // weights: canonical, non-zero; their sum for the alpha term
-    u32 rho_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < N; i++) {
-        u32 w[8];
-        if (!be32_to_words(w, rho_be32 + 32 * i)) return fail(PS_ERR_ENCODING, fn + ": rho[" + std::to_string(i) + "] is not below r");
-        u32 any = 0;
-        for (int k = 0; k < 8; k++) any |= w[k];
-        if (!any) return fail(PS_ERR_ARG, fn + ": rho[" + std::to_string(i) + "] is zero (the proof would not be checked)");
-        words_add_mod_r(rho_sum, w);
-    }
+    u32 rho_sum[8];
+    int rc = batch_weights(fn, rho_be32, N, rho_sum);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // the key: as in ps_groth16_verify
-    int rc = vk_array_in_subgroup(c, vk->io_lp, fn.c_str());
-    if (rc) return rc;
+    if ((rc = vk_array_in_subgroup(c, vk->io_lp, fn.c_str()))) return rc;
     Affine<Fp> alpha;
     Affine<Fp2> beta2, gamma, delta2;
     if (!read_g1(alpha, vk->alpha) || !read_g2(beta2, vk->beta2) || !read_g2(gamma, vk->gamma) || !read_g2(delta2, vk->delta2))
@@ -240,7 +266,7 @@ static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, con
     Scope scope;
     ps_points** arr[3] = {scope.points(), scope.points(), scope.points()};
     ps_points** ra = scope.points();
-    ps_scalars **rho = scope.scalars(), **t = scope.scalars();
+    ps_scalars** rho = scope.scalars();
     for (int k = 0; k < 3; k++) {
         raw[k].resize(wbs[k] * N);
         for (size_t i = 0; i < N; i++) memcpy(raw[k].data() + wbs[k] * i, proofs + 384 * i + offs[k], wbs[k]);
@@ -274,17 +300,7 @@ static int verify_batch_impl(ps_ctx* c, const std::string& fn, size_t max_n, con
     // product is fetched after the sums)
     // X = sum_j (sum_i rho_i io_ij) IoLP_j and sum_i rho_i C_i: two sums instead of N
     uint8_t xb[96], cb[96];
-    if (diff) {
-        if (storage_wait_ready(io->st, c->stream)) return fail(PS_ERR_HIP, fn + ": event wait failed");
-        const u32* tw = nullptr;
-        if ((rc = weighted_columns(c, rho_m, scalars_ptr(io), N, diff, &tw))) return rc;
-        if ((rc = scalars_alloc(c, diff, t))) return rc;
-        if (hipMemcpyAsync((*t)->st->p, tw, 32 * diff, hipMemcpyDeviceToDevice, c->stream) != hipSuccess || storage_mark_ready((*t)->st, c->stream))
-            return fail(PS_ERR_HIP, fn + ": copy of the column sums failed");
-        if ((rc = ps_msm(c, vk->io_lp, *t, xb))) return rc;
-    } else {
-        write_identity(PS_G1, xb);
-    }
+    if ((rc = weighted_io_sum(c, fn, scope, rho_m, io, N, vk->io_lp, xb))) return rc;
     if ((rc = ps_msm(c, *arr[2], *rho, cb))) return rc;
     clk.mark(4);
     pairing::Fp12 f;

@@ -99,6 +99,22 @@ static int locate_build_trees(ps_ctx* c, const ps_groth16_vk* vk, const ps_scala
     return PS_OK;
 }
 
+// K sums of `diff` >= 1 scaled points side by side: segment k = scal[k * diff + j] * base[j], j < diff, summed by levels of
+// k_g1_pair_sums.  *src and *dst are two buffers of K * diff points; on return the sum of segment k is (*src)[k * diff] (the
+// two may have changed places) and *dst is free.  Enqueued on c->stream; K * diff < 2^32 is the caller's.  Shared by the
+// descent below (X_S) and by ps_phgr13_verify_batch (the io part of rho_i gv_i, verify_phgr13_batch.inc).
+static void segment_sums(ps_ctx* c, const Xyzz<Fp>* base, size_t diff, size_t K, const Fr* scal_mont, Xyzz<Fp>** src, Xyzz<Fp>** dst) {
+    constexpr size_t WX = sizeof(Xyzz<Fp>) / 4;
+    hipLaunchKernelGGL(k_gather_words, dim3(nblocks(K * WX * diff)), dim3(256), 0, c->stream, (const u32*)base, (const u32*)nullptr, (u32)K, (u64)0, (u64)0,
+                       (u32)(WX * diff), (u32*)*src);  // base, K times
+    hipLaunchKernelGGL(k_ec_scale<Fp>, dim3(nblocks(K * diff)), dim3(256), 0, c->stream, *src, (u32)(K * diff), scal_mont, ~0ull);
+    for (size_t n = diff; n > 1; n = (n + 1) / 2) {  // K segments of diff points, the sum of a segment ends in its first slot
+        hipLaunchKernelGGL(k_g1_pair_sums, dim3(nblocks(K * ((n + 1) / 2))), dim3(256), 0, c->stream, (const Xyzz<Fp>*)*src, (u32)n, (u32)K, (u32)diff, *dst,
+                           (u32)diff);
+        std::swap(*src, *dst);
+    }
+}
+
 // check(S) for the K nodes idx[] of level l: pass[k] = 1 / 0
 static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep, int l, const u32* idx, size_t K, uint8_t* pass) {
     typedef pairing_dev::Fp12 D12;
@@ -127,13 +143,7 @@ static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep
         gather(rows, d_idx, K, 8 * cols, 8, 8 * diff, w + o_t);
         hipLaunchKernelGGL(k_fr_to_mont, dim3(nblocks(K * diff)), dim3(256), 0, c->stream, (Fr*)(w + o_tm), (const u32*)(w + o_t), (u64)(K * diff));
         Xyzz<Fp>*src = (Xyzz<Fp>*)(w + o_p0), *dst = (Xyzz<Fp>*)(w + o_p1);
-        gather(t.iolp, nullptr, K, 0, 0, WX * diff, src);  // IoLP, K times
-        hipLaunchKernelGGL(k_ec_scale<Fp>, dim3(nblocks(K * diff)), dim3(256), 0, c->stream, src, (u32)(K * diff), (const Fr*)(w + o_tm), ~0ull);
-        for (size_t n = diff; n > 1; n = (n + 1) / 2) {  // K segments of diff points, the sum of a segment ends in its first slot
-            hipLaunchKernelGGL(k_g1_pair_sums, dim3(nblocks(K * ((n + 1) / 2))), dim3(256), 0, c->stream, (const Xyzz<Fp>*)src, (u32)n, (u32)K, (u32)diff, dst,
-                               (u32)diff);
-            std::swap(src, dst);
-        }
+        segment_sums(c, t.iolp, diff, K, (const Fr*)(w + o_tm), &src, &dst);
         gather(src, nullptr, K, WX * diff, 0, WX, norm);
     } else {
         HIP_TRY(hipMemsetAsync(norm, 0, sizeof(Xyzz<Fp>) * K, c->stream));  // X_S is the identity (ZZ = 0)

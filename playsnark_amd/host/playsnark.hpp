@@ -338,6 +338,16 @@ inline bool PHGR13Verify(Context& c, const ps_phgr13_vk& vk, const ps_phgr13_pro
     check(ps_phgr13_verify(c.get(), &vk, io.get(), &p, &ok));
     return ok != 0;
 }
+// PHGR13Verify for proofs.size() proofs under one key (ps_phgr13_verify_batch): the five pairing products of the single
+// verifier, each weighted by rho and each checked on its own.  io = proofs.size() x diff scalars (proof-major), rho_be32 =
+// proofs.size() x 32 bytes drawn after the proofs are fixed.  *info (optional): which equations failed, device Miller loops
+inline bool PHGR13VerifyBatch(Context& c, const ps_phgr13_vk& vk, const Poly& io, const std::vector<ps_phgr13_proof>& proofs,
+                              const uint8_t* rho_be32, ps_phgr13_batch_info* info = nullptr) {
+    int ok = 0;
+    check(ps_phgr13_verify_batch(c.get(), &vk, io.get(), proofs.data(), proofs.size(), rho_be32, &ok));
+    if (info) check(ps_phgr13_verify_batch_info(c.get(), info));
+    return ok != 0;
+}
 // func NewGroth16TrustedSetup(qap QAP) Groth16Setup (groth16.go:64), toxic waste drawn by the caller
 inline ps_groth16_crs NewGroth16TrustedSetup(Context& c, const QAP& q, const ps_groth16_toxic& tw) {
     ps_groth16_crs out;

@@ -1366,6 +1366,49 @@ func PHGR13VerifyHIP(hp *HipPHGR13, p PHGR13Proof, io Vector) bool {
 	return ok != 0
 }
 
+// PHGR13VerifyBatchHIP checks many proofs under one key in one call (ps_phgr13_verify_batch): the five pairing products of
+// PHGR13Verify (pinochio.go:281-378), each weighted by a random linear combination over the proofs and each with its own
+// final exponentiation.  The weights are drawn here, after the proofs are in hand, 128 bits each.  The second result is
+// the mask of the equations that did not hold (bit 0 division, 1 v, 2 w, 3 y, 4 linear), 0 for an accepted batch.
+func PHGR13VerifyBatchHIP(hp *HipPHGR13, proofs []PHGR13Proof, ios []Vector) (bool, uint32) {
+	if len(proofs) != len(ios) {
+		panic("PHGR13VerifyBatchHIP: one public-input vector per proof")
+	}
+	if len(proofs) == 0 {
+		return true, 0
+	}
+	var all Vector
+	raw := make([]C.ps_phgr13_proof, len(proofs))
+	rho := make([]byte, 32*len(proofs))
+	for i, p := range proofs {
+		all = append(all, ios[i]...)
+		in := &raw[i]
+		copyTo(unsafe.Pointer(&in.vss[0]), affineOf(C.PS_G1, p.vss))
+		copyTo(unsafe.Pointer(&in.vass[0]), affineOf(C.PS_G1, p.vass))
+		copyTo(unsafe.Pointer(&in.wss[0]), affineOf(C.PS_G2, p.wss))
+		copyTo(unsafe.Pointer(&in.wass[0]), affineOf(C.PS_G1, p.wass))
+		copyTo(unsafe.Pointer(&in.yss[0]), affineOf(C.PS_G1, p.yss))
+		copyTo(unsafe.Pointer(&in.yass[0]), affineOf(C.PS_G1, p.yass))
+		copyTo(unsafe.Pointer(&in.hs[0]), affineOf(C.PS_G1, p.hs))
+		copyTo(unsafe.Pointer(&in.gz[0]), affineOf(C.PS_G1, p.gz))
+		for zero := true; zero; { // 128 random bits, drawn again in the (2^-128) case that they are all zero
+			random.Bytes(rho[32*i+16:32*i+32], random.New())
+			for _, b := range rho[32*i+16 : 32*i+32] {
+				zero = zero && b == 0
+			}
+		}
+	}
+	dio := uploadSolution(all)
+	defer C.ps_scalars_free(dio)
+	var ok C.int
+	call(func() C.int {
+		return C.ps_phgr13_verify_batch(hipCtx, &hp.vk, dio, &raw[0], C.size_t(len(proofs)), u8(rho), &ok)
+	})
+	var info C.ps_phgr13_batch_info
+	call(func() C.int { return C.ps_phgr13_verify_batch_info(hipCtx, &info) })
+	return ok != 0, uint32(info.failed)
+}
+
 // HipPHGR13Multi: every device holds only ITS index ranges of the evaluation key -- vs .. ybs over len(vs), gsi over
 // n-1 -- its own QAP of the circuit and its own copy of the solution.  The quotient runs once, on device 0; the other
 // devices copy their range of h from it device to device.
