@@ -58,7 +58,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      then ps_points_lagrange_check and ps_groth16_crs_check_from_srs; then ps_qap_create_fr (with the new
  *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch;
  *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table;
- *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info). */
+ *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info);
+ *      then ps_msm_prediction_counts. */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -252,6 +253,18 @@ int ps_msm_set_tail(ps_ctx* ctx, int mode);
  * symbol, no existing struct changed). */
 int ps_msm_set_accumulate(ps_ctx* ctx, int mode);
 int ps_msm_last_accumulate(ps_ctx* ctx, int* path);
+/* In the automatic mode a sum does not enqueue both point passes every time: the context remembers, per kind of sum (the
+ * array and its table, the length, the window, the width of the scalars, the number of arrays over one sort), which pass the
+ * device chose last and launches only that one -- ps_msm_launch / ps_msm_finish, ps_msm, ps_msm_be32, ps_msm_i64,
+ * ps_msm_multi and the provers' sums.  The device still decides: when it chooses the other pass -- the distribution of the
+ * scalars changed -- the call that returns the result (ps_msm_finish, ps_msm_multi, the prover) runs the point pass a second
+ * time first, so SUCH A SUM IS SUMMED TWICE (about one lone point pass of extra latency), and the next four sums of that
+ * kind enqueue both passes again.  Results and ps_msm_last_accumulate never depend on the guess.  ps_msm_batch keeps the slices.
+ * ps_msm_prediction_counts: out[0] admitted sums of this context launched with both passes, out[1] with one, out[2] how
+ * many of the latter were summed twice.  The sums over one sort (ps_msm_multi) share one verdict and count as one.  Sums
+ * that are not admitted, and forced modes, count nowhere.  Added within revision 5 (found by symbol, no existing struct
+ * changed). */
+int ps_msm_prediction_counts(ps_ctx* ctx, uint64_t* out /* [3] */);
 /* Per-stage device time of the sum finished last, measured with HIP events on the streams its kernels
  * run on.  Stages: 0 digits (+counter memset), 1 scan, 2 scatter (+ the buckets' order by size where whole buckets are
  * considered, ps_msm_set_accumulate), 3 queue (bucket memset, and with

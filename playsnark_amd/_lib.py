@@ -40,6 +40,7 @@ SYMBOLS = [
     "ps_msm_set_accumulate", "ps_msm_last_accumulate",
     "ps_msm_batch_set_table",
     "ps_phgr13_verify_batch", "ps_phgr13_verify_batch_info",
+    "ps_msm_prediction_counts",
 ]
 
 
@@ -196,6 +197,8 @@ def _load():
     if hasattr(lib, "ps_msm_set_accumulate"):  # found by symbol: an older build named by PLAYSNARK_HIP_LIB (A/B runs) loads without the knob
         lib.ps_msm_set_accumulate.argtypes = [vp, i]
         lib.ps_msm_last_accumulate.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "ps_msm_prediction_counts"):  # found by symbol, as above
+        lib.ps_msm_prediction_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.ps_microbench_mad.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ps_ctx_set_table_budget.argtypes = [vp, C.c_longlong]
     lib.ps_qap_is_valid.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

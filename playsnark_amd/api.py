@@ -115,6 +115,13 @@ class Context:
         _check(lib.ps_msm_last_accumulate(self._h, C.byref(path)))
         return path.value
 
+    def prediction_counts(self) -> dict:
+        """Admitted sums of this context by how their point pass was launched (ps_msm_prediction_counts): with both families,
+        with the one the last sum of their kind took, and how many of the latter had to be summed again."""
+        k = (C.c_uint64 * 3)()
+        _check(lib.ps_msm_prediction_counts(self._h, k))
+        return {"both": int(k[0]), "one": int(k[1]), "redone": int(k[2])}
+
     STAGES = ("digits", "scan", "scatter", "queue", "accumulate", "fixup", "reduce")
 
     def set_timing(self, enable: bool):

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "msm.hpp"
+#include "point_pass_predict.hpp"
 #include "msm_batch.hpp"
 #include "msm_batch_plan.hpp"
 #include "msm_batch_multi_plan.hpp"
@@ -191,7 +192,11 @@ struct ps_ctx : MsmWorkspace {
     // pending sum has a workspace to itself (`ws`: the context, or one of `workers`) and carries the plan it was launched
     // with; accumulations are chained in launch order, so a later sum's sort and accumulation run beside the earlier
     // ones' latency-bound fix-up / reduction / host fold.
-    struct PendingMsm { int group; MsmPlan plan; MsmWorkspace* ws; };
+    // `launched`: the point-pass families an admitted sum was launched with (point_pass_predict.hpp: ACC_AUTO both, else the one
+    // the history named) under `key`; a sum launched with one family keeps a reference on its points (redo_*: the caller may
+    // drop a slice handle before the finish) so that ps_msm_finish can run the point pass again when the device chose the other
+    struct PendingMsm { int group; MsmPlan plan; MsmWorkspace* ws; u32 launched; PassKey key; struct Storage* redo_st; size_t redo_first, redo_n; };
+    PassHistory pass_history;  // the last verdict per kind of sum, and the counters of ps_msm_prediction_counts
     PendingMsm q[PS_MSM_QUEUE];
     int q_head = 0, q_len = 0;
     hipEvent_t ev_fork = nullptr;
@@ -348,6 +353,8 @@ extern "C" void ps_ctx_destroy(ps_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->created()) (void)c->sync();
     for (MsmWorkspace& w : c->workers) if (w.created()) (void)w.sync();
+    for (int j = 0; j < c->q_len; j++)  // sums launched and never finished: the references they keep for a second point pass
+        if (Storage* st = c->q[(c->q_head + j) % PS_MSM_QUEUE].redo_st) storage_unref(st);
     quotient_cache_free(c->qcache);
     if (c->up_scalars) ps_scalars_free(c->up_scalars);
     for (ps_scalars* v : c->pv_scalars)
@@ -1206,9 +1213,13 @@ static bool table_ref(const ps_points* pts, size_t n, int wbits, int W, TableRef
 // device -- *dev_sets points at the pl.sets weighted sums in `wins`, nothing is copied to the pinned slot, and the number
 // of sets is not bound by that slot.  `n` is then the length of the virtual scalar array (members x points), and
 // `member_n` (0: n) the length of one member -- the index range whose window table a tabled batch reads.
+// family (automatic plans only): ACC_AUTO enqueues both point passes, ACC_SLICES / ACC_BUCKETS only the one the caller expects
+// the device to choose -- the launches of the forced mode, but with the verdict word, so that a wrong guess returns at once
+// and the caller runs the pass again (ps_msm_finish).
 template <class F>
 static int msm_points_t(MsmWorkspace* sw, MsmWorkspace* rw, const ps_points* pts, size_t n, const MsmPlan& pl, bool timed, int slot,
-                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr, size_t member_n = 0) {
+                        hipEvent_t wait_acc, hipEvent_t acc_done, bool inline_tail = false, Xyzz<F>** dev_sets = nullptr, size_t member_n = 0,
+                        u32 family = ACC_AUTO) {
     typedef typename KernelField<F>::type KF;      // Fp -> Fp, Fp2 -> lane-split Fp2s
     constexpr unsigned LN = FieldTraits<KF>::LANES;  // lanes per logical thread
     const u64 total = (u64)pl.W * n;
@@ -1264,10 +1275,11 @@ static int msm_points_t(MsmWorkspace* sw, MsmWorkspace* rw, const ps_points* pts
     PS_STAGE_MARK(sw);  // 4: buffers cleared and the previous sum's accumulation done ("queue")
     constexpr bool PF = LN == 1 || PS_G2_ACC_WAVES == 1;  // next point prefetched (the lane-pair G2 kernel at two waves per SIMD has no registers to spare)
     // Whole buckets in order of size (msm.hpp section 4b) where the plan asks for them: forced, only that path is launched;
-    // automatic, both are enqueued and the verdict word the sort left on the device lets one of them return at once.
-    // ps_msm_batch (dev_sets) keeps the slices.
-    const u32 acc_mode = dev_sets ? (u32)ACC_SLICES : (u32)pl.acc;
-    const u32* verdict = acc_mode == ACC_SLICES ? nullptr : (const u32*)sw->border.p + 2 * BO_CLASSES;
+    // automatic, the verdict word the sort left on the device makes the family it does not name return at once -- both are
+    // enqueued, or only the one `family` names.  ps_msm_batch (dev_sets) keeps the slices.
+    const u32 plan_mode = dev_sets ? (u32)ACC_SLICES : (u32)pl.acc;
+    const u32* verdict = plan_mode == ACC_SLICES ? nullptr : (const u32*)sw->border.p + 2 * BO_CLASSES;
+    const u32 acc_mode = plan_mode == ACC_AUTO ? family : plan_mode;  // the families launched
     if (acc_mode != ACC_SLICES)
         hipLaunchKernelGGL((k_bucket_sum<KF, PF>), dim3(nblocks(G * LN)), dim3(256), 0, st, src, (const u32*)sw->sorted.p,
                            (const u32*)sw->offs.p, (const u32*)sw->perm.p, (u32)G, idx_mask, w_stride, pstride, (Xyzz<F>*)rw->buckets.p,
@@ -1290,7 +1302,7 @@ static int msm_points_t(MsmWorkspace* sw, MsmWorkspace* rw, const ps_points* pts
         // quads of a bucket must fit THIS group's 256-thread block (64 G1 points, 32 G2 points)
         const u32 lpb = qlpb;
         hipLaunchKernelGGL(k_qfixup<KF>, dim3(nblocks(G * (u64)lpb * QTraits<KF>::GL)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M,
-                           nthreads_acc, lpb, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2);
+                           nthreads_acc, lpb, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2, verdict);
     } else if (split_fixup) {
         u32* ccount = (u32*)rw->heavy.p + 1;
         u32* clist = (u32*)rw->heavy.p + 2 + 2 * max_heavy + 1;
@@ -1304,22 +1316,22 @@ static int msm_points_t(MsmWorkspace* sw, MsmWorkspace* rw, const ps_points* pts
         constexpr u32 chain_npb = 256 / QTraits<KF>::GL;
         hipLaunchKernelGGL(k_qfixup_chain<KF>, dim3((unsigned)std::min<size_t>((max_chain + chain_npb - 1) / chain_npb, 512)), dim3(256), 0, st,
                            (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p,
-                           (const u32*)ccount, (const u32*)clist);
+                           (const u32*)ccount, (const u32*)clist, verdict);
     } else
     hipLaunchKernelGGL(k_fixup<KF>, dim3(nblocks(G * LN)), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc,
-                       (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2);
+                       (const Xyzz<F>*)rw->parts.p, (Xyzz<F>*)rw->buckets.p, (u32*)rw->heavy.p, (u32*)rw->heavy.p + 2, verdict);
     if (acc_mode != ACC_BUCKETS) {
         const u32* hcount = (const u32*)rw->heavy.p;
         const u32* hlist = hcount + 2;
         u32* job_base = (u32*)rw->heavy.p + 2 + max_heavy;
-        hipLaunchKernelGGL(k_heavy_jobs, dim3(1), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, hcount, hlist, job_base, heavy_npb);
+        hipLaunchKernelGGL(k_heavy_jobs, dim3(1), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc, hcount, hlist, job_base, heavy_npb, verdict);
         // two levels of quad trees for every plan (qtail.hpp): the one-lane kernels of rounds 1-2 (jobs of 1024 slices, strided
         // chains, an 8-level LDS tree of 14-36 us additions) took 0.43 ms for the 2^19 ones of a boolean witness at 2^20 points
         hipLaunchKernelGGL(k_qfixup_heavy_part<KF>, dim3(1024), dim3(256), 0, st, (const u32*)sw->offs.p, (u32)G, pl.M, nthreads_acc,
                            (const Xyzz<F>*)rw->parts.p,
-                           hcount, hlist, (const u32*)job_base, (Xyzz<F>*)rw->hparts.p);
+                           hcount, hlist, (const u32*)job_base, (Xyzz<F>*)rw->hparts.p, verdict);
         hipLaunchKernelGGL(k_qfixup_heavy<KF>, dim3(256), dim3(256), 0, st, (const Xyzz<F>*)rw->hparts.p, (Xyzz<F>*)rw->buckets.p, hcount,
-                           hlist, (const u32*)job_base);
+                           hlist, (const u32*)job_base, verdict);
     }
     PS_STAGE_MARK(sw);  // 6: after fixup
     {
@@ -1533,7 +1545,7 @@ static int msm_plan_checked(ps_ctx* c, const ps_points* const* pts, size_t k, si
 #define PS_CHAIN_MIN_ENTRIES (1ull << 21)  // sums with fewer digits than this are not chained behind the previous accumulation
 #endif
 static int msm_launch_any(MsmWorkspace* ws, const ps_points* pts, const ps_scalars* sc, const MsmPlan& pl, bool timed, hipEvent_t wait_acc,
-                          hipEvent_t acc_done, bool inline_tail) {
+                          hipEvent_t acc_done, bool inline_tail, u32 family = ACC_AUTO) {
     hipStream_t ss = inline_tail ? ws->stream : ws->tail;  // a lone short sum keeps one stream
     int rc = msm_sort(ws, sc, pl, timed, ss);
     if (rc) return rc;
@@ -1541,8 +1553,8 @@ static int msm_launch_any(MsmWorkspace* ws, const ps_points* pts, const ps_scala
         HIP_TRY(hipEventRecord(ws->ev_sort_local, ss));
         HIP_TRY(hipStreamWaitEvent(ws->stream, ws->ev_sort_local, 0));
     }
-    rc = pts->group == PS_G1 ? msm_points_t<Fp>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail)
-                             : msm_points_t<Fp2>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail);
+    rc = pts->group == PS_G1 ? msm_points_t<Fp>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail, nullptr, 0, family)
+                             : msm_points_t<Fp2>(ws, ws, pts, sc->n, pl, timed, 0, wait_acc, acc_done, inline_tail, nullptr, 0, family);
     ws->ev_valid = timed && !rc;
     return rc;
 }
@@ -1600,6 +1612,24 @@ static void write_identity(int group, uint8_t* out) {  // zero.Clone(), algebra.
     out[0] = 0x40;
 }
 
+// what the history of point passes is kept by (point_pass_predict.hpp)
+// (sums: the arrays summed over the one sort; the first one stands for all of them)
+static PassKey pass_key(const ps_points* pts, const ps_scalars* sc, const MsmPlan& pl, size_t sums = 1) {
+    PassKey k;
+    k.storage = pts->st;
+    TableRef tr{};
+    if (pl.table && table_ref(pts, sc->n, pl.c, pl.W, &tr)) k.table = tr.base;
+    k.first = pts->first;
+    k.n = sc->n;
+    k.G = pl.G;
+    k.group = pts->group;
+    k.c = pl.c;
+    k.W = pl.W;
+    k.width = pp_width_class(sc->max_bits, sc->neg_small);
+    k.sums = (int)sums;
+    return k;
+}
+
 // k sums over one scalar vector.  The sort runs on ring[0]'s stream; the point passes rotate over the workspaces of
 // `ring` (entries may coincide when k is small), accumulation i+1 chained behind accumulation i so that it runs beside
 // the fix-up and reduction of sum i.  Four workspaces: a tail that shares the chip with the following accumulations is
@@ -1625,9 +1655,25 @@ static int msm_multi_sort(ps_ctx* c, MsmWorkspace* const* ring, const ps_scalars
     }
     return PS_OK;
 }
+// What the sums over one sort were launched with (point_pass_predict.hpp): their point passes share the sort's ONE verdict
+// word, so they are one sum to the history -- one guess at the launch, one check at the finish, and on a wrong guess all of
+// them run again.
+struct MultiGuess {
+    u32 family = ACC_AUTO;
+    PassKey key;
+};
+static MultiGuess msm_multi_guess(ps_ctx* c, const ps_points* const* pts, size_t k, const ps_scalars* sc, const MsmPlan& pl) {
+    MultiGuess g;
+    if (pl.acc == ACC_AUTO && k) {
+        g.key = pass_key(pts[0], sc, pl, k);
+        g.family = c->pass_history.predict(g.key);
+    }
+    return g;
+}
 // first_wait: a point pass launched before this call that the first accumulation is chained behind
+// family: the point-pass families to launch for an automatic plan (MultiGuess::family, or the device's verdict for a second run)
 static int msm_multi_points(ps_ctx* c, MsmWorkspace* const* ring, const ps_points* const* pts, size_t k, const ps_scalars* sc,
-                            const MsmPlan& pl, hipEvent_t first_wait) {
+                            const MsmPlan& pl, hipEvent_t first_wait, u32 family = ACC_AUTO) {
     MsmWorkspace* w0 = ring[0];
     for (size_t i = 0; i < k; i++) {
         if (!c->ev_multi[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_multi[i], hipEventDisableTiming));
@@ -1640,8 +1686,8 @@ static int msm_multi_points(ps_ctx* c, MsmWorkspace* const* ring, const ps_point
         // the chain: 2^20-point G1 sums 2.97 ms per step chained, 3.03-3.08 unchained.)
         const bool chained = (u64)pl.W * sc->n >= PS_MULTI_CHAIN_MIN_ENTRIES;
         hipEvent_t wait = !chained ? nullptr : i ? c->ev_acc[i - 1] : first_wait;
-        int rc = pts[i]->group == PS_G1 ? msm_points_t<Fp>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i])
-                                        : msm_points_t<Fp2>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i]);
+        int rc = pts[i]->group == PS_G1 ? msm_points_t<Fp>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i], false, nullptr, 0, family)
+                                        : msm_points_t<Fp2>(w0, rw, pts[i], sc->n, pl, false, (int)i, wait, c->ev_acc[i], false, nullptr, 0, family);
         if (rc) {
             for (int j = 0; j < PS_MULTI_RING; j++) (void)ring[j]->sync();
             return rc;
@@ -1669,11 +1715,20 @@ static int msm_multi_ring(ps_ctx* c, bool self, size_t k, MsmWorkspace** ring) {
     return PS_OK;
 }
 
-// fold result i on the host while the GPU works on i+1...; out == nullptr just drains
-static int msm_multi_finish(ps_ctx* c, const MsmWorkspace* w0, const ps_points* const* pts, size_t k, const MsmPlan& pl, uint8_t* const* out) {
+// fold result i on the host while the GPU works on i+1...; out == nullptr just drains.  `guess`: what msm_multi_points was
+// given; when the device chose the other family, every point pass runs again over the sort ring[0] still holds.
+static int msm_multi_finish(ps_ctx* c, MsmWorkspace* const* ring, const ps_points* const* pts, size_t k, const ps_scalars* sc,
+                            const MsmPlan& pl, const MultiGuess& guess, uint8_t* const* out) {
+    const MsmWorkspace* w0 = ring[0];
     for (size_t i = 0; i < k; i++) {
         HIP_TRY(hipEventSynchronize(c->ev_multi[i]));
         if (!out) continue;
+        if (i == 0 && pl.acc == ACC_AUTO && c->pass_history.observe(guess.key, guess.family, (u32)msm_acc_path(w0, pl))) {
+            for (size_t j = 1; j < k; j++) HIP_TRY(hipEventSynchronize(c->ev_multi[j]));  // (they returned on the verdict word)
+            const int rc = msm_multi_points(c, ring, pts, k, sc, pl, nullptr, (u32)msm_acc_path(w0, pl));
+            if (rc) return rc;
+            HIP_TRY(hipEventSynchronize(c->ev_multi[0]));
+        }
         if (pts[i]->group == PS_G1) msm_fold_host<Fp>(w0, pl, (int)i, out[i]);
         else msm_fold_host<Fp2>(w0, pl, (int)i, out[i]);
     }
@@ -1711,8 +1766,9 @@ extern "C" int ps_msm_multi(ps_ctx* c, const ps_points* const* pts, size_t k, co
     MsmWorkspace* ring[PS_MULTI_RING];
     if ((rc = msm_multi_ring(c, true, k, ring))) return rc;
     if ((rc = msm_multi_sort(c, ring, sc, pl, true))) return rc;
-    if ((rc = msm_multi_points(c, ring, pts, k, sc, pl, nullptr))) return rc;
-    return msm_multi_finish(c, c, pts, k, pl, out);
+    const MultiGuess guess = msm_multi_guess(c, pts, k, sc, pl);
+    if ((rc = msm_multi_points(c, ring, pts, k, sc, pl, nullptr, guess.family))) return rc;
+    return msm_multi_finish(c, ring, pts, k, sc, pl, guess, out);
 }
 
 // allow_self = false keeps the context's own workspace out of the rotation (the provers run the quotient on its stream while
@@ -1747,7 +1803,7 @@ static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc
     if (c->q_len == 0) HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
     ps_ctx::PendingMsm& e = c->q[(c->q_head + c->q_len) % PS_MSM_QUEUE];
     if (sc->n == 0) {
-        e = {pts->group, MsmPlan{}, ws};
+        e = {pts->group, MsmPlan{}, ws, ACC_AUTO, PassKey{}, nullptr, 0, 0};
     } else {
         MsmPlan pl;
         int rc0 = msm_plan_checked(c, &pts, 1, sc->n, sc->max_bits, &pl);
@@ -1761,10 +1817,23 @@ static int msm_launch_impl(ps_ctx* c, const ps_points* pts, const ps_scalars* sc
         // below that the host's ~25 launches per sum are the bound)
         const bool chained = (u64)pl.W * sc->n >= PS_CHAIN_MIN_ENTRIES;
         hipEvent_t wait = (chained && c->last_chain && c->last_chain != ws) ? c->last_chain->ev_acc_local : nullptr;
-        int rc = msm_launch_any(ws, pts, sc, pl, c->timing, wait, nullptr, lone);
+        // an admitted sum: only the point pass the last sum of its kind took, where the history knows one (point_pass_predict.hpp)
+        u32 family = ACC_AUTO;
+        PassKey key{};
+        if (pl.acc == ACC_AUTO) {
+            key = pass_key(pts, sc, pl);
+            family = c->pass_history.predict(key);
+        }
+        int rc = msm_launch_any(ws, pts, sc, pl, c->timing, wait, nullptr, lone, family);
         if (rc) return rc;
         c->last_chain = ws;
-        e = {pts->group, pl, ws};
+        e = {pts->group, pl, ws, family, key, nullptr, 0, 0};
+        if (family != ACC_AUTO) {  // ps_msm_finish may have to run the point pass again
+            pts->st->refs.fetch_add(1);
+            e.redo_st = pts->st;
+            e.redo_first = pts->first;
+            e.redo_n = pts->n;
+        }
     }
     c->q_len++;
     return PS_OK;
@@ -1782,8 +1851,31 @@ extern "C" int ps_msm_finish(ps_ctx* c, uint8_t* out) {
         write_identity(e.group, out);
         return PS_OK;
     }
+    struct RedoRef {  // the reference a sum launched with one family holds on its points goes on every way out
+        Storage* st;
+        ~RedoRef() { if (st) storage_unref(st); }
+    } redo_ref{e.redo_st};
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipEventSynchronize(e.ws->ev_tail_done));  // the copy of the results: the last thing the sum enqueued (tail stream, or its own stream for a lone short sum)
+    if (pl.acc == ACC_AUTO) {
+        const u32 verdict = (u32)msm_acc_path(e.ws, pl);
+        if (c->pass_history.observe(e.key, e.launched, verdict)) {
+            // The device chose the family that was not launched: the kernels that ran returned at once and the results that came
+            // back are the reduction of buckets nobody wrote.  The sort's outputs stay on the workspace until another sum takes
+            // it, which cannot happen before this call returns: the point pass runs again over them, with the device's choice.
+            ps_points again;
+            again.group = e.group;
+            again.n = e.redo_n;
+            again.st = e.redo_st;
+            again.first = e.redo_first;
+            again.device = c->device;
+            const int rc = e.group == PS_G1
+                               ? msm_points_t<Fp>(e.ws, e.ws, &again, e.redo_n, pl, e.ws->ev_valid, 0, nullptr, nullptr, false, nullptr, 0, verdict)
+                               : msm_points_t<Fp2>(e.ws, e.ws, &again, e.redo_n, pl, e.ws->ev_valid, 0, nullptr, nullptr, false, nullptr, 0, verdict);
+            if (rc) return rc;
+            HIP_TRY(hipEventSynchronize(e.ws->ev_tail_done));
+        }
+    }
     if (e.group == PS_G1) msm_fold_host<Fp>(e.ws, pl, 0, out);
     else msm_fold_host<Fp2>(e.ws, pl, 0, out);
     c->last_info = ps_msm_info{pl.c, pl.W, msm_entries(e.ws, pl, e.group), pl.G, pl.M, pl.table ? 1 : 0};
@@ -1863,6 +1955,14 @@ extern "C" int ps_msm_set_tail(ps_ctx* c, int mode) {
 extern "C" int ps_msm_set_accumulate(ps_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return fail(PS_ERR_ARG, "accumulate mode must be 0 (automatic), 1 (slices) or 2 (whole buckets)");
     c->forced_acc = mode;
+    return PS_OK;
+}
+extern "C" int ps_msm_prediction_counts(ps_ctx* c, uint64_t* out) {
+    if (!c || !out) return fail(PS_ERR_ARG, "NULL argument");
+    const PassCounts& k = c->pass_history.counts();
+    out[0] = k.both;
+    out[1] = k.one;
+    out[2] = k.redone;
     return PS_OK;
 }
 extern "C" int ps_msm_last_accumulate(ps_ctx* c, int* path) {

@@ -59,7 +59,7 @@ struct MsmPlan {
     int lpb;      // quads per bucket in k_qfixup (0: the one-thread-per-bucket k_fixup)
     int rc_s;     // column bits of the row / column split of a bucket set (0: bit sums straight from the buckets)
     bool busy;    // planned while other sums were pending on the context: lane-time counts, not depth (capi.hip, msm_plan_tail)
-    int acc;      // the point pass (bucket_order.hpp): ACC_SLICES, ACC_BUCKETS, or ACC_AUTO = both enqueued, the device's verdict word picks
+    int acc;      // the point pass (bucket_order.hpp): ACC_SLICES, ACC_BUCKETS, or ACC_AUTO = the device's verdict word picks (the host launches both, or the one it expects: point_pass_predict.hpp)
 };
 // Entries of the sorted list: point index | window << ENTRY_W_SHIFT | sign << 31.  The window field is used only
 // with a window table (then the index must fit ENTRY_W_SHIFT bits); without one the index may use all 31 bits.
@@ -944,7 +944,11 @@ __global__ void __launch_bounds__(256, PS_ACC_WAVES(KF)) k_accumulate(const char
 // search, every bucket written by exactly one lane (empty ones included).  A wave runs as long as its largest bucket, so the
 // buckets are taken in order of size (bucket_order.hpp): the three kernels below run at the end of the sort.
 // The verdict word: ACC_BUCKETS or ACC_SLICES, decided on the device by k_bo_scan (or forced by the host); every kernel of
-// the path not taken reads it with one scalar load and returns.
+// the path not taken reads it with one scalar load and returns, BEFORE its first load of an index, a count or a list: the
+// host may have launched only the family it expected (point_pass_predict.hpp), and then nothing of the other family's
+// state -- the lists' counts, the partial slots -- was written for this sum.  The reduction that follows such a launch runs
+// over buckets nobody wrote: it indexes by thread and block only and its arithmetic has no data-dependent loop or address,
+// so it yields garbage the host discards, never a fault.
 __global__ void __launch_bounds__(256) k_bo_count(const u32* __restrict__ offs, u32 G, u32* __restrict__ hist) {
     PS_TAIL_PRIO_HERE;
     __shared__ u32 lh[BO_CLASSES];
@@ -1077,8 +1081,10 @@ template <class KF>
 __global__ void __launch_bounds__(256, PS_TAIL_WAVES) k_fixup(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
                                                   const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
                                                   Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
-                                                  u32* __restrict__ heavy_count, u32* __restrict__ heavy_list) {
+                                                  u32* __restrict__ heavy_count, u32* __restrict__ heavy_list,
+                                                  const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
+    if (verdict && *verdict == ACC_BUCKETS) return;
     u32 g = logical_tid<KF>();
     if (g >= G) return;
     const int M = eff_slice(offs[G], T, Mplan);
@@ -1175,8 +1181,10 @@ __host__ __device__ inline u32 heavy_chunk_of(u32 span, u32 npb) {
 
 // job_base[h] = number of jobs of the heavy buckets before h; job_base[nheavy] = total.  One workgroup.
 __global__ void __launch_bounds__(256) k_heavy_jobs(const u32* __restrict__ offs, u32 G, int Mplan, u32 T, const u32* __restrict__ heavy_count,
-                                                    const u32* __restrict__ heavy_list, u32* __restrict__ job_base, u32 npb) {
+                                                    const u32* __restrict__ heavy_list, u32* __restrict__ job_base, u32 npb,
+                                                    const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
+    if (verdict && *verdict == ACC_BUCKETS) return;  // k_bucket_sum took this sum: the heavy list is not this sum's
     const int M = eff_slice(offs[G], T, Mplan);
     __shared__ u32 wsum[4];
     const u32 nheavy = *heavy_count;

@@ -219,6 +219,7 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     const size_t cnt = sh.sv->n;
     MsmWorkspace* ring[PS_MULTI_RING] = {nullptr, nullptr, nullptr, nullptr};
     MsmPlan mpl{};
+    MultiGuess guess;  // the point pass the seven sums are launched with (point_pass_predict.hpp)
     Scope scope;
     ps_scalars** h = scope.scalars();
     bool sums = false, h_launched = false;
@@ -245,7 +246,8 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     if (!rc && h_first) rc = launch_h();
     if (!rc && cnt) {
         hipEvent_t after_h = (h_first && (*h)->n && c->last_chain) ? c->last_chain->ev_acc_local : nullptr;
-        if (!(rc = msm_multi_points(c, ring, sh.pts, 7, sh.sv, mpl, after_h))) sums = true;
+        guess = msm_multi_guess(c, sh.pts, 7, sh.sv, mpl);
+        if (!(rc = msm_multi_points(c, ring, sh.pts, 7, sh.sv, mpl, after_h, guess.family))) sums = true;
     }
     if (!rc && !h_first) rc = launch_h();
     if (rc) {  // what is in flight finishes before its buffers can be reused
@@ -260,7 +262,7 @@ static int phgr13_share_sums(ps_ctx* c, const Phgr13Share& sh, bool h_first, con
     c->phase_ms[1] = ms_since(t_h);
     const auto t_sums = std::chrono::steady_clock::now();
     if (sums) {
-        int r2 = msm_multi_finish(c, ring[0], sh.pts, 7, mpl, rc ? nullptr : dst);
+        int r2 = msm_multi_finish(c, ring, sh.pts, 7, sh.sv, mpl, guess, rc ? nullptr : dst);
         if (!rc) rc = r2;
     }
     c->phase_ms[2] = ms_since(t_sums);

@@ -183,10 +183,12 @@ template <class KF>
 __global__ void __launch_bounds__(256) k_qfixup(const u32* __restrict__ offs, u32 G, int Mplan, u32 T, u32 LPB,
                                                 const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
                                                 Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
-                                                u32* __restrict__ heavy_count, u32* __restrict__ heavy_list) {
+                                                u32* __restrict__ heavy_count, u32* __restrict__ heavy_list,
+                                                const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
     constexpr u32 GL = QTraits<KF>::GL;
     __shared__ Fp sm[256];
+    if (verdict && *verdict == ACC_BUCKETS) return;  // a sum k_bucket_sum took: nothing below was written for it (msm.hpp section 4b)
     const int M = eff_slice(offs[G], T, Mplan);
     const u32 pt = threadIdx.x / GL;
     const u64 gp = (u64)blockIdx.x * (256 / GL) + pt;
@@ -226,9 +228,11 @@ template <class KF>
 __global__ void __launch_bounds__(256) k_qfixup_chain(const u32* __restrict__ offs, u32 G, int Mplan, u32 T,
                                                       const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
                                                       Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
-                                                      const u32* __restrict__ chain_count, const u32* __restrict__ chain_list) {
+                                                      const u32* __restrict__ chain_count, const u32* __restrict__ chain_list,
+                                                      const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
     constexpr u32 GL = QTraits<KF>::GL, NPB = 256 / GL;
+    if (verdict && *verdict == ACC_BUCKETS) return;  // a sum k_bucket_sum took: nothing below was written for it (msm.hpp section 4b)
     const u32 nchain = *chain_count;
     const int M = eff_slice(offs[G], T, Mplan);
     for (u32 h = blockIdx.x * NPB + threadIdx.x / GL; h < nchain; h += gridDim.x * NPB) {
@@ -261,10 +265,12 @@ __global__ void __launch_bounds__(256) k_qfixup_heavy_part(const u32* __restrict
                                                             const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ parts,
                                                             const u32* __restrict__ heavy_count, const u32* __restrict__ heavy_list,
                                                             const u32* __restrict__ job_base,
-                                                            Xyzz<typename FieldTraits<KF>::Store>* __restrict__ hparts) {
+                                                            Xyzz<typename FieldTraits<KF>::Store>* __restrict__ hparts,
+                                                            const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
     constexpr u32 GL = QTraits<KF>::GL, NPB = 256 / GL;
     __shared__ Fp sm[256];
+    if (verdict && *verdict == ACC_BUCKETS) return;  // a sum k_bucket_sum took: nothing below was written for it (msm.hpp section 4b)
     const u32 nheavy = *heavy_count;
     if (nheavy == 0) return;
     const int M = eff_slice(offs[G], T, Mplan);
@@ -298,10 +304,11 @@ template <class KF>
 __global__ void __launch_bounds__(256) k_qfixup_heavy(const Xyzz<typename FieldTraits<KF>::Store>* __restrict__ hparts,
                                                        Xyzz<typename FieldTraits<KF>::Store>* __restrict__ buckets,
                                                        const u32* __restrict__ heavy_count, const u32* __restrict__ heavy_list,
-                                                       const u32* __restrict__ job_base) {
+                                                       const u32* __restrict__ job_base, const u32* __restrict__ verdict) {
     PS_TAIL_PRIO_HERE;
     constexpr u32 GL = QTraits<KF>::GL, NPB = 256 / GL;
     __shared__ Fp sm[256];
+    if (verdict && *verdict == ACC_BUCKETS) return;  // a sum k_bucket_sum took: nothing below was written for it (msm.hpp section 4b)
     const u32 nheavy = *heavy_count;
     const u32 pt = threadIdx.x / GL;
     for (u32 h = blockIdx.x; h < nheavy; h += gridDim.x) {
