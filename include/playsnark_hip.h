@@ -59,7 +59,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_csr_fr) and ps_qap_wide_entries; then ps_msm_batch, ps_msm_batch_set_chunk and ps_groth16_prove_batch;
  *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table;
  *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info);
- *      then ps_msm_prediction_counts. */
+ *      then ps_msm_prediction_counts; then ps_phgr13_verify_batch_locate and ps_phgr13_verify_batch_locate_info (with the
+ *      new ps_phgr13_locate_info). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -751,7 +752,7 @@ int ps_groth16_verify_batch_locate_info(ps_ctx* ctx, ps_verify_locate_info* out)
  * could cancel (vass + D with wass - D).
  * Every point is untrusted, as in ps_phgr13_verify: encoding, curve and subgroup, PS_ERR_ENCODING otherwise, and
  * ps_last_error() names the proof index and the element of a bad proof point.  A malformed proof fails the CALL: there is
- * no per-proof verdict (a rejected batch can be halved by the caller).  vs_io, ws_io, ys_io of different lengths:
+ * no per-proof verdict (ps_phgr13_verify_batch_locate names the invalid proofs of a rejected batch).  vs_io, ws_io, ys_io of different lengths:
  * PS_ERR_LENGTH.  diff = 0 is legal.  nproofs = 0: *ok = 1.  nproofs = 1 with rho = 1 gives the verdict of ps_phgr13_verify.
  * Needs an empty MSM queue (PS_ERR_ARG), like every one-call form.
  * Caps, checked before any device work: nproofs <= 2^20 and nproofs * (diff + 1) < 2^24; PS_ERR_ARG beyond, with a message
@@ -772,6 +773,62 @@ typedef struct {
 int ps_phgr13_verify_batch(ps_ctx* ctx, const ps_phgr13_vk* vk, const ps_scalars* io, const ps_phgr13_proof* proofs,
                            size_t nproofs, const uint8_t* rho_be32, int* ok);
 int ps_phgr13_verify_batch_info(ps_ctx* ctx, ps_phgr13_batch_info* out); /* of the last batch call on ctx */
+
+/* WHICH proofs of a PHGR13 batch are invalid, and which of the five equations each of them violates.  Arguments,
+ * validation, error codes, messages and caps are exactly those of ps_phgr13_verify_batch (lengths; canonical, non-zero rho;
+ * encoding, curve and subgroup of every point, ps_last_error() naming the proof and the element -- a malformed or
+ * off-subgroup proof fails the CALL with PS_ERR_ENCODING, there is no per-proof "malformed" verdict; an empty MSM queue).
+ * valid[i] = 1 / 0 for proof i, failed[i] (may be NULL) = the mask of the equations proof i violates (bit c = E_c, 0 for a
+ * valid proof), *ninvalid = the number of zeros in valid.  nproofs = 0: *ninvalid = 0 and nothing is written.  nproofs = 1
+ * rejected: valid[0] = 0 and failed[0] = the batch's mask, without a descent.  On an error *ninvalid = 0 and the contents of
+ * valid and failed are unspecified.  Afterwards ps_phgr13_verify_batch_info reports the mask of the whole batch, as after
+ * the plain call.
+ * How: for a set S of proofs the five equations of ps_phgr13_verify_batch restricted to S,
+ *     E0(S)  final_exp(F_S * prod_k miller(P_S,k, ws_k) * miller(-hs_S, yts) * miller(-(yss_S + sum_j t_S,j ys_j), G2)) == 1
+ *     E1(S)  final_exp(miller(vass_S, G2) * miller(-vss_S, av)) == 1
+ *     E2(S)  final_exp(miller(wass_S, G2) * miller(-aw, wss_S)) == 1
+ *     E3(S)  final_exp(miller(yass_S, G2) * miller(-yss_S, ay)) == 1
+ *     E4(S)  final_exp(miller(gz_S, gamma) * miller(-(vss_S + yss_S), bgamma2) * miller(-bgamma, wss_S)) == 1
+ * with X_S = sum_{i in S} rho_i X_i, t_S,j = sum_S rho_i io_ij, P_S,k = sum_S io_ik (rho_i gv_i) and F_S = prod_S
+ * miller(rho_i gv_i, wss_i), are each multiplicative over disjoint unions.  The whole batch is checked exactly as
+ * ps_phgr13_verify_batch checks it; if it is rejected, the sets of a binary tree over the proofs are checked from the root
+ * down, both halves of every failing set, each half only on the equations its parent failed, from partial results kept on
+ * the device (no step passes over the proofs of a set again; the diff loops of E0 of every set run on the device and one
+ * Fp12 value per set comes back).
+ * Soundness: E_c({i}) is proof i's own equation c (PHGR13Verify, pinochio.go:281-378) raised to rho_i != 0, and GT has prime
+ * order, so a set bit of failed[i] is always exact; valid[i] = 1, or an unset bit of failed[i], is wrong only if a check
+ * that passed hid a cancellation: probability <= nproofs / 2^bits(rho) per passed product, over the choice of rho (drawn
+ * after the proofs are fixed).
+ * Cost: an accepted batch is the work of ps_phgr13_verify_batch (one check, five products, nothing else is launched or
+ * allocated beyond the levels of its product tree, kept apart from the key's loops; measured below); b invalid proofs among N cost checks <= 1 + 2 b ceil(log2 N) and
+ * products <= 5 + 2 ceil(log2 N) * sum_i popcount(failed[i]), each product two or three host Miller loops and one final
+ * exponentiation, the products of a level side by side on at most 16 host threads.
+ * Measured (profiles/phgr13_verify_locate.txt; N = 256, 1 024, 4 096, diff = 6 and 63, medians of interleaved runs): an accepted
+ * batch costs the plain call plus 0.9 .. 2.6 ms of extra product launches -- inside the plain call's run-to-run spread (0.5 ..
+ * 8 ms) at diff = 6 and N <= 1 024, but 1.1 .. 2.1 ms (2 .. 4 %) against a spread of 0.2 .. 1.0 ms at diff = 63: not free there.
+ * A rejected batch beats both a loop of ps_phgr13_verify and caller-side halving with ps_phgr13_verify_batch at every
+ * measured point: one bad proof among 4 096 at diff = 6 in 112 ms (one equation failed) or 381 ms (three, E0 among them)
+ * against 1.5 s of halving and 19.6 s of the loop; sixteen in 137 / 497 ms against 15.8 s and 19.6 s.  The smallest margins:
+ * 2.1 x halving (one bad proof, E0 failed, diff = 63, N = 256) and 3.8 x the loop (sixteen, diff = 6, N = 256).
+ * Device memory, kept by the context, on top of the plain call's: 1 344 B per proof for the levels of the product tree
+ * (2 x sizeof Fp12 = 2 x 672) and 672 B per public input; for a rejected batch also, for the trees its failed equations
+ * read, 448 B per proof (2 x sizeof XYZZ G1 = 2 x 224) for each of the up to seven G1 elements and, if E0 failed, for each
+ * public input, 896 B per proof (2 x sizeof XYZZ G2) for wss if E2 or E4 failed, 64 B per proof and per (public input + 1)
+ * for the scalar sums if E0 failed, and while the trees are built 152 B per proof and element (sizeof affine G1 112 + Fr 40)
+ * plus 224 B per proof and 40 B per proof and public input.  A batch that cannot get them fails with PS_ERR_HIP and a
+ * message that gives the bytes asked for. */
+typedef struct {
+    uint32_t checks;    /* sets evaluated, the whole batch included */
+    uint32_t products;  /* pairing products evaluated = final exponentiations: 5 for the batch, then one per tested (set, equation) */
+    uint32_t levels;    /* depth reached below the root (0: accepted, or nproofs <= 1) */
+    uint32_t invalid;   /* proofs reported invalid */
+    uint32_t failed;    /* OR of the masks of the invalid proofs = the batch's ps_phgr13_batch_info.failed */
+    uint32_t reserved[3];
+} ps_phgr13_locate_info;
+int ps_phgr13_verify_batch_locate(ps_ctx* ctx, const ps_phgr13_vk* vk, const ps_scalars* io, const ps_phgr13_proof* proofs,
+                                  size_t nproofs, const uint8_t* rho_be32, uint8_t* valid /* nproofs bytes: 1 / 0 */,
+                                  uint8_t* failed /* nproofs masks, bit c = E_c; may be NULL */, size_t* ninvalid);
+int ps_phgr13_verify_batch_locate_info(ps_ctx* ctx, ps_phgr13_locate_info* out); /* of the last locate call on ctx */
 
 #ifdef __cplusplus
 }

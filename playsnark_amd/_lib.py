@@ -41,6 +41,7 @@ SYMBOLS = [
     "ps_msm_batch_set_table",
     "ps_phgr13_verify_batch", "ps_phgr13_verify_batch_info",
     "ps_msm_prediction_counts",
+    "ps_phgr13_verify_batch_locate", "ps_phgr13_verify_batch_locate_info",
 ]
 
 
@@ -58,6 +59,11 @@ class VerifyLocateInfo(C.Structure):  # ps_verify_locate_info
 
 class Phgr13BatchInfo(C.Structure):  # ps_phgr13_batch_info
     _fields_ = [("failed", C.c_uint32), ("device_loops", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class Phgr13LocateInfo(C.Structure):  # ps_phgr13_locate_info
+    _fields_ = [("checks", C.c_uint32), ("products", C.c_uint32), ("levels", C.c_uint32), ("invalid", C.c_uint32), ("failed", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
 
 
 class Csr(C.Structure):
@@ -241,6 +247,9 @@ def _load():
     lib.ps_groth16_verify_batch_locate_info.argtypes = [vp, C.POINTER(VerifyLocateInfo)]
     lib.ps_phgr13_verify_batch.argtypes = [vp, C.POINTER(Phgr13Vk), vp, C.POINTER(Phgr13Proof), sz, C.c_char_p, C.POINTER(C.c_int)]
     lib.ps_phgr13_verify_batch_info.argtypes = [vp, C.POINTER(Phgr13BatchInfo)]
+    if hasattr(lib, "ps_phgr13_verify_batch_locate"):  # found by symbol: an older build named by PLAYSNARK_HIP_LIB (A/B runs) loads without it
+        lib.ps_phgr13_verify_batch_locate.argtypes = [vp, C.POINTER(Phgr13Vk), vp, C.POINTER(Phgr13Proof), sz, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(sz)]
+        lib.ps_phgr13_verify_batch_locate_info.argtypes = [vp, C.POINTER(Phgr13LocateInfo)]
     lib.ps_qap_column_sums.argtypes = [vp, vp, i, vp, pp]
     lib.ps_groth16_setup_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs)]
     lib.ps_groth16_crs_contribute.argtypes = [vp, C.POINTER(Groth16Crs), C.c_char_p, C.c_char_p, C.POINTER(Groth16Crs)]

@@ -1118,13 +1118,8 @@ def PHGR13Verify(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys
 PHGR13_EQUATIONS = ("division", "v", "w", "y", "linear")  # bit c of PHGR13VerifyBatchInfo()["failed"]: equation E_c
 
 
-def PHGR13VerifyBatch(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, proofs: Sequence["PHGR13Proof"],
-                      ios: Sequence[Poly], rhos: Sequence[int]) -> bool:
-    """PHGR13Verify (pinochio.go:281) for many proofs under one key (ps_phgr13_verify_batch): the five pairing products of
-    the single verifier, each weighted by `rhos` (non-zero, below r, drawn AFTER the proofs are fixed; 128 random bits each
-    are enough) and each checked on its own.  ios[i] are proof i's public inputs (a Poly each, or ONE Poly of
-    len(proofs) * len(vs_io) scalars, proof-major).  Returns the verdict; PHGR13VerifyBatchInfo(ctx) says which of the five
-    equations failed.  A malformed proof raises; there is no per-proof verdict."""
+def _phgr13_batch_args(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, proofs, ios, rhos):
+    """(vk, io, raw proofs, n, rho bytes) as ps_phgr13_verify_batch and ps_phgr13_verify_batch_locate take them"""
     vk = _lib.Phgr13Vk()
     for name in ("av", "aw", "ay", "gamma", "bgamma", "bgamma2", "yts"):
         C.memmove(getattr(vk, name), vk_points[name], len(vk_points[name]))
@@ -1143,9 +1138,50 @@ def PHGR13VerifyBatch(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Point
     if len(rhos) != n:
         raise LengthMismatch(f"{len(rhos)} weights for {n} proofs")
     rho = b"".join(int(v).to_bytes(32, "big") for v in rhos)
+    return vk, io, raw, n, rho
+
+
+def PHGR13VerifyBatch(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, proofs: Sequence["PHGR13Proof"],
+                      ios: Sequence[Poly], rhos: Sequence[int], locate: bool = False):
+    """PHGR13Verify (pinochio.go:281) for many proofs under one key (ps_phgr13_verify_batch): the five pairing products of
+    the single verifier, each weighted by `rhos` (non-zero, below r, drawn AFTER the proofs are fixed; 128 random bits each
+    are enough) and each checked on its own.  ios[i] are proof i's public inputs (a Poly each, or ONE Poly of
+    len(proofs) * len(vs_io) scalars, proof-major).  Returns the verdict; PHGR13VerifyBatchInfo(ctx) says which of the five
+    equations failed.  A malformed proof raises; there is no per-proof verdict: with locate=True a rejected batch is checked
+    proof by proof with PHGR13Verify and the list of the bad indices is returned instead (empty for an accepted batch) --
+    PHGR13VerifyBatchLocate finds them by bisection on the device."""
+    vk, io, raw, n, rho = _phgr13_batch_args(ctx, vk_points, vs_io, ws_io, ys_io, proofs, ios, rhos)
     ok = C.c_int(0)
     _check(lib.ps_phgr13_verify_batch(ctx._h, C.byref(vk), io._h, raw, n, rho, C.byref(ok)))
-    return bool(ok.value)
+    if not locate:
+        return bool(ok.value)
+    if ok.value:
+        return []
+    diff = len(vs_io)
+    return [i for i, p in enumerate(proofs) if not PHGR13Verify(ctx, vk_points, vs_io, ws_io, ys_io, p, io.slice(i * diff, diff))]
+
+
+def PHGR13VerifyBatchLocate(ctx: Context, vk_points: dict, vs_io: Points, ws_io: Points, ys_io: Points, proofs: Sequence["PHGR13Proof"],
+                            ios: Sequence[Poly], rhos: Sequence[int]):
+    """The invalid proofs of a batch and the equations each one violates (ps_phgr13_verify_batch_locate): the batch check of
+    PHGR13VerifyBatch, then, if it fails, a bisection over partial results kept on the device, every half tested only on the
+    equations its parent failed -- at most 1 + 2 b ceil(log2 N) checks for b invalid proofs among N, where locate=True of
+    PHGR13VerifyBatch verifies all N one by one.  Arguments as PHGR13VerifyBatch.  Returns (the bad indices in ascending
+    order, {index: mask of the equations that proof violates, bit c = PHGR13_EQUATIONS[c]}, info) with info = {"checks",
+    "products", "levels", "invalid", "failed"} of the call.  A set bit is exact; "valid", or an unset bit, is relative to the
+    weights, like the batch verdict itself."""
+    vk, io, raw, n, rho = _phgr13_batch_args(ctx, vk_points, vs_io, ws_io, ys_io, proofs, ios, rhos)
+    valid = C.create_string_buffer(max(n, 1))
+    failed = C.create_string_buffer(max(n, 1))
+    ninvalid = C.c_size_t(0)
+    _check(lib.ps_phgr13_verify_batch_locate(ctx._h, C.byref(vk), io._h, raw, n, rho, valid, failed, C.byref(ninvalid)))
+    raw_info = _lib.Phgr13LocateInfo()
+    _check(lib.ps_phgr13_verify_batch_locate_info(ctx._h, C.byref(raw_info)))
+    flags, masks = valid.raw, failed.raw
+    bad = [i for i in range(n) if flags[i] == 0]
+    assert len(bad) == ninvalid.value
+    info = {k: getattr(raw_info, k) for k in ("checks", "products", "levels", "invalid", "failed")}
+    return bad, {i: masks[i] for i in bad}, info
 
 
 def PHGR13VerifyBatchInfo(ctx: Context) -> dict:

@@ -173,6 +173,11 @@ struct ps_ctx : MsmWorkspace {
     DevBuf pvb_rows;
     ps_phgr13_batch_info pvb_info{0, 0, {0, 0}};  // of the last call (ps_phgr13_verify_batch_info)
     float pvb_ms[5] = {0, 0, 0, 0, 0};                   // ... and its stages when timed (ps_debug_phgr13_verify_batch_stage_ms)
+    // ps_phgr13_verify_batch_locate (verify_phgr13_locate.inc): its trees are rebuilt by every rejected batch in the lc_ buffers
+    // above (F tree, G1 trees, scalar tree, ys_io in XYZZ form, the round's workspace) and the wss tree here
+    DevBuf plc_g2;
+    ps_phgr13_locate_info plc_info{0, 0, 0, 0, 0, {0, 0, 0}};  // of the last locate call (ps_phgr13_verify_batch_locate_info)
+    float plc_ms[3] = {0, 0, 0};                               // ... and its descent's wall clock (ps_debug_phgr13_verify_locate_ms)
     u32 simds = 0;                   // SIMDs of the device (how far k_miller_batch spreads a small batch), 0: not asked yet
     // ps_msm_be32 / ps_msm_i64 (seam S1: one upload per BlindEval call): the converted scalars of the call live in a vector
     // the context keeps, so a call does not pay a hipMalloc and a hipFree (which synchronises the device) of 32 bytes per
@@ -2163,7 +2168,9 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "locate_dev.hpp"
 #include "verify_batch.inc"
 #include "verify_locate.inc"
+#include "locate_phgr13_dev.hpp"
 #include "verify_phgr13_batch.inc"
+#include "verify_phgr13_locate.inc"
 #include "srs_setup.inc"
 #include "srs_phase1.inc"
 #include "crs_check.inc"

@@ -46,8 +46,10 @@ PS_HD static inline const Base2& f12_coeff(const Fp12& a, int d) {
     const Fp6& h = (d & 1) ? a.c1 : a.c0;
     return (d >> 1) == 0 ? h.c0 : (d >> 1) == 1 ? h.c1 : h.c2;
 }
+// (f12_mul_coeff and f12_mul_mem are forced inline: left to the inliner they went out of line the day a second kernel,
+// k_f12_segment_products of locate_phgr13_dev.hpp, called them, and k_f12_product went from 187 registers to 280 + 32.)
 PS_HD static inline Base2 f2_reduce(const Base2& a) { return Base2{fp_mul_call(f_norm(a.c0), fp_one()), fp_mul_call(f_norm(a.c1), fp_one())}; }
-PS_HD static inline Base2 f12_mul_coeff(const Fp12& a, const Fp12& b, int d) {
+PS_HD static inline __attribute__((always_inline)) Base2 f12_mul_coeff(const Fp12& a, const Fp12& b, int d) {
     Base2 lo = f_zero((const Base2*)0), hi = f_zero((const Base2*)0);
     for (int d1 = 0; d1 < 6; d1++) {
         const int d2 = d1 <= d ? d - d1 : d + 6 - d1;
@@ -56,7 +58,7 @@ PS_HD static inline Base2 f12_mul_coeff(const Fp12& a, const Fp12& b, int d) {
     }
     return f_norm(f_add(f2_reduce(lo), mul_xi(f2_reduce(hi))));
 }
-PS_HD static inline void f12_mul_mem(Fp12& out, const Fp12& a, const Fp12& b) {  // out must not alias a or b
+PS_HD static inline __attribute__((always_inline)) void f12_mul_mem(Fp12& out, const Fp12& a, const Fp12& b) {  // out must not alias a or b
     out.c0.c0 = f12_mul_coeff(a, b, 0); out.c1.c0 = f12_mul_coeff(a, b, 1);
     out.c0.c1 = f12_mul_coeff(a, b, 2); out.c1.c1 = f12_mul_coeff(a, b, 3);
     out.c0.c2 = f12_mul_coeff(a, b, 4); out.c1.c2 = f12_mul_coeff(a, b, 5);

@@ -13,6 +13,8 @@
 // ps_msm_batch over the columns of io (k_gather_words transposes them); the eight S_X: ONE ps_msm_multi; t: weighted_columns;
 // the loops and their product: k_miller_batch, k_f12_product (verify_batch.inc).  The host runs the remaining eleven loops
 // and the five final exponentiations on its threads, as ps_phgr13_verify does.
+// The body is phgr13_verify_batch_impl, which ps_phgr13_verify_batch_locate (verify_phgr13_locate.inc) calls too: there it keeps
+// the levels of the product tree and hands a rejected batch's device state over (PvbKeep).
 
 constexpr size_t PS_PHGR13_VERIFY_BATCH_MAX = (size_t)1 << 20;
 constexpr size_t PS_PHGR13_VERIFY_BATCH_TERMS = (size_t)1 << 24;  // proofs x (diff + 1): the two XYZZ buffers of the segments are 2 x 224 B each
@@ -45,9 +47,26 @@ static int first_outside_subgroup(ps_ctx* c, const ps_points* arr, size_t* idx) 
     return PS_OK;
 }
 
-static int phgr13_verify_batch_impl(ps_ctx* c, const ps_phgr13_vk* vk, const ps_scalars* io, const ps_phgr13_proof* proofs, size_t nproofs,
-                                    const uint8_t* rho_be32, int* ok) {
-    const std::string fn = "ps_phgr13_verify_batch";
+// What a REJECTED batch hands to the descent of ps_phgr13_verify_batch_locate (verify_phgr13_locate.inc) instead of freeing
+// it, in the manner of VbKeep: rho (plain words; its Montgomery form stays in c->vb_rho until the next call), the views of the
+// seven G1 elements and of wss, rho_i gv_i (affine, the P_k behind them), the transposed inputs, and the key's points.  The
+// handles are the holder's from then on.  The Miller values stay where phgr13_miller_levels put them (c->lc_f12).
+struct PvbKeep {
+    ps_scalars *rho = nullptr, *iot = nullptr;
+    ps_points* view[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // vss vass wass yss yass hs gz | wss
+    ps_points *g1 = nullptr, *rgv = nullptr;  // what the G1 views are slices of; rho_i gv_i
+    Affine<Fp> aw, bgamma;
+    Affine<Fp2> av, ay, gamma, bgamma2, yts;
+};
+// verify_phgr13_locate.inc: k_miller_batch over the n + diff pairs, the product tree over the first n values with every
+// level kept (c->lc_f12), the key's loops multiplied in separately; *res is the batch's product
+static int phgr13_miller_levels(ps_ctx* c, const std::string& fn, const Affine<Fp>* g1, const Affine<Fp2>* g2, size_t n, size_t diff,
+                                const pairing_dev::Fp12** res);
+
+// The batch check behind ps_phgr13_verify_batch (fn = its name, keep = nullptr) and ps_phgr13_verify_batch_locate (its own
+// name; keep != nullptr: the levels of the product tree are retained and a rejected batch fills *keep).
+static int phgr13_verify_batch_impl(ps_ctx* c, const std::string& fn, const ps_phgr13_vk* vk, const ps_scalars* io, const ps_phgr13_proof* proofs,
+                                    size_t nproofs, const uint8_t* rho_be32, int* ok, PvbKeep* keep) {
     VbClock clk(c, c->pvb_ms, PS_PVB_STAGES);
     if (c->q_len) return fail(PS_ERR_ARG, fn + ": sums are pending on this context (ps_msm_finish them first)");
     const size_t N = nproofs, diff = vk->vs_io->n, cols = diff + 1, pd = std::max<size_t>(diff, 1);
@@ -118,8 +137,9 @@ static int phgr13_verify_batch_impl(ps_ctx* c, const ps_phgr13_vk* vk, const ps_
         return fail(PS_ERR_ENCODING, fn + ": " + (arr->group == PS_G1 ? g1_names[bad / N] : "wss") + " of proof " + std::to_string(bad % N) +
                                          " is outside the order-r subgroup");
     }
+    ps_points** views[NG1];
     for (int e = 0; e < NG1; e++) {
-        ps_points** v = scope.points();
+        ps_points** v = views[e] = scope.points();
         if ((rc = ps_points_slice(*g1, e * N, N, v))) return rc;
         view[e] = *v;
     }
@@ -193,7 +213,9 @@ static int phgr13_verify_batch_impl(ps_ctx* c, const ps_phgr13_vk* vk, const ps_
     // the device's share of E0: N + diff loops and their product in ONE launch each, only enqueued here -- the sums below
     // queue up behind them
     const pairing_dev::Fp12* fdev = nullptr;
-    if ((rc = miller_product_launch(c, (const Affine<Fp>*)points_ptr(*g1m), (const Affine<Fp2>*)points_ptr(*g2m), N + diff, &fdev))) return rc;
+    rc = keep ? phgr13_miller_levels(c, fn, (const Affine<Fp>*)points_ptr(*g1m), (const Affine<Fp2>*)points_ptr(*g2m), N, diff, &fdev)
+              : miller_product_launch(c, (const Affine<Fp>*)points_ptr(*g1m), (const Affine<Fp2>*)points_ptr(*g2m), N + diff, &fdev);
+    if (rc) return rc;
     clk.mark(3);
     // the eight S_X: one sort of rho, eight point passes
     uint8_t sb[NG1][96], swss[192], tyb[96];
@@ -238,6 +260,17 @@ static int phgr13_verify_batch_impl(ps_ctx* c, const ps_phgr13_vk* vk, const ps_
     c->pvb_info.device_loops = (u32)(N + diff);
     *ok = failed ? 0 : 1;
     clk.mark(4);
+    if (keep && failed) {  // out of the scope's slots: the holder's from here on
+        auto take = [](auto** slot) { auto* h = *slot; *slot = nullptr; return h; };
+        for (int e = 0; e < NG1; e++) keep->view[e] = take(views[e]);
+        keep->view[NG1] = take(wss);
+        keep->g1 = take(g1);
+        keep->rgv = take(g1m);
+        keep->rho = take(rho);
+        keep->iot = take(iot);
+        keep->aw = aw; keep->bgamma = bgamma;
+        keep->av = av; keep->ay = ay; keep->gamma = gamma; keep->bgamma2 = bgamma2; keep->yts = yts;
+    }
     return scope.finish(PS_OK);
 }
 
@@ -247,7 +280,7 @@ extern "C" int ps_phgr13_verify_batch(ps_ctx* c, const ps_phgr13_vk* vk, const p
         return fail(PS_ERR_ARG, "ps_phgr13_verify_batch: NULL argument");
     *ok = 0;
     c->pvb_info = ps_phgr13_batch_info{0, 0, {0, 0}};
-    return phgr13_verify_batch_impl(c, vk, io, proofs, nproofs, rho_be32, ok);
+    return phgr13_verify_batch_impl(c, "ps_phgr13_verify_batch", vk, io, proofs, nproofs, rho_be32, ok, nullptr);
 }
 
 extern "C" int ps_phgr13_verify_batch_info(ps_ctx* c, ps_phgr13_batch_info* out) {

@@ -348,6 +348,22 @@ inline bool PHGR13VerifyBatch(Context& c, const ps_phgr13_vk& vk, const Poly& io
     if (info) check(ps_phgr13_verify_batch_info(c.get(), info));
     return ok != 0;
 }
+// The invalid proofs of a PHGR13 batch, by bisection over partial results kept on the device (ps_phgr13_verify_batch_locate):
+// their indices in ascending order, empty for an accepted batch.  *masks (optional): per proof the equations it violates
+// (bit c = E_c, 0 for a valid proof); *info (optional): checks, products, depth, count and the batch's mask
+inline std::vector<size_t> PHGR13VerifyBatchLocate(Context& c, const ps_phgr13_vk& vk, const Poly& io, const std::vector<ps_phgr13_proof>& proofs,
+                                                   const uint8_t* rho_be32, std::vector<uint8_t>* masks = nullptr, ps_phgr13_locate_info* info = nullptr) {
+    const size_t n = proofs.size();
+    std::vector<uint8_t> valid(n ? n : 1, 1), failed(n ? n : 1, 0);
+    size_t ninvalid = 0;
+    check(ps_phgr13_verify_batch_locate(c.get(), &vk, io.get(), proofs.data(), n, rho_be32, valid.data(), failed.data(), &ninvalid));
+    if (info) check(ps_phgr13_verify_batch_locate_info(c.get(), info));
+    std::vector<size_t> bad;
+    for (size_t i = 0; i < n; i++)
+        if (!valid[i]) bad.push_back(i);
+    if (masks) masks->assign(failed.begin(), failed.begin() + n);
+    return bad;
+}
 // func NewGroth16TrustedSetup(qap QAP) Groth16Setup (groth16.go:64), toxic waste drawn by the caller
 inline ps_groth16_crs NewGroth16TrustedSetup(Context& c, const QAP& q, const ps_groth16_toxic& tw) {
     ps_groth16_crs out;

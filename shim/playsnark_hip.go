@@ -1377,6 +1377,21 @@ func PHGR13VerifyBatchHIP(hp *HipPHGR13, proofs []PHGR13Proof, ios []Vector) (bo
 	if len(proofs) == 0 {
 		return true, 0
 	}
+	raw, rho, all := phgr13BatchInputs(proofs, ios)
+	dio := uploadSolution(all)
+	defer C.ps_scalars_free(dio)
+	var ok C.int
+	call(func() C.int {
+		return C.ps_phgr13_verify_batch(hipCtx, &hp.vk, dio, &raw[0], C.size_t(len(proofs)), u8(rho), &ok)
+	})
+	var info C.ps_phgr13_batch_info
+	call(func() C.int { return C.ps_phgr13_verify_batch_info(hipCtx, &info) })
+	return ok != 0, uint32(info.failed)
+}
+
+// phgr13BatchInputs lays the proofs out as the batch entries take them, draws one 128-bit weight per proof (after the proofs
+// are in hand) and joins the public inputs proof-major.
+func phgr13BatchInputs(proofs []PHGR13Proof, ios []Vector) ([]C.ps_phgr13_proof, []byte, Vector) {
 	var all Vector
 	raw := make([]C.ps_phgr13_proof, len(proofs))
 	rho := make([]byte, 32*len(proofs))
@@ -1398,15 +1413,42 @@ func PHGR13VerifyBatchHIP(hp *HipPHGR13, proofs []PHGR13Proof, ios []Vector) (bo
 			}
 		}
 	}
+	return raw, rho, all
+}
+
+// PHGR13VerifyBatchLocateHIP names the invalid proofs of a batch and the equations each one violates
+// (ps_phgr13_verify_batch_locate): the batch check of PHGR13VerifyBatchHIP first, then, if it fails, a bisection over partial
+// results kept on the device, every half tested only on the equations its parent failed -- at most 1 + 2 b ceil(log2 N)
+// checks for b invalid proofs among N.  The weights are drawn here, as in PHGR13VerifyBatchHIP.  Returns the indices of the
+// invalid proofs in ascending order (nil for an accepted batch), their masks (bit 0 division, 1 v, 2 w, 3 y, 4 linear) in the
+// same order, and the number of pairing products evaluated.
+func PHGR13VerifyBatchLocateHIP(hp *HipPHGR13, proofs []PHGR13Proof, ios []Vector) ([]int, []uint8, int) {
+	if len(proofs) != len(ios) {
+		panic("PHGR13VerifyBatchLocateHIP: one public-input vector per proof")
+	}
+	if len(proofs) == 0 {
+		return nil, nil, 0
+	}
+	raw, rho, all := phgr13BatchInputs(proofs, ios)
 	dio := uploadSolution(all)
 	defer C.ps_scalars_free(dio)
-	var ok C.int
+	valid := make([]byte, len(proofs))
+	failed := make([]byte, len(proofs))
+	var ninvalid C.size_t
+	var info C.ps_phgr13_locate_info
 	call(func() C.int {
-		return C.ps_phgr13_verify_batch(hipCtx, &hp.vk, dio, &raw[0], C.size_t(len(proofs)), u8(rho), &ok)
+		return C.ps_phgr13_verify_batch_locate(hipCtx, &hp.vk, dio, &raw[0], C.size_t(len(proofs)), u8(rho), u8(valid), u8(failed), &ninvalid)
 	})
-	var info C.ps_phgr13_batch_info
-	call(func() C.int { return C.ps_phgr13_verify_batch_info(hipCtx, &info) })
-	return ok != 0, uint32(info.failed)
+	call(func() C.int { return C.ps_phgr13_verify_batch_locate_info(hipCtx, &info) })
+	var bad []int
+	var masks []uint8
+	for i, v := range valid {
+		if v == 0 {
+			bad = append(bad, i)
+			masks = append(masks, failed[i])
+		}
+	}
+	return bad, masks, int(info.products)
 }
 
 // HipPHGR13Multi: every device holds only ITS index ranges of the evaluation key -- vs .. ybs over len(vs), gsi over
