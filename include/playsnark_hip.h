@@ -60,7 +60,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      then ps_msm_batch_multi and ps_phgr13_prove_batch; then ps_msm_batch_set_table;
  *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info);
  *      then ps_msm_prediction_counts; then ps_phgr13_verify_batch_locate and ps_phgr13_verify_batch_locate_info (with the
- *      new ps_phgr13_locate_info). */
+ *      new ps_phgr13_locate_info).  Then ps_poly_scan_tile, ps_poly_eval, ps_poly_div_linear, ps_kzg_commit, ps_kzg_open,
+ *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -829,6 +830,56 @@ int ps_phgr13_verify_batch_locate(ps_ctx* ctx, const ps_phgr13_vk* vk, const ps_
                                   size_t nproofs, const uint8_t* rho_be32, uint8_t* valid /* nproofs bytes: 1 / 0 */,
                                   uint8_t* failed /* nproofs masks, bit c = E_c; may be NULL */, size_t* ninvalid);
 int ps_phgr13_verify_batch_locate_info(ps_ctx* ctx, ps_phgr13_locate_info* out); /* of the last locate call on ctx */
+
+/* ---- KZG polynomial commitments over the powers-of-tau string: Poly.Commit / PolyCommit, Poly.Eval (algebra.go:107-115)
+ *      and Poly.Div by a linear factor (algebra.go:119-137) ----
+ * The commitment of p (n coefficients, lowest degree first) is C = sum_i p_i tau_g1[i] = [p(tau)] G1; the proof that
+ * p(z) = y is pi = [q(tau)] G1 with q = (p(X) - y) / (X - z); anybody checks e(C - y G1 + z pi, G2) = e(pi, tau G2).  Entry
+ * points added within revision 5 (found by symbol, no struct at all).
+ * Shared conventions: z, y and rho are 32-byte big-endian and canonical (PS_ERR_ENCODING otherwise); a NULL argument is
+ * PS_ERR_ARG; an empty p is PS_ERR_LENGTH; k = 0 is PS_OK with no output buffer written; k * n >= 2^32 is PS_ERR_ARG (split the
+ * points).  p may be a view (ps_scalars_slice).
+ *
+ * Value and quotient come from ONE recurrence, h_n = 0, h_i = p_i + z h_{i+1}: h_0 = p(z) and q_{i-1} = h_i -- on the device
+ * a scan in three launches (tile totals, one carry walk per point, apply), for all k points at once.
+ * ps_poly_scan_tile: the coefficients per workgroup of that scan (tests sit on its edges; a constant of the build). */
+int ps_poly_scan_tile(void);
+/* y[j] = p(z_j), j < k: y_be32 has k * 32 bytes.  (Poly.Eval, algebra.go:107-115.) */
+int ps_poly_eval(ps_ctx* ctx, const ps_scalars* p, const uint8_t* z_be32, size_t k, uint8_t* y_be32);
+/* *q: k * (n - 1) scalars, row j = the quotient of p by (X - z_j), lowest degree first -- member-major, the layout
+ * ps_msm_batch reads; rem[j] = p(z_j).  Poly.Div (algebra.go:119-137) with the divisor (1, -z) of the reference's
+ * highest-first order.  n = 1: PS_ERR_LENGTH (no quotient to hold).  k = 0: *q is an empty vector.  Caller frees *q. */
+int ps_poly_div_linear(ps_ctx* ctx, const ps_scalars* p, const uint8_t* z_be32, size_t k, ps_scalars** q, uint8_t* rem_be32);
+/* out = sum_i p_i tau_g1[i]: ps_msm over the first n points of the string, which may be longer than p; a shorter string is
+ * PS_ERR_LENGTH (algebra.go:350-352), a G2 array PS_ERR_ARG.  Needs an empty MSM queue. */
+int ps_kzg_commit(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* p, uint8_t out[96]);
+/* y[j] = p(z_j) and proofs[j] = [q_j(tau)] G1, j < k (k * 32 and k * 96 bytes): values and quotients on the device, then ONE
+ * ps_msm_batch of the k quotient rows over tau_g1[0 .. n-1); the quotients never leave the device.  Proof j is byte-identical
+ * to ps_msm over that view and row j of ps_poly_div_linear.  n = 1: y = p_0 and identity proofs, without a division.  The string
+ * must hold at least n points (the commitment being opened needs them; PS_ERR_LENGTH).  Needs an empty MSM queue
+ * (PS_ERR_ARG otherwise), as the other composite entries do. */
+int ps_kzg_open(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* p, const uint8_t* z_be32, size_t k, uint8_t* y_be32,
+                uint8_t* proofs /* k x 96 */);
+/* *ok = 1 iff e(commit - y G1 + z proof, G2) = e(proof, tau_g2_1), tau_g2_1 being the string's tau_g2[1] = tau G2.  Host only
+ * (the ate pairing of the verifiers, two Miller loops and one final exponentiation).  A point that is not canonical or not
+ * on the curve: PS_ERR_ENCODING; a point outside the order-r subgroup: *ok = 0. */
+int ps_kzg_verify(const uint8_t tau_g2_1[192], const uint8_t commit[96], const uint8_t z_be32[32], const uint8_t y_be32[32],
+                  const uint8_t proof[96], int* ok);
+/* k openings (C_j, z_j, y_j, pi_j) under ONE string -- polynomials and points may all differ -- by random linear combination:
+ *     e(sum_j rho_j (C_j + z_j pi_j) - (sum_j rho_j y_j) G1, G2) * e(-sum_j rho_j pi_j, tau_g2_1) == 1
+ * -- two sums over the uploaded points (ps_msm), the scalars rho_j z_j and sum rho_j y_j on the host, one two-pair product.
+ * commits, proofs: k * 96 bytes; z, y, rho: k * 32.  rho: canonical (PS_ERR_ENCODING), non-zero (PS_ERR_ARG: a zero weight
+ * would skip an opening), drawn by the caller AFTER commitments, points, values and proofs are fixed, as for
+ * ps_groth16_verify_batch; 128 random bits each are enough.
+ * *ok = 1 iff the combined equation holds.  Every opening valid => 1 for every rho.  Some opening invalid => the left side
+ * is the product of the single equations' values raised to rho_j, a non-trivial linear form in the rho_j over a group of
+ * prime order, so *ok = 1 with probability <= 1 / (2^bits(rho) - 1) over the choice of rho (the false-accept bound; with
+ * equal weights two errors can cancel: y_1 + d with y_2 - d).
+ * Encodings and the curve equation are always tested (PS_ERR_ENCODING).  check_subgroup != 0: commitments and proofs go
+ * through ps_points_check_subgroup and tau_g2_1 is tested likewise; a point outside the subgroup gives *ok = 0 (0 only for
+ * points the caller made itself).  k = 0: *ok = 1.  k <= 2^24 (PS_ERR_ARG beyond).  Needs an empty MSM queue. */
+int ps_kzg_verify_batch(ps_ctx* ctx, const uint8_t tau_g2_1[192], const uint8_t* commits, const uint8_t* z_be32, const uint8_t* y_be32,
+                        const uint8_t* proofs, const uint8_t* rho_be32, size_t k, int check_subgroup, int* ok);
 
 #ifdef __cplusplus
 }

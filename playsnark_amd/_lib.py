@@ -42,6 +42,7 @@ SYMBOLS = [
     "ps_phgr13_verify_batch", "ps_phgr13_verify_batch_info",
     "ps_msm_prediction_counts",
     "ps_phgr13_verify_batch_locate", "ps_phgr13_verify_batch_locate_info",
+    "ps_poly_scan_tile", "ps_poly_eval", "ps_poly_div_linear", "ps_kzg_commit", "ps_kzg_open", "ps_kzg_verify", "ps_kzg_verify_batch",
 ]
 
 
@@ -262,6 +263,14 @@ def _load():
                                                 C.POINTER(C.c_int)]
     lib.ps_points_lagrange_check.argtypes = [vp, vp, vp, vp, i, C.c_char_p, sz, C.POINTER(C.c_int)]
     lib.ps_groth16_crs_check_from_srs.argtypes = [vp, vp, C.POINTER(Groth16Srs), C.POINTER(Groth16Crs), C.c_char_p, sz, i, C.POINTER(C.c_int)]
+    if hasattr(lib, "ps_kzg_open"):  # found by symbol: an older build named by PLAYSNARK_HIP_LIB (A/B runs) loads without KZG
+        lib.ps_poly_scan_tile.argtypes = []
+        lib.ps_poly_eval.argtypes = [vp, vp, C.c_char_p, sz, C.c_char_p]
+        lib.ps_poly_div_linear.argtypes = [vp, vp, C.c_char_p, sz, pp, C.c_char_p]
+        lib.ps_kzg_commit.argtypes = [vp, vp, vp, C.c_char_p]
+        lib.ps_kzg_open.argtypes = [vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
+        lib.ps_kzg_verify.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
+        lib.ps_kzg_verify_batch.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, i, C.POINTER(C.c_int)]
     return lib
 
 

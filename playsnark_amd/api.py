@@ -349,6 +349,23 @@ class Poly:
         _check(lib.ps_msm(self.ctx._h, blindedPoint._h, self._h, out))
         return out.raw
 
+    def Eval(self, zs: Sequence[int]) -> list:
+        """func (p Poly) Eval(i Element) Element (algebra.go:107-115) at every point of zs, on the device (ps_poly_eval)."""
+        k = len(zs)
+        out = C.create_string_buffer(32 * max(k, 1))
+        _check(lib.ps_poly_eval(self.ctx._h, self._h, _rho_bytes(zs), k, out))
+        return [int.from_bytes(out.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+
+    def DivLinear(self, zs: Sequence[int]):
+        """func (p Poly) Div(p2 Poly) (algebra.go:119-137) by the linear factors (X - z), z in zs, all at once
+        (ps_poly_div_linear).  Returns (q, rems): q a Poly of len(zs) * (len(p) - 1) coefficients, row j the quotient by
+        (X - zs[j]), lowest degree first -- the layout msm_batch reads -- and rems[j] = p(zs[j])."""
+        k = len(zs)
+        h = C.c_void_p()
+        rem = C.create_string_buffer(32 * max(k, 1))
+        _check(lib.ps_poly_div_linear(self.ctx._h, self._h, _rho_bytes(zs), k, C.byref(h), rem))
+        return Poly(self.ctx, h), [int.from_bytes(rem.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+
     def free(self):
         if self._h:
             lib.ps_scalars_free(self._h)
@@ -770,7 +787,46 @@ def Groth16SRSCheckUpdate(ctx: Context, before: Groth16SRS, after: Groth16SRS, s
     return bool(ok.value)
 
 
-_CRS_ARRAYS = ("xi", "xi2", "io_lp", "nio_lp", "xi_t", "lxi", "lxi2", "lxi_t")
+def KZGCommit(tau_g1: Points, p: Poly) -> bytes:
+    """func (p Poly) Commit: [p(tau)] G1 = sum_i p_i tau_g1[i] over the first len(p) powers of the string (ps_kzg_commit).
+    The string may be longer than p; a shorter one raises LengthMismatch."""
+    out = C.create_string_buffer(96)
+    _check(lib.ps_kzg_commit(p.ctx._h, tau_g1._h, p._h, out))
+    return out.raw
+
+
+def KZGOpen(tau_g1: Points, p: Poly, zs: Sequence[int]):
+    """(ys, proofs): ys[j] = p(zs[j]) and proofs[j] = [q_j(tau)] G1 with q_j = (p - ys[j]) / (X - zs[j]) (ps_kzg_open): values
+    and quotients on the device, then one batched sum of the quotient rows over the string."""
+    k = len(zs)
+    ys = C.create_string_buffer(32 * max(k, 1))
+    proofs = C.create_string_buffer(96 * max(k, 1))
+    _check(lib.ps_kzg_open(p.ctx._h, tau_g1._h, p._h, _rho_bytes(zs), k, ys, proofs))
+    return ([int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], [proofs.raw[96 * j : 96 * j + 96] for j in range(k)])
+
+
+def KZGVerify(tau_g2_1: bytes, commit: bytes, z: int, y: int, proof: bytes) -> bool:
+    """e(C - y G1 + z pi, G2) == e(pi, tau G2), on the host (ps_kzg_verify); tau_g2_1 = the string's tau_g2[1].  A point outside
+    the subgroup gives False, a malformed one raises."""
+    ok = C.c_int(0)
+    _check(lib.ps_kzg_verify(bytes(tau_g2_1), bytes(commit), _be32(z), _be32(y), bytes(proof), C.byref(ok)))
+    return bool(ok.value)
+
+
+def KZGVerifyBatch(ctx: Context, tau_g2_1: bytes, commits: Sequence[bytes], zs: Sequence[int], ys: Sequence[int], proofs: Sequence[bytes],
+                   rhos: Sequence[int], check_subgroup: bool = True) -> bool:
+    """len(commits) openings under one string in one weighted equation (ps_kzg_verify_batch).  rhos: one non-zero weight below
+    r per opening, drawn AFTER everything else is fixed (128 random bits each are enough)."""
+    k = len(commits)
+    if not (len(zs) == len(ys) == len(proofs) == len(rhos) == k):
+        raise LengthMismatch("KZGVerifyBatch: commits, zs, ys, proofs and rhos must have one length")
+    ok = C.c_int(0)
+    _check(lib.ps_kzg_verify_batch(ctx._h, bytes(tau_g2_1), b"".join(commits), _rho_bytes(zs), _rho_bytes(ys), b"".join(proofs), _rho_bytes(rhos), k,
+                                   int(check_subgroup), C.byref(ok)))
+    return bool(ok.value)
+
+
+_CRS_ARRAYS =("xi", "xi2", "io_lp", "nio_lp", "xi_t", "lxi", "lxi2", "lxi_t")
 
 
 def _crs_to_pair(ctx: Context, crs: "_lib.Groth16Crs"):

@@ -23,6 +23,7 @@
 #include "msm_batch_plan.hpp"
 #include "msm_batch_multi_plan.hpp"
 #include "quotient.hpp"
+#include "poly_scan.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"
@@ -2174,3 +2175,4 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "srs_setup.inc"
 #include "srs_phase1.inc"
 #include "crs_check.inc"
+#include "kzg.inc"

@@ -924,6 +924,128 @@ func CheckFromSRSHIP(srs *HipGroth16SRS, key *HipGroth16, checkSubgroup bool) bo
 	return ok != 0
 }
 
+// ---------------------------------------------------------------------------------------
+// KZG commitments over the string's tau_g1: Poly.Commit / PolyCommit, Poly.Eval (algebra.go:107-115) and Poly.Div by a
+// linear factor (algebra.go:119-137)
+// ---------------------------------------------------------------------------------------
+
+func uploadPoly(p Poly) *C.ps_scalars {
+	var h *C.ps_scalars
+	raw := marshalScalars(p)
+	call(func() C.int { return C.ps_scalars_upload(hipCtx, u8(raw), C.size_t(len(p)), &h) })
+	return h
+}
+
+func elementsFrom(raw []byte) []Element {
+	out := make([]Element, len(raw)/32)
+	for i := range out {
+		e := NewElement()
+		if err := e.UnmarshalBinary(raw[32*i : 32*i+32]); err != nil {
+			panic(err)
+		}
+		out[i] = e
+	}
+	return out
+}
+
+// PolyScanTile is the number of coefficients one workgroup of the device scan owns (ps_poly_scan_tile).
+func PolyScanTile() int { return int(C.ps_poly_scan_tile()) }
+
+// EvalHIP replaces `func (p Poly) Eval(i Element) Element` for several points at once (ps_poly_eval).
+func (p Poly) EvalHIP(zs []Element) []Element {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	call(func() C.int { return C.ps_poly_eval(hipCtx, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys)) })
+	return elementsFrom(ys)
+}
+
+// DivLinearHIP replaces `func (p Poly) Div(p2 Poly)` for the divisors (X - z), z in zs: the quotients, lowest degree first,
+// and the remainders p(z) (ps_poly_div_linear).
+func (p Poly) DivLinearHIP(zs []Element) ([]Poly, []Element) {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	var q *C.ps_scalars
+	rem := make([]byte, 32*len(zs))
+	call(func() C.int { return C.ps_poly_div_linear(hipCtx, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), &q, u8(rem)) })
+	defer C.ps_scalars_free(q)
+	all := downloadPoly(q)
+	rows := make([]Poly, len(zs))
+	for j := range rows {
+		rows[j] = all[j*(len(p)-1) : (j+1)*(len(p)-1)]
+	}
+	return rows, elementsFrom(rem)
+}
+
+// KZGCommit replaces `func (p Poly) Commit`: [p(tau)] G1 over the string's first len(p) powers (ps_kzg_commit).
+func KZGCommit(srs *HipGroth16SRS, p Poly) Commit {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	out := make([]byte, g1Wire)
+	call(func() C.int { return C.ps_kzg_commit(hipCtx, srs.s.tau_g1, h, u8(out)) })
+	return pointFrom(C.PS_G1, out, zeroG1)
+}
+
+// KZGOpen returns p(z) and the opening proof [q_z(tau)] G1 for every z in zs (ps_kzg_open).
+func KZGOpen(srs *HipGroth16SRS, p Poly, zs []Element) ([]Element, []Commit) {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	raw := make([]byte, g1Wire*len(zs))
+	call(func() C.int {
+		return C.ps_kzg_open(hipCtx, srs.s.tau_g1, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys), u8(raw))
+	})
+	proofs := make([]Commit, len(zs))
+	for j := range proofs {
+		proofs[j] = pointFrom(C.PS_G1, raw[g1Wire*j:g1Wire*(j+1)], zeroG1)
+	}
+	return elementsFrom(ys), proofs
+}
+
+// tauG2 fetches tau G2 = tau_g2[1] of the string, affine.
+func tauG2(srs *HipGroth16SRS) []byte {
+	out := make([]byte, g2Wire)
+	call(func() C.int { return C.ps_points_download(hipCtx, srs.s.tau_g2, 1, 1, u8(out)) })
+	return out
+}
+
+// KZGVerify checks one opening: e(C - y G1 + z pi, G2) == e(pi, tau G2), on the host (ps_kzg_verify).
+func KZGVerify(srs *HipGroth16SRS, commit Commit, z, y Element, proof Commit) bool {
+	t2 := tauG2(srs)
+	var ok C.int
+	check(func() C.int {
+		return C.ps_kzg_verify(u8(t2), u8(affineOf(C.PS_G1, commit)), u8(mustMarshalElement(z)), u8(mustMarshalElement(y)),
+			u8(affineOf(C.PS_G1, proof)), &ok)
+	})
+	return ok != 0
+}
+
+// KZGVerifyBatch checks len(commits) openings under one string in one weighted equation (ps_kzg_verify_batch).  The weights
+// are drawn here, after everything else is in hand.  checkSubgroup = false only for points this process made itself.
+func KZGVerifyBatch(srs *HipGroth16SRS, commits []Commit, zs, ys []Element, proofs []Commit, checkSubgroup bool) bool {
+	k := len(commits)
+	if len(zs) != k || len(ys) != k || len(proofs) != k {
+		panic(fmt.Sprintf("KZGVerifyBatch: %d commitments, %d points, %d values, %d proofs", k, len(zs), len(ys), len(proofs)))
+	}
+	t2 := tauG2(srs)
+	cs, ps := make([]byte, 0, g1Wire*k), make([]byte, 0, g1Wire*k)
+	for j := 0; j < k; j++ {
+		cs = append(cs, affineOf(C.PS_G1, commits[j])...)
+		ps = append(ps, affineOf(C.PS_G1, proofs[j])...)
+	}
+	rho := drawWeights(k)
+	sub := C.int(0)
+	if checkSubgroup {
+		sub = 1
+	}
+	var ok C.int
+	call(func() C.int {
+		return C.ps_kzg_verify_batch(hipCtx, u8(t2), u8(cs), u8(marshalScalars(Poly(zs))), u8(marshalScalars(Poly(ys))), u8(ps), u8(rho),
+			C.size_t(k), sub, &ok)
+	})
+	return ok != 0
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
