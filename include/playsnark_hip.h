@@ -61,7 +61,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      then ps_phgr13_verify_batch and ps_phgr13_verify_batch_info (with the new ps_phgr13_batch_info);
  *      then ps_msm_prediction_counts; then ps_phgr13_verify_batch_locate and ps_phgr13_verify_batch_locate_info (with the
  *      new ps_phgr13_locate_info).  Then ps_poly_scan_tile, ps_poly_eval, ps_poly_div_linear, ps_kzg_commit, ps_kzg_open,
- *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all). */
+ *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all).  Then ps_scalars_lincomb, ps_kzg_open_multi and
+ *      ps_kzg_verify_multi (no struct either). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -880,6 +881,41 @@ int ps_kzg_verify(const uint8_t tau_g2_1[192], const uint8_t commit[96], const u
  * points the caller made itself).  k = 0: *ok = 1.  k <= 2^24 (PS_ERR_ARG beyond).  Needs an empty MSM queue. */
 int ps_kzg_verify_batch(ps_ctx* ctx, const uint8_t tau_g2_1[192], const uint8_t* commits, const uint8_t* z_be32, const uint8_t* y_be32,
                         const uint8_t* proofs, const uint8_t* rho_be32, size_t k, int check_subgroup, int* ok);
+
+/* ---- Many polynomials at shared points: Poly.Add / Poly.Sub (algebra.go:161-196) on the device, and ONE proof per point ----
+ * *out: t rows of N = max_i len(v_i) scalars, row j = sum_i c_ij v_i with every v_i zero-extended to N -- member-major, the
+ * layout ps_msm_batch and the scan read; canonical plain words like any ps_scalars.  coef_be32: m * t canonical scalars, entry
+ * [i * t + j] (PS_ERR_ENCODING otherwise).  The inputs may be views (ps_scalars_slice) and may repeat.  A NULL argument or
+ * m = 0: PS_ERR_ARG; an empty input: PS_ERR_LENGTH; t = 0: *out is an empty vector.  Limits: t * N < 2^32 (what the scan reads)
+ * and m * t <= 2^20 (the coefficients go to the device as one table); PS_ERR_ARG beyond.  A zero coefficient costs no product.
+ * Caller frees *out. */
+int ps_scalars_lincomb(ps_ctx* ctx, const ps_scalars* const* v, size_t m, const uint8_t* coef_be32 /* m * t, entry [i * t + j] */,
+                       size_t t, ps_scalars** out);
+/* m polynomials opened at t points with ONE proof per point.  c_ij != 0 means "polynomial i is opened at point j, with this
+ * weight":
+ *     y[i * t + j] = p_i(z_j) where c_ij != 0, 32 zero bytes elsewhere
+ *     proofs[j] = [q_j(tau)] G1,  f_j = sum_i c_ij p_i,  q_j = (f_j - f_j(z_j)) / (X - z_j)
+ * The weights are the caller's: powers of a Fiat-Shamir challenge, drawn AFTER the commitments and the values are fixed
+ * (weights known beforehand let errors in two values of one point cancel).  Division by (X - z) is linear, so the call costs
+ * t rows of ps_msm_batch whatever m is: values by the scan per polynomial, the rows f_j by ps_scalars_lincomb, their quotients
+ * by the scan, ONE ps_msm_batch over tau_g1[0 .. N-1), N = max_i len(p_i); nothing leaves the device.  Proof j is byte-identical
+ * to ps_msm over that view and row j of ps_poly_div_linear applied to row j of ps_scalars_lincomb; with m = 1 and c = 1 the
+ * call returns ps_kzg_open's bytes.  N = 1: the values are the constants and the proofs identities.  A column of c without a
+ * non-zero entry: PS_ERR_ARG (nothing would be opened at that point); tau_g1 shorter than N: PS_ERR_LENGTH; t = 0: PS_OK,
+ * nothing written; the limits of ps_scalars_lincomb.  Needs an empty MSM queue (PS_ERR_ARG otherwise). */
+int ps_kzg_open_multi(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* const* polys, size_t m, const uint8_t* z_be32 /* t */,
+                      size_t t, const uint8_t* coef_be32 /* m * t */, uint8_t* y_be32 /* m * t */, uint8_t* proofs /* t * 96 */);
+/* The check of what ps_kzg_open_multi made.  With w_i = sum_j rho_j c_ij and s = sum_j rho_j sum_i c_ij y_ij (on the host):
+ *     e(sum_i w_i C_i + sum_j rho_j z_j pi_j - s G1, G2) * e(-sum_j rho_j pi_j, tau_g2_1) == 1
+ * -- ps_kzg_verify_batch's equation with C'_j = sum_i c_ij C_i folded into the scalars: two sums over the uploaded [C | pi]
+ * array and one two-pair product.  y entries where c_ij = 0 are ignored (not even decoded).  rho: one weight per POINT, with the
+ * rules of ps_kzg_verify_batch (canonical, non-zero, drawn afterwards); the subgroup option, the encoding errors and the
+ * false-accept bound are that call's too.  A column of c without a non-zero entry: PS_ERR_ARG.  t = 0: *ok = 1.
+ * m + t <= 2^24 (PS_ERR_ARG beyond).  Needs an empty MSM queue.  With m = t and c the identity matrix this is
+ * ps_kzg_verify_batch. */
+int ps_kzg_verify_multi(ps_ctx* ctx, const uint8_t tau_g2_1[192], const uint8_t* commits /* m * 96 */, size_t m, const uint8_t* z_be32,
+                        size_t t, const uint8_t* coef_be32, const uint8_t* y_be32 /* m * t */, const uint8_t* proofs /* t * 96 */,
+                        const uint8_t* rho_be32 /* t */, int check_subgroup, int* ok);
 
 #ifdef __cplusplus
 }

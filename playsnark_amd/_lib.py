@@ -43,6 +43,7 @@ SYMBOLS = [
     "ps_msm_prediction_counts",
     "ps_phgr13_verify_batch_locate", "ps_phgr13_verify_batch_locate_info",
     "ps_poly_scan_tile", "ps_poly_eval", "ps_poly_div_linear", "ps_kzg_commit", "ps_kzg_open", "ps_kzg_verify", "ps_kzg_verify_batch",
+    "ps_scalars_lincomb", "ps_kzg_open_multi", "ps_kzg_verify_multi",
 ]
 
 
@@ -271,6 +272,11 @@ def _load():
         lib.ps_kzg_open.argtypes = [vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
         lib.ps_kzg_verify.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
         lib.ps_kzg_verify_batch.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, i, C.POINTER(C.c_int)]
+    if hasattr(lib, "ps_kzg_open_multi"):  # likewise: added after the KZG block, within revision 5
+        lib.ps_scalars_lincomb.argtypes = [vp, C.POINTER(vp), sz, C.c_char_p, sz, pp]
+        lib.ps_kzg_open_multi.argtypes = [vp, vp, C.POINTER(vp), sz, C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_char_p]
+        lib.ps_kzg_verify_multi.argtypes = [vp, C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, i,
+                                            C.POINTER(C.c_int)]
     return lib
 
 

@@ -283,6 +283,11 @@ def _be32(v: int) -> bytes:
     return int(v).to_bytes(32, "big")
 
 
+def _handles(polys):
+    """the ps_scalars* of several Polys as one C array"""
+    return (C.c_void_p * len(polys))(*[p._h.value for p in polys])
+
+
 class Poly:
     """type Poly []Element (algebra.go:89), device-resident (ps_scalars).  Also stands in for
     Vector = []Value (algebra.go:13) through from_values (Value.ToFieldElement, curve.go:17-19)."""
@@ -365,6 +370,31 @@ class Poly:
         rem = C.create_string_buffer(32 * max(k, 1))
         _check(lib.ps_poly_div_linear(self.ctx._h, self._h, _rho_bytes(zs), k, C.byref(h), rem))
         return Poly(self.ctx, h), [int.from_bytes(rem.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+
+    @staticmethod
+    def LinComb(polys: Sequence["Poly"], coef_matrix: Sequence[Sequence[int]]) -> "Poly":
+        """len(coef_matrix[0]) rows of N = max len(p) coefficients, row j = sum_i coef_matrix[i][j] * polys[i] with every
+        polynomial zero-extended to N, on the device (ps_scalars_lincomb).  One Poly of t * N coefficients, row after row -- the
+        layout msm_batch and DivLinear's quotients use; slice(j * N, N) is row j.  Polynomials may be views and may repeat."""
+        m = len(polys)
+        if m == 0 or len(coef_matrix) != m or any(len(row) != len(coef_matrix[0]) for row in coef_matrix):
+            raise LengthMismatch("Poly.LinComb: one row of coefficients per polynomial, all of one length")
+        t = len(coef_matrix[0])
+        ctx = polys[0].ctx
+        hs = _handles(polys)
+        h = C.c_void_p()
+        _check(lib.ps_scalars_lincomb(ctx._h, hs, m, _rho_bytes([c for row in coef_matrix for c in row]), t, C.byref(h)))
+        return Poly(ctx, h)
+
+    def Add(self, p2: "Poly") -> "Poly":
+        """func (p Poly) Add(p2 Poly) Poly (algebra.go:161-178) on the device.  The result has the length of the longer operand:
+        it is NOT normalised (the reference strips leading zeros, algebra.go:230) -- finding the degree would need a pass over the
+        result and a copy back, and every consumer here (sums, scans) takes zeros as they are.  Compare after normalising."""
+        return Poly.LinComb([self, p2], [[1], [1]])
+
+    def Sub(self, p2: "Poly") -> "Poly":
+        """func (p Poly) Sub(p2 Poly) Poly (algebra.go:180-197) on the device; the length of the longer operand, as for Add."""
+        return Poly.LinComb([self, p2], [[1], [R_ORDER - 1]])
 
     def free(self):
         if self._h:
@@ -803,6 +833,40 @@ def KZGOpen(tau_g1: Points, p: Poly, zs: Sequence[int]):
     proofs = C.create_string_buffer(96 * max(k, 1))
     _check(lib.ps_kzg_open(p.ctx._h, tau_g1._h, p._h, _rho_bytes(zs), k, ys, proofs))
     return ([int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], [proofs.raw[96 * j : 96 * j + 96] for j in range(k)])
+
+
+def KZGOpenMulti(tau_g1: Points, polys: Sequence[Poly], zs: Sequence[int], coef: Sequence[Sequence[int]]):
+    """(ys, proofs) for len(polys) polynomials at len(zs) points with ONE proof per point (ps_kzg_open_multi).  coef[i][j] != 0:
+    polynomial i is opened at point j with this weight -- powers of a challenge drawn AFTER commitments and values are fixed.
+    ys[i][j] = polys[i](zs[j]) there and None elsewhere; proofs[j] = [q_j(tau)] G1 for q_j = (f_j - f_j(z_j)) / (X - z_j),
+    f_j = sum_i coef[i][j] polys[i]."""
+    m, t = len(polys), len(zs)
+    if len(coef) != m or any(len(row) != t for row in coef):
+        raise LengthMismatch("KZGOpenMulti: coef is len(polys) rows of len(zs) weights")
+    if m == 0:
+        raise LengthMismatch("KZGOpenMulti: no polynomial")
+    hs = _handles(polys)
+    ys = C.create_string_buffer(32 * max(m * t, 1))
+    proofs = C.create_string_buffer(96 * max(t, 1))
+    _check(lib.ps_kzg_open_multi(polys[0].ctx._h, tau_g1._h, hs, m, _rho_bytes(zs), t, _rho_bytes([c for row in coef for c in row]), ys, proofs))
+    val = lambda e: int.from_bytes(ys.raw[32 * e : 32 * e + 32], "big")
+    return ([[val(i * t + j) if int(coef[i][j]) % R_ORDER else None for j in range(t)] for i in range(m)],
+            [proofs.raw[96 * j : 96 * j + 96] for j in range(t)])
+
+
+def KZGVerifyMulti(ctx: Context, tau_g2_1: bytes, commits: Sequence[bytes], zs: Sequence[int], coef: Sequence[Sequence[int]],
+                   ys: Sequence[Sequence[Optional[int]]], proofs: Sequence[bytes], rhos: Sequence[int], check_subgroup: bool = True) -> bool:
+    """What KZGOpenMulti made, in one weighted equation (ps_kzg_verify_multi): len(commits) commitments, len(zs) points, one
+    proof and one non-zero weight rho per point, drawn AFTER everything else is fixed.  ys[i][j] is read where coef[i][j] != 0
+    (None counts as 0 elsewhere)."""
+    m, t = len(commits), len(zs)
+    if not (len(proofs) == len(rhos) == t) or len(coef) != m or len(ys) != m or any(len(row) != t for row in coef) or any(len(row) != t for row in ys):
+        raise LengthMismatch("KZGVerifyMulti: coef and ys are len(commits) rows of len(zs) entries; one proof and one rho per point")
+    ok = C.c_int(0)
+    _check(lib.ps_kzg_verify_multi(ctx._h, bytes(tau_g2_1), b"".join(commits), m, _rho_bytes(zs), t, _rho_bytes([c for row in coef for c in row]),
+                                   _rho_bytes([y or 0 for row in ys for y in row]), b"".join(proofs), _rho_bytes(rhos), int(check_subgroup),
+                                   C.byref(ok)))
+    return bool(ok.value)
 
 
 def KZGVerify(tau_g2_1: bytes, commit: bytes, z: int, y: int, proof: bytes) -> bool:

@@ -24,6 +24,7 @@
 #include "msm_batch_multi_plan.hpp"
 #include "quotient.hpp"
 #include "poly_scan.hpp"
+#include "fr_lincomb.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"

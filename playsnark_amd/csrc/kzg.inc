@@ -25,8 +25,12 @@ static void words_to_be32(uint8_t* be, const u32* w) {
 
 // The three launches for k points over p (n >= 1 coefficients): y_be32[j] = p(z_j); q_words != nullptr (n >= 2): row j of
 // q_words = the n - 1 quotient coefficients by (X - z_j).  Returns with the stream idle.
-static int poly_scan_run(ps_ctx* c, const char* who, const ps_scalars* p, const std::vector<FrPow2Table>& tabs, u32* q_words, uint8_t* y_be32) {
-    const u64 n = p->n, k = tabs.size();
+// row_len != 0: p holds k rows of row_len coefficients and point j meets ROW j -- the same kernels, launched once per row with a
+// grid of one point, every pointer moved to the row's own (3 k launches; k is small where sums of milliseconds follow).
+static int poly_scan_run(ps_ctx* c, const char* who, const ps_scalars* p, const std::vector<FrPow2Table>& tabs, u32* q_words, uint8_t* y_be32,
+                         u64 row_len = 0) {
+    const u64 n = row_len ? row_len : p->n, k = tabs.size();
+    const u64 per_launch = row_len ? 1 : POLY_SCAN_MAX_POINTS_PER_LAUNCH;
     const u32 tiles = (u32)poly_scan_tiles(n);
     hipStream_t st = c->stream;
     Scope scope(st);
@@ -40,9 +44,9 @@ static int poly_scan_run(ps_ctx* c, const char* who, const ps_scalars* p, const 
     if (storage_wait_ready(p->st, st)) return fail(PS_ERR_HIP, std::string(who) + ": event wait failed");
     if ((e = hipMemcpyAsync(d_tabs, tabs.data(), sizeof(FrPow2Table) * k, hipMemcpyHostToDevice, st)) != hipSuccess)
         return fail(PS_ERR_HIP, std::string(who) + ": copy of the power tables: " + hipGetErrorString(e));
-    const u32* coef = scalars_ptr(p);
-    for (u64 j0 = 0; j0 < k; j0 += POLY_SCAN_MAX_POINTS_PER_LAUNCH) {  // blockIdx.y picks the point
-        const u32 kb = (u32)std::min<u64>(k - j0, POLY_SCAN_MAX_POINTS_PER_LAUNCH);
+    for (u64 j0 = 0; j0 < k; j0 += per_launch) {  // blockIdx.y picks the point
+        const u32 kb = (u32)std::min<u64>(k - j0, per_launch);
+        const u32* coef = scalars_ptr(p) + 8 * j0 * row_len;
         Fr* tot = totals + j0 * tiles;
         Fr* car = carries + j0 * tiles;
         hipLaunchKernelGGL(k_poly_scan_tile<false>, dim3(tiles, kb), dim3(POLY_SCAN_THREADS), 0, st, coef, n, tiles, (const FrPow2Table*)(d_tabs + j0), tot,
@@ -57,7 +61,7 @@ static int poly_scan_run(ps_ctx* c, const char* who, const ps_scalars* p, const 
     std::vector<u32> y(8 * k);
     if ((e = hipMemcpyAsync(y.data(), d_y, 32 * k, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
         return fail(PS_ERR_HIP, std::string(who) + ": run: " + hipGetErrorString(e));
-    for (u64 j = 0; j < k; j++) words_to_be32(y_be32 + 32 * j, y.data() + 8 * j);
+    for (u64 j = 0; y_be32 && j < k; j++) words_to_be32(y_be32 + 32 * j, y.data() + 8 * j);
     return scope.finish(PS_OK);
 }
 
@@ -194,6 +198,42 @@ extern "C" int ps_kzg_verify(const uint8_t* tau_g2_1, const uint8_t* commit, con
     return PS_OK;
 }
 
+// The core of the combined checks: with the points [C_0 .. C_{nc-1} | pi_0 .. pi_{np-1}] and the scalars sc = [a_0 .. a_{nc+np-1} | ..]
+// whose np entries from rho_at on are the weights rho_j,
+//     A = sum_i a_i pts_i - s G1,  B = sum_j rho_j pi_j:   *ok = (e(A, G2) e(-B, tau G2) == 1)
+// -- two sums over the uploaded points, one two-pair product.  The upload validates encodings and the curve equation.
+static int kzg_check_sums(ps_ctx* c, const std::string& who, const Affine<Fp2>& t2, const uint8_t* commits, size_t nc, const uint8_t* proofs, size_t np,
+                          const std::vector<uint8_t>& sc, size_t rho_at, const Fr& s, int check_subgroup, int* ok) {
+    int rc;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint8_t> raw(96 * (nc + np));
+    memcpy(raw.data(), commits, 96 * nc);
+    memcpy(raw.data() + 96 * nc, proofs, 96 * np);
+    Scope scope;
+    ps_points **all = scope.points(), **pis = scope.points();
+    ps_scalars **w = scope.scalars(), **a = scope.scalars(), **rho = scope.scalars();
+    if ((rc = ps_points_upload(c, PS_G1, raw.data(), nc + np, PS_FMT_AFFINE, all))) return rc;
+    if (check_subgroup) {
+        int in = 0;
+        if (!all_in_subgroup({}, {&t2})) return PS_OK;
+        if ((rc = ps_points_check_subgroup(c, *all, &in)) || !in) return rc;
+    }
+    if ((rc = ps_scalars_upload(c, sc.data(), sc.size() / 32, w)) || (rc = ps_points_slice(*all, nc, np, pis)) ||
+        (rc = ps_scalars_slice(*w, 0, nc + np, a)) || (rc = ps_scalars_slice(*w, rho_at, np, rho)))
+        return rc;
+    uint8_t two[2 * 96], coef[2 * 32], a_bytes[96], b_bytes[96];
+    if ((rc = ps_msm(c, *all, *a, two)) || (rc = ps_msm(c, *pis, *rho, b_bytes))) return rc;
+    generator_bytes<Fp>(two + 96);
+    memset(coef, 0, 32);
+    coef[31] = 1;
+    fr_mont_to_be32(coef + 32, fr_neg(s));
+    if ((rc = ps_points_lincomb(PS_G1, two, coef, 2, a_bytes))) return rc;
+    Affine<Fp> pa, pb;
+    if (!read_g1(pa, a_bytes) || !read_g1(pb, b_bytes)) return fail(PS_ERR_ENCODING, who + ": internal: a sum does not decode");
+    *ok = product_is_one({{pa, generator((const Fp2*)0)}, {pairing_dev::neg_g1(pb), t2}}) ? 1 : 0;
+    return PS_OK;
+}
+
 extern "C" int ps_kzg_verify_batch(ps_ctx* c, const uint8_t* tau_g2_1, const uint8_t* commits, const uint8_t* z_be32, const uint8_t* y_be32,
                                    const uint8_t* proofs, const uint8_t* rho_be32, size_t k, int check_subgroup, int* ok) {
     const std::string who = "ps_kzg_verify_batch";
@@ -219,31 +259,175 @@ extern "C" int ps_kzg_verify_batch(ps_ctx* c, const uint8_t* tau_g2_1, const uin
         s = fr_reduce(fr_add(s, fr_mul(rho, y)));
     }
     if (k == 0) { *ok = 1; return PS_OK; }
-    HIP_TRY(hipSetDevice(c->device));
-    // the points [C_0 .. C_{k-1} | pi_0 .. pi_{k-1}]: the upload validates encodings and the curve equation
-    std::vector<uint8_t> raw(2 * 96 * k);
-    memcpy(raw.data(), commits, 96 * k);
-    memcpy(raw.data() + 96 * k, proofs, 96 * k);
-    Scope scope;
-    ps_points **all = scope.points(), **pis = scope.points();
-    ps_scalars **w = scope.scalars(), **rho = scope.scalars();
-    if ((rc = ps_points_upload(c, PS_G1, raw.data(), 2 * k, PS_FMT_AFFINE, all))) return rc;
-    if (check_subgroup) {
-        int in = 0;
-        if (!all_in_subgroup({}, {&t2})) return PS_OK;
-        if ((rc = ps_points_check_subgroup(c, *all, &in)) || !in) return rc;
-    }
-    if ((rc = ps_scalars_upload(c, sc.data(), 2 * k, w)) || (rc = ps_points_slice(*all, k, k, pis)) || (rc = ps_scalars_slice(*w, 0, k, rho))) return rc;
     // A = sum_j rho_j (C_j + z_j pi_j) - s G1,  B = sum_j rho_j pi_j:   e(A, G2) e(-B, tau G2) == 1
-    uint8_t two[2 * 96], coef[2 * 32], a_bytes[96], b_bytes[96];
-    if ((rc = ps_msm(c, *all, *w, two)) || (rc = ps_msm(c, *pis, *rho, b_bytes))) return rc;
-    generator_bytes<Fp>(two + 96);
-    memset(coef, 0, 32);
-    coef[31] = 1;
-    fr_mont_to_be32(coef + 32, fr_neg(s));
-    if ((rc = ps_points_lincomb(PS_G1, two, coef, 2, a_bytes))) return rc;
-    Affine<Fp> a, b;
-    if (!read_g1(a, a_bytes) || !read_g1(b, b_bytes)) return fail(PS_ERR_ENCODING, who + ": internal: a sum does not decode");
-    *ok = product_is_one({{a, generator((const Fp2*)0)}, {pairing_dev::neg_g1(b), t2}}) ? 1 : 0;
+    return kzg_check_sums(c, who, t2, commits, k, proofs, k, sc, 0, s, check_subgroup, ok);
+}
+
+// ---- many polynomials at shared points: one proof per point ----
+
+// An m x t matrix of canonical coefficients (PS_ERR_ENCODING otherwise) as the table k_fr_lincomb reads
+static int lincomb_coefs(const std::string& who, const uint8_t* coef_be32, size_t m, size_t t, std::vector<FrLincombCoef>* out) {
+    out->assign(m * t, FrLincombCoef());
+    for (size_t e = 0; e < m * t; e++) {
+        Fr v;
+        if (!fr_mont_from_canonical_be32(&v, coef_be32 + 32 * e))
+            return fail(PS_ERR_ENCODING, who + ": coefficient [" + std::to_string(e / t) + "][" + std::to_string(e % t) + "] is not below r");
+        const Fr cv = fr_canon(v);
+        u32 any = 0;
+        for (int k = 0; k < FR_L; k++) { (*out)[e].l[k] = cv.l[k]; any |= (u32)cv.l[k]; }
+        (*out)[e].nonzero = any ? 1 : 0;
+    }
     return PS_OK;
+}
+
+// the checks on the inputs of a combination; *N = the longest
+static int lincomb_inputs(const std::string& who, const ps_scalars* const* v, size_t m, u64* N) {
+    if (!v || m == 0) return fail(PS_ERR_ARG, who + (v ? ": no input" : ": NULL argument"));
+    *N = 0;
+    for (size_t l = 0; l < m; l++) {
+        if (!v[l]) return fail(PS_ERR_ARG, who + ": input " + std::to_string(l) + " is NULL");
+        if (v[l]->n == 0) return fail(PS_ERR_LENGTH, who + ": input " + std::to_string(l) + " is empty");
+        *N = std::max<u64>(*N, v[l]->n);
+    }
+    return PS_OK;
+}
+static int lincomb_size(const std::string& who, u64 m, u64 t, u64 N) {
+    if (fr_lincomb_size_ok(m, t, N)) return PS_OK;
+    return fail(PS_ERR_ARG, who + ": " + std::to_string(t) + " rows x " + std::to_string(N) + " scalars reach 2^32, or " + std::to_string(m) + " x " +
+                                std::to_string(t) + " coefficients exceed 2^20 (split the rows)");
+}
+
+extern "C" int ps_scalars_lincomb(ps_ctx* c, const ps_scalars* const* v, size_t m, const uint8_t* coef_be32, size_t t, ps_scalars** out) {
+    const std::string who = "ps_scalars_lincomb";
+    if (!c || !out) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *out = nullptr;
+    u64 N;
+    int rc = lincomb_inputs(who, v, m, &N);
+    if (rc) return rc;
+    if (t && !coef_be32) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if ((rc = lincomb_size(who, m, t, N))) return rc;
+    std::vector<FrLincombCoef> coefs;
+    if ((rc = lincomb_coefs(who, coef_be32, m, t, &coefs))) return rc;
+    std::vector<FrLincombInput> ins(m);
+    for (size_t l = 0; l < m; l++) ins[l] = FrLincombInput{scalars_ptr(v[l]), v[l]->n};
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    Scope scope(st);
+    if ((rc = scalars_fresh(c, who.c_str(), (u64)t * N, scope.result(out)))) return rc;
+    if (t == 0) return scope.finish(PS_OK);  // an empty vector
+    FrLincombInput* d_in = nullptr;
+    FrLincombCoef* d_coef = nullptr;
+    hipError_t e;
+    if ((e = scope.device(&d_in, m)) != hipSuccess || (e = scope.device(&d_coef, m * t)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+    for (size_t l = 0; l < m; l++)
+        if (storage_wait_ready(v[l]->st, st)) return fail(PS_ERR_HIP, who + ": event wait failed");
+    if ((e = hipMemcpyAsync(d_in, ins.data(), sizeof(FrLincombInput) * m, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_coef, coefs.data(), sizeof(FrLincombCoef) * m * t, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": copy of the tables: " + hipGetErrorString(e));
+    const u64 groups = fr_lincomb_groups(t);
+    for (u64 k = 0; k < fr_lincomb_launches(groups); k++)  // blockIdx.y picks the group of rows
+        hipLaunchKernelGGL(k_fr_lincomb, dim3((u32)fr_lincomb_blocks(N), (u32)fr_lincomb_launch_groups(groups, k)), dim3(FR_LINCOMB_THREADS), 0, st,
+                           (const FrLincombInput*)d_in, (u32)m, (const FrLincombCoef*)d_coef, (u32)t, (u32)(k * FR_LINCOMB_MAX_GROUPS_PER_LAUNCH), N,
+                           (u32*)(*out)->st->p);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": run: " + hipGetErrorString(e));
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_kzg_open_multi(ps_ctx* c, const ps_points* tau_g1, const ps_scalars* const* polys, size_t m, const uint8_t* z_be32, size_t t,
+                                 const uint8_t* coef_be32, uint8_t* y_be32, uint8_t* proofs) {
+    const std::string who = "ps_kzg_open_multi";
+    if (!c || !tau_g1) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (tau_g1->group != PS_G1) return fail(PS_ERR_ARG, who + ": tau_g1 is a G1 array");
+    u64 N;
+    int rc = lincomb_inputs(who, polys, m, &N);
+    if (rc) return rc;
+    if (tau_g1->n < N)
+        return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(N) + " and the " + std::to_string(tau_g1->n) + " powers of the string");
+    if (c->q_len) return fail(PS_ERR_ARG, who + ": sums are pending on this context (ps_msm_finish them first)");
+    if (t == 0) return PS_OK;
+    if (!z_be32 || !coef_be32 || !y_be32 || !proofs) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if ((rc = lincomb_size(who, m, t, N))) return rc;
+    std::vector<FrLincombCoef> coefs;
+    std::vector<FrPow2Table> tabs, mine;
+    if ((rc = lincomb_coefs(who, coef_be32, m, t, &coefs)) || (rc = poly_scan_tables(who.c_str(), z_be32, t, &tabs))) return rc;
+    for (size_t j = 0; j < t; j++) {
+        bool any = false;
+        for (size_t i = 0; i < m && !any; i++) any = coefs[i * t + j].nonzero != 0;
+        if (!any) return fail(PS_ERR_ARG, who + ": no polynomial is opened at z[" + std::to_string(j) + "] (its column of coefficients is zero)");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // 1. values: one evaluation per polynomial, over the points of its non-zero entries
+    memset(y_be32, 0, 32 * m * t);
+    std::vector<size_t> at;
+    std::vector<uint8_t> ys;
+    for (size_t i = 0; i < m; i++) {
+        at.clear();
+        mine.clear();
+        for (size_t j = 0; j < t; j++)
+            if (coefs[i * t + j].nonzero) { at.push_back(j); mine.push_back(tabs[j]); }
+        if (at.empty()) continue;
+        ys.resize(32 * at.size());
+        if ((rc = poly_scan_run(c, who.c_str(), polys[i], mine, nullptr, ys.data()))) return rc;
+        for (size_t a = 0; a < at.size(); a++) memcpy(y_be32 + 32 * (i * t + at[a]), ys.data() + 32 * a, 32);
+    }
+    if (N == 1) {  // constants: every quotient is zero
+        for (size_t j = 0; j < t; j++) write_identity(PS_G1, proofs + 96 * j);
+        return PS_OK;
+    }
+    // 2. the rows f_j, 3. their quotients by (X - z_j), 4. ONE batched sum of the t quotient rows; nothing leaves the device
+    Scope scope(c->stream);
+    ps_scalars **f = scope.scalars(), **q = scope.scalars();
+    ps_points** head = scope.points();
+    if ((rc = ps_scalars_lincomb(c, polys, m, coef_be32, t, f))) return rc;
+    if ((rc = scalars_fresh(c, who.c_str(), (u64)t * (N - 1), q))) return rc;
+    if ((rc = poly_scan_run(c, who.c_str(), *f, tabs, (u32*)(*q)->st->p, nullptr, N))) return rc;
+    if ((rc = ps_points_slice(tau_g1, 0, N - 1, head))) return rc;
+    return scope.finish(ps_msm_batch(c, *head, *q, t, proofs));
+}
+
+extern "C" int ps_kzg_verify_multi(ps_ctx* c, const uint8_t* tau_g2_1, const uint8_t* commits, size_t m, const uint8_t* z_be32, size_t t,
+                                   const uint8_t* coef_be32, const uint8_t* y_be32, const uint8_t* proofs, const uint8_t* rho_be32, int check_subgroup,
+                                   int* ok) {
+    const std::string who = "ps_kzg_verify_multi";
+    if (!c || !tau_g2_1 || !ok || (t && (!commits || !z_be32 || !coef_be32 || !y_be32 || !proofs || !rho_be32))) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *ok = 0;
+    if (m > PS_VERIFY_BATCH_MAX || t > PS_VERIFY_BATCH_MAX || m + t > PS_VERIFY_BATCH_MAX)
+        return fail(PS_ERR_ARG, who + ": more than 2^24 commitments and points (split the points: the verdicts of the parts AND together)");
+    if (c->q_len) return fail(PS_ERR_ARG, who + ": sums are pending on this context (ps_msm_finish them first)");
+    Affine<Fp2> t2;
+    if (!read_g2(t2, tau_g2_1)) return fail(PS_ERR_ENCODING, who + ": tau_g2_1 is not a canonical point on the curve");
+    u32 rho_sum[8];
+    int rc = batch_weights(who, rho_be32, t, rho_sum);
+    if (rc) return rc;
+    if (t == 0) { *ok = 1; return PS_OK; }
+    // the scalars [w_i | rho_j z_j | rho_j] with w_i = sum_j rho_j c_ij, and s = sum_j rho_j sum_i c_ij y_ij, on the host
+    std::vector<uint8_t> sc(32 * (m + 2 * t));
+    std::vector<Fr> w(m, fr_zero());
+    Fr s = fr_zero();
+    for (size_t j = 0; j < t; j++) {
+        Fr z;
+        if (!fr_mont_from_canonical_be32(&z, z_be32 + 32 * j)) return fail(PS_ERR_ENCODING, who + ": z[" + std::to_string(j) + "] is not below r");
+        const Fr rho = fr_mont_from_be32(rho_be32 + 32 * j);
+        fr_mont_to_be32(sc.data() + 32 * (m + j), fr_mul(rho, z));
+        memcpy(sc.data() + 32 * (m + t + j), rho_be32 + 32 * j, 32);
+        Fr col = fr_zero();  // sum_i c_ij y_ij
+        bool any = false;
+        for (size_t i = 0; i < m; i++) {
+            const std::string at = "[" + std::to_string(i) + "][" + std::to_string(j) + "]";
+            Fr cv, y;
+            if (!fr_mont_from_canonical_be32(&cv, coef_be32 + 32 * (i * t + j))) return fail(PS_ERR_ENCODING, who + ": coefficient " + at + " is not below r");
+            if (fr_is_zero(cv)) continue;  // nothing is opened here: y is not read
+            any = true;
+            if (!fr_mont_from_canonical_be32(&y, y_be32 + 32 * (i * t + j))) return fail(PS_ERR_ENCODING, who + ": y" + at + " is not below r");
+            w[i] = fr_reduce(fr_add(w[i], fr_mul(rho, cv)));
+            col = fr_reduce(fr_add(col, fr_mul(cv, y)));
+        }
+        if (!any) return fail(PS_ERR_ARG, who + ": no polynomial is opened at z[" + std::to_string(j) + "] (its column of coefficients is zero)");
+        s = fr_reduce(fr_add(s, fr_mul(rho, col)));
+    }
+    for (size_t i = 0; i < m; i++) fr_mont_to_be32(sc.data() + 32 * i, w[i]);
+    // A = sum_i w_i C_i + sum_j rho_j z_j pi_j - s G1,  B = sum_j rho_j pi_j:   e(A, G2) e(-B, tau G2) == 1
+    return kzg_check_sums(c, who, t2, commits, m, proofs, t, sc, m + t, s, check_subgroup, ok);
 }

@@ -131,6 +131,16 @@ class Poly {
         if (!out.empty()) check(ps_scalars_download(ctx_->get(), h_, 0, out.size(), out[0].data()));
         return out;
     }
+    // t rows of N = max size() coefficients, row j = sum_i coef[i * t + j] polys[i] (ps_scalars_lincomb); Poly.Add / Poly.Sub
+    // (algebra.go:161-196) are the coefficients (1, 1) and (1, r - 1).  The result is not normalised.
+    static Poly LinComb(Context& c, const std::vector<const Poly*>& polys, const std::vector<Scalar>& coef, size_t t) {
+        if (polys.empty() || coef.size() != polys.size() * t) throw LengthMismatch("Poly::LinComb: polys.size() * t coefficients");
+        std::vector<const ps_scalars*> hs;
+        for (auto* p : polys) hs.push_back(p->get());
+        ps_scalars* h = nullptr;
+        check(ps_scalars_lincomb(c.get(), hs.data(), hs.size(), coef.empty() ? nullptr : coef[0].data(), t, &h));
+        return Poly(c, h);
+    }
 
   private:
     friend class QAP;
@@ -486,6 +496,42 @@ inline std::vector<std::vector<Bytes>> SolCommitsBatch(Context& c, const std::ve
         for (size_t j = 0; j < k; j++) out[i].emplace_back(flat[i].begin() + wb * j, flat[i].begin() + wb * (j + 1));
     }
     return out;
+}
+// polys.size() polynomials opened at zs.size() points with ONE proof per point (ps_kzg_open_multi): coef[i * t + j] != 0 means
+// "polynomial i is opened at point j, with this weight" (powers of a challenge drawn after commitments and values are fixed).
+// ys[i * t + j] = p_i(z_j) there, zero elsewhere; proofs[j]: 96 bytes
+struct KZGMultiOpening {
+    std::vector<Scalar> ys;
+    std::vector<Bytes> proofs;
+};
+inline KZGMultiOpening KZGOpenMulti(Context& c, const Points& tau_g1, const std::vector<const Poly*>& polys, const std::vector<Scalar>& zs,
+                                    const std::vector<Scalar>& coef) {
+    const size_t m = polys.size(), t = zs.size();
+    if (m == 0 || coef.size() != m * t) throw LengthMismatch("KZGOpenMulti: polys.size() * zs.size() coefficients");
+    std::vector<const ps_scalars*> hs;
+    for (auto* p : polys) hs.push_back(p->get());
+    KZGMultiOpening out;
+    out.ys.resize(m * t);
+    std::vector<uint8_t> flat(96 * t + 1);
+    check(ps_kzg_open_multi(c.get(), tau_g1.get(), hs.data(), m, t ? zs[0].data() : nullptr, t, t ? coef[0].data() : nullptr,
+                            t ? out.ys[0].data() : nullptr, flat.data()));
+    for (size_t j = 0; j < t; j++) out.proofs.emplace_back(flat.begin() + 96 * j, flat.begin() + 96 * (j + 1));
+    return out;
+}
+// the check of such an opening in one weighted equation (ps_kzg_verify_multi): commits m x 96 bytes, one non-zero rho per point
+// drawn after everything else is fixed
+inline bool KZGVerifyMulti(Context& c, const uint8_t tau_g2_1[192], const Bytes& commits, const std::vector<Scalar>& zs,
+                           const std::vector<Scalar>& coef, const KZGMultiOpening& opening, const std::vector<Scalar>& rhos,
+                           bool check_subgroup = true) {
+    const size_t m = commits.size() / 96, t = zs.size();
+    if (coef.size() != m * t || opening.ys.size() != m * t || opening.proofs.size() != t || rhos.size() != t)
+        throw LengthMismatch("KZGVerifyMulti: m x t coefficients and values, one proof and one rho per point");
+    Bytes proofs;
+    for (auto& p : opening.proofs) proofs.insert(proofs.end(), p.begin(), p.end());
+    int ok = 0;
+    check(ps_kzg_verify_multi(c.get(), tau_g2_1, commits.data(), m, t ? zs[0].data() : nullptr, t, t ? coef[0].data() : nullptr,
+                              t ? opening.ys[0].data() : nullptr, proofs.data(), t ? rhos[0].data() : nullptr, check_subgroup ? 1 : 0, &ok));
+    return ok != 0;
 }
 // members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic
 inline void SetBatchChunk(Context& c, int members) { check(ps_msm_batch_set_chunk(c.get(), members)); }

@@ -1046,6 +1046,103 @@ func KZGVerifyBatch(srs *HipGroth16SRS, commits []Commit, zs, ys []Element, proo
 	return ok != 0
 }
 
+// LinCombHIP returns the len(coef[0]) rows sum_i coef[i][j] * polys[i], every polynomial zero-extended to the longest
+// (ps_scalars_lincomb).  `func (p Poly) Add` / `Sub` (algebra.go:161-196) are the columns (1, 1) and (1, -1); the rows are not
+// normalised.
+func LinCombHIP(polys []Poly, coef [][]Element) []Poly {
+	m := len(polys)
+	if m == 0 || len(coef) != m {
+		panic(fmt.Sprintf("LinCombHIP: %d polynomials, %d rows of coefficients", m, len(coef)))
+	}
+	t := len(coef[0])
+	hs := make([]*C.ps_scalars, m)
+	flat := make(Poly, 0, m*t)
+	n := 0
+	for i, p := range polys {
+		hs[i] = uploadPoly(p)
+		defer C.ps_scalars_free(hs[i])
+		flat = append(flat, coef[i]...)
+		if len(p) > n {
+			n = len(p)
+		}
+	}
+	var out *C.ps_scalars
+	call(func() C.int {
+		return C.ps_scalars_lincomb(hipCtx, (**C.ps_scalars)(unsafe.Pointer(&hs[0])), C.size_t(m), u8(marshalScalars(flat)), C.size_t(t), &out)
+	})
+	defer C.ps_scalars_free(out)
+	all := downloadPoly(out)
+	rows := make([]Poly, t)
+	for j := range rows {
+		rows[j] = all[j*n : (j+1)*n]
+	}
+	return rows
+}
+
+// KZGOpenMulti opens len(polys) polynomials at len(zs) points with ONE proof per point (ps_kzg_open_multi).  coef[i][j] != 0
+// means "polynomial i is opened at point j, with this weight": powers of a Fiat-Shamir challenge drawn after the commitments
+// and the values are fixed.  ys[i][j] = polys[i](zs[j]) where coef[i][j] != 0 and zero elsewhere.
+func KZGOpenMulti(srs *HipGroth16SRS, polys []Poly, zs []Element, coef [][]Element) ([][]Element, []Commit) {
+	m, t := len(polys), len(zs)
+	if m == 0 || len(coef) != m {
+		panic(fmt.Sprintf("KZGOpenMulti: %d polynomials, %d rows of coefficients", m, len(coef)))
+	}
+	hs := make([]*C.ps_scalars, m)
+	flat := make(Poly, 0, m*t)
+	for i, p := range polys {
+		hs[i] = uploadPoly(p)
+		defer C.ps_scalars_free(hs[i])
+		flat = append(flat, coef[i]...)
+	}
+	ys := make([]byte, 32*m*t)
+	raw := make([]byte, g1Wire*t)
+	call(func() C.int {
+		return C.ps_kzg_open_multi(hipCtx, srs.s.tau_g1, (**C.ps_scalars)(unsafe.Pointer(&hs[0])), C.size_t(m), u8(marshalScalars(Poly(zs))),
+			C.size_t(t), u8(marshalScalars(flat)), u8(ys), u8(raw))
+	})
+	vals := elementsFrom(ys)
+	rows := make([][]Element, m)
+	for i := range rows {
+		rows[i] = vals[i*t : (i+1)*t]
+	}
+	proofs := make([]Commit, t)
+	for j := range proofs {
+		proofs[j] = pointFrom(C.PS_G1, raw[g1Wire*j:g1Wire*(j+1)], zeroG1)
+	}
+	return rows, proofs
+}
+
+// KZGVerifyMulti checks what KZGOpenMulti made in one weighted equation (ps_kzg_verify_multi).  The weights of the points are
+// drawn here, after everything else is in hand.
+func KZGVerifyMulti(srs *HipGroth16SRS, commits []Commit, zs []Element, coef, ys [][]Element, proofs []Commit, checkSubgroup bool) bool {
+	m, t := len(commits), len(zs)
+	if len(coef) != m || len(ys) != m || len(proofs) != t {
+		panic(fmt.Sprintf("KZGVerifyMulti: %d commitments, %d points, %d rows of weights, %d of values, %d proofs", m, t, len(coef), len(ys), len(proofs)))
+	}
+	t2 := tauG2(srs)
+	cs, ps := make([]byte, 0, g1Wire*m), make([]byte, 0, g1Wire*t)
+	cf, yf := make(Poly, 0, m*t), make(Poly, 0, m*t)
+	for i := 0; i < m; i++ {
+		cs = append(cs, affineOf(C.PS_G1, commits[i])...)
+		cf = append(cf, coef[i]...)
+		yf = append(yf, ys[i]...)
+	}
+	for j := 0; j < t; j++ {
+		ps = append(ps, affineOf(C.PS_G1, proofs[j])...)
+	}
+	rho := drawWeights(t)
+	sub := C.int(0)
+	if checkSubgroup {
+		sub = 1
+	}
+	var ok C.int
+	call(func() C.int {
+		return C.ps_kzg_verify_multi(hipCtx, u8(t2), u8(cs), C.size_t(m), u8(marshalScalars(Poly(zs))), C.size_t(t), u8(marshalScalars(cf)),
+			u8(marshalScalars(yf)), u8(ps), u8(rho), sub, &ok)
+	})
+	return ok != 0
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
