@@ -62,7 +62,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      then ps_msm_prediction_counts; then ps_phgr13_verify_batch_locate and ps_phgr13_verify_batch_locate_info (with the
  *      new ps_phgr13_locate_info).  Then ps_poly_scan_tile, ps_poly_eval, ps_poly_div_linear, ps_kzg_commit, ps_kzg_open,
  *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all).  Then ps_scalars_lincomb, ps_kzg_open_multi and
- *      ps_kzg_verify_multi (no struct either). */
+ *      ps_kzg_verify_multi (no struct either).  Then ps_poly_scan_set_group, ps_poly_div_roots, ps_kzg_open_set and
+ *      ps_kzg_verify_set (no struct either). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -916,6 +917,42 @@ int ps_kzg_open_multi(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* co
 int ps_kzg_verify_multi(ps_ctx* ctx, const uint8_t tau_g2_1[192], const uint8_t* commits /* m * 96 */, size_t m, const uint8_t* z_be32,
                         size_t t, const uint8_t* coef_be32, const uint8_t* y_be32 /* m * t */, const uint8_t* proofs /* t * 96 */,
                         const uint8_t* rho_be32 /* t */, int check_subgroup, int* ok);
+
+/* ---- One polynomial at a SET of points: Poly.Div (algebra.go:119-137) by Z_S = prod_j (X - z_j), and ONE proof for the set ----
+ * S = {z_0 .. z_{k-1}}, k distinct canonical points; r = the interpolant of (z_j, p(z_j)), degree < k; q = (p - r) / Z_S, the
+ * n - k quotient coefficients.  By partial fractions, with w_j = 1 / prod_{l != j} (z_j - z_l),
+ *     q = sum_j w_j (p - p(z_j)) / (X - z_j)
+ * -- the rows of the linear scan, folded into ONE row while they are scanned: totals and carry walk of
+ * ps_poly_div_linear for the k points, then an apply pass in which a workgroup owns a tile and a group of
+ * ps_poly_scan_set_group() points.  Device memory beside the result: ceil(k / G) partial rows of n - k scalars (none for k <= G),
+ * where k rows of n - 1 would be needed to compose the same from ps_poly_div_linear and ps_scalars_lincomb.
+ * Shared conventions: z and y are 32-byte big-endian and canonical (PS_ERR_ENCODING otherwise); two equal points are PS_ERR_ARG
+ * (the message names both indices: the weights do not exist -- the k single-point openings take repeated points); k = 0 is
+ * PS_ERR_ARG (division by the constant 1 is a copy and is not offered); k > 1024 (the host work is quadratic in k) or
+ * k * n >= 2^32 is PS_ERR_ARG; a NULL argument is PS_ERR_ARG; an empty p is PS_ERR_LENGTH.  p may be a view.
+ * ps_poly_scan_set_group: G, the points a workgroup folds (tests sit on its edges; a constant of the build). */
+int ps_poly_scan_set_group(void);
+/* *q: the n - k coefficients of q, lowest degree first; an empty vector for n <= k.  y[j] = p(z_j) (k * 32 bytes).  rem, unless
+ * NULL: the k coefficients of the remainder r, lowest first (k * 32 bytes) -- interpolated on the host from the y_j, O(k^2); for
+ * n <= k it is p zero-extended.  Poly.Div with the divisor Z_S of the reference's highest-first order.  Caller frees *q. */
+int ps_poly_div_roots(ps_ctx* ctx, const ps_scalars* p, const uint8_t* z_be32, size_t k, ps_scalars** q, uint8_t* y_be32 /* k */,
+                      uint8_t* rem_be32 /* k coefficients, lowest first; may be NULL */);
+/* y[j] = p(z_j) and proof = [q(tau)] G1 for the whole set: the scan above, then ONE ps_msm (the lone sum, not a row of
+ * ps_msm_batch) over tau_g1[0 .. n-k); nothing but values and proof leaves the device.  The proof is byte-identical to ps_msm
+ * over that view and ps_poly_div_roots' quotient, equals sum_j w_j proofs_j of ps_kzg_open, and for k = 1 is ps_kzg_open's.
+ * n <= k: the proof is the identity and the values are ps_poly_eval's.  The string must hold at least n points (the commitment
+ * being opened needs them; PS_ERR_LENGTH, BlindEval's wording, algebra.go:350-352).  Needs an empty MSM queue (PS_ERR_ARG). */
+int ps_kzg_open_set(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* p, const uint8_t* z_be32, size_t k, uint8_t* y_be32 /* k */,
+                    uint8_t proof[96]);
+/* *ok = 1 iff  e(commit - [r(tau)] G1, G2) * e(-proof, [Z_S(tau)] G2) == 1.
+ * On the host: the coefficients of r (interpolation of the (z_j, y_j)) and of Z_S, both O(k^2).  On the device: [r(tau)] G1 as
+ * ps_msm over tau_g1[0 .. k) and [Z_S(tau)] G2 as ps_msm over tau_g2[0 .. k].  Then commit - R by ps_points_lincomb and one
+ * two-pair product on the host.  tau_g1 holds at least k points and tau_g2 at least k + 1 (PS_ERR_LENGTH otherwise); they are the
+ * caller's own arrays and are not tested here (ps_groth16_srs_check does that).  Encodings and the curve equation of commit and
+ * proof are always tested (PS_ERR_ENCODING); check_subgroup != 0: both are tested for the subgroup as ps_kzg_verify tests them,
+ * and a point outside gives *ok = 0.  For k = 1 the equation is ps_kzg_verify's.  Needs an empty MSM queue. */
+int ps_kzg_verify_set(ps_ctx* ctx, const ps_points* tau_g1 /* >= k */, const ps_points* tau_g2 /* >= k + 1 */, const uint8_t commit[96],
+                      const uint8_t* z_be32, const uint8_t* y_be32, size_t k, const uint8_t proof[96], int check_subgroup, int* ok);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,7 @@ SYMBOLS = [
     "ps_phgr13_verify_batch_locate", "ps_phgr13_verify_batch_locate_info",
     "ps_poly_scan_tile", "ps_poly_eval", "ps_poly_div_linear", "ps_kzg_commit", "ps_kzg_open", "ps_kzg_verify", "ps_kzg_verify_batch",
     "ps_scalars_lincomb", "ps_kzg_open_multi", "ps_kzg_verify_multi",
+    "ps_poly_scan_set_group", "ps_poly_div_roots", "ps_kzg_open_set", "ps_kzg_verify_set",
 ]
 
 
@@ -277,6 +278,11 @@ def _load():
         lib.ps_kzg_open_multi.argtypes = [vp, vp, C.POINTER(vp), sz, C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_char_p]
         lib.ps_kzg_verify_multi.argtypes = [vp, C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, i,
                                             C.POINTER(C.c_int)]
+    if hasattr(lib, "ps_kzg_open_set"):  # likewise: one polynomial at a set of points, within revision 5
+        lib.ps_poly_scan_set_group.argtypes = []
+        lib.ps_poly_div_roots.argtypes = [vp, vp, C.c_char_p, sz, pp, C.c_char_p, C.c_char_p]
+        lib.ps_kzg_open_set.argtypes = [vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
+        lib.ps_kzg_verify_set.argtypes = [vp, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, sz, C.c_char_p, i, C.POINTER(C.c_int)]
     return lib
 
 

@@ -371,6 +371,19 @@ class Poly:
         _check(lib.ps_poly_div_linear(self.ctx._h, self._h, _rho_bytes(zs), k, C.byref(h), rem))
         return Poly(self.ctx, h), [int.from_bytes(rem.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
 
+    def DivRoots(self, zs: Sequence[int], remainder: bool = True):
+        """func (p Poly) Div(p2 Poly) (algebra.go:119-137) by Z_S = prod (X - z), z in zs, len(zs) >= 1 distinct points
+        (ps_poly_div_roots).  Returns (q, ys, rem): q a Poly of len(p) - len(zs) coefficients, lowest degree first (empty for
+        len(p) <= len(zs)); ys[j] = p(zs[j]); rem the len(zs) coefficients of the remainder, lowest first -- the interpolant of
+        (zs[j], ys[j]), made on the host in O(len(zs)^2); None with remainder=False, which skips that work."""
+        k = len(zs)
+        h = C.c_void_p()
+        ys = C.create_string_buffer(32 * max(k, 1))
+        rem = C.create_string_buffer(32 * max(k, 1)) if remainder else None
+        _check(lib.ps_poly_div_roots(self.ctx._h, self._h, _rho_bytes(zs), k, C.byref(h), ys, rem))
+        val = lambda buf: [int.from_bytes(buf.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+        return Poly(self.ctx, h), val(ys), (val(rem) if remainder else None)
+
     @staticmethod
     def LinComb(polys: Sequence["Poly"], coef_matrix: Sequence[Sequence[int]]) -> "Poly":
         """len(coef_matrix[0]) rows of N = max len(p) coefficients, row j = sum_i coef_matrix[i][j] * polys[i] with every
@@ -866,6 +879,30 @@ def KZGVerifyMulti(ctx: Context, tau_g2_1: bytes, commits: Sequence[bytes], zs: 
     _check(lib.ps_kzg_verify_multi(ctx._h, bytes(tau_g2_1), b"".join(commits), m, _rho_bytes(zs), t, _rho_bytes([c for row in coef for c in row]),
                                    _rho_bytes([y or 0 for row in ys for y in row]), b"".join(proofs), _rho_bytes(rhos), int(check_subgroup),
                                    C.byref(ok)))
+    return bool(ok.value)
+
+
+def KZGOpenSet(tau_g1: Points, p: Poly, zs: Sequence[int]):
+    """(ys, proof): ys[j] = p(zs[j]) and ONE proof [q(tau)] G1 for the whole set, q = (p - r) / prod (X - zs[j]) with r the
+    interpolant of the values (ps_kzg_open_set): the quotients by the single points folded into one row on the device, then
+    one lone sum over the string.  len(zs) >= 1 distinct points; the identity for len(p) <= len(zs)."""
+    k = len(zs)
+    ys = C.create_string_buffer(32 * max(k, 1))
+    proof = C.create_string_buffer(96)
+    _check(lib.ps_kzg_open_set(p.ctx._h, tau_g1._h, p._h, _rho_bytes(zs), k, ys, proof))
+    return [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], proof.raw
+
+
+def KZGVerifySet(ctx: Context, tau_g1: Points, tau_g2: Points, commit: bytes, zs: Sequence[int], ys: Sequence[int], proof: bytes,
+                 check_subgroup: bool = True) -> bool:
+    """e(C - [r(tau)] G1, G2) * e(-proof, [Z_S(tau)] G2) == 1 for what KZGOpenSet made (ps_kzg_verify_set): tau_g1 holds at least
+    len(zs) powers of the string and tau_g2 at least len(zs) + 1.  A point outside the subgroup gives False (with
+    check_subgroup), a malformed one raises."""
+    if len(zs) != len(ys):
+        raise LengthMismatch("KZGVerifySet: one value per point")
+    ok = C.c_int(0)
+    _check(lib.ps_kzg_verify_set(ctx._h, tau_g1._h, tau_g2._h, bytes(commit), _rho_bytes(zs), _rho_bytes(ys), len(zs), bytes(proof),
+                                 int(check_subgroup), C.byref(ok)))
     return bool(ok.value)
 
 

@@ -25,6 +25,7 @@
 #include "quotient.hpp"
 #include "poly_scan.hpp"
 #include "fr_lincomb.hpp"
+#include "poly_scan_set.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"

@@ -6,7 +6,12 @@
 //   ps_kzg_open             values and proofs [q_j(tau)] G1 of k points: the scan, then ONE ps_msm_batch of the k quotient rows
 //   ps_kzg_verify           e(C - y G1 + z pi, G2) == e(pi, tau G2), on the host (pairing.inc)
 //   ps_kzg_verify_batch     k openings under one string by random linear combination: two sums, one two-pair product
-// The only kernels are the three of poly_scan.hpp; everything else is made of existing entry points.
+//   ps_poly_div_roots       q = (p - r) / prod_j (X - z_j), the values, the remainder  <- Poly.Div  (algebra.go:119-137) by Z_S
+//   ps_kzg_open_set         values and ONE proof [q(tau)] G1 for a set of k points: the scan's totals and carries, the set apply
+//                           pass (poly_scan_set.hpp), then ONE lone ps_msm
+//   ps_kzg_verify_set       e(C - [r(tau)] G1, G2) e(-pi, [Z_S(tau)] G2) == 1: r and Z_S on the host, two short sums, one product
+// The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp) and k_poly_scan_set_apply (poly_scan_set.hpp);
+// everything else is made of existing entry points.
 
 // {z_j^(2^i)}, i < POLY_SCAN_POWERS, for k canonical points (PS_ERR_ENCODING otherwise)
 static int poly_scan_tables(const char* who, const uint8_t* z_be32, size_t k, std::vector<FrPow2Table>* tabs) {
@@ -430,4 +435,236 @@ extern "C" int ps_kzg_verify_multi(ps_ctx* c, const uint8_t* tau_g2_1, const uin
     for (size_t i = 0; i < m; i++) fr_mont_to_be32(sc.data() + 32 * i, w[i]);
     // A = sum_i w_i C_i + sum_j rho_j z_j pi_j - s G1,  B = sum_j rho_j pi_j:   e(A, G2) e(-B, tau G2) == 1
     return kzg_check_sums(c, who, t2, commits, m, proofs, t, sc, m + t, s, check_subgroup, ok);
+}
+
+// ---- one polynomial at a SET of points: one quotient, one proof ----
+
+// What the host derives from the k points of a set, all in Montgomery form:
+//   z[j], w[j] = 1 / prod_{l != j} (z_j - z_l)  (canonical limbs: the kernel's weights; k^2 products and ONE inversion, the
+//   denominators being inverted together), and with want_zs: zs = Z_S = prod_j (X - z_j), k + 1 coefficients lowest first
+//   (k^2 products more; the verifier and the remainder need it, the opening does not) -- hence PS_KZG_SET_MAX.
+struct KzgSet {
+    std::vector<Fr> z, w, zs;
+};
+static int kzg_set_prepare(const std::string& who, const uint8_t* z_be32, size_t k, bool want_zs, KzgSet* s) {
+    s->z.assign(k, fr_zero());
+    s->w.assign(k, fr_zero());
+    for (size_t j = 0; j < k; j++)
+        if (!fr_mont_from_canonical_be32(&s->z[j], z_be32 + 32 * j)) return fail(PS_ERR_ENCODING, who + ": z[" + std::to_string(j) + "] is not below r");
+    for (size_t j = 0; j < k; j++)
+        for (size_t l = 0; l < j; l++)
+            if (!memcmp(z_be32 + 32 * l, z_be32 + 32 * j, 32))
+                return fail(PS_ERR_ARG, who + ": z[" + std::to_string(l) + "] and z[" + std::to_string(j) +
+                                            "] are equal (a set has distinct points; the single-point openings take repeated ones)");
+    std::vector<Fr> d(k), pre(k);  // d_j = prod_{l != j} (z_j - z_l), non-zero: the points are distinct; pre_j = d_0 .. d_j
+    for (size_t j = 0; j < k; j++) {
+        d[j] = fr_one();
+        for (size_t l = 0; l < k; l++)
+            if (l != j) d[j] = fr_mul(d[j], fr_sub(s->z[j], s->z[l]));  // a difference of two products' values: class 1, |V| < 10r/8
+        pre[j] = j ? fr_mul(pre[j - 1], d[j]) : d[j];
+    }
+    Fr inv = fr_inv(pre[k - 1]);
+    for (size_t j = k; j-- > 0;) {
+        s->w[j] = fr_canon(j ? fr_mul(inv, pre[j - 1]) : inv);
+        inv = fr_mul(inv, d[j]);
+    }
+    if (!want_zs) return PS_OK;
+    s->zs.assign(k + 1, fr_zero());
+    s->zs[0] = fr_one();
+    for (size_t j = 0; j < k; j++)  // times (X - z_j), from the top down: new[i + 1] = old[i] - z_j old[i + 1], in two steps
+        for (size_t i = j + 1; i-- > 0;) {
+            s->zs[i + 1] = fr_reduce(fr_add(s->zs[i + 1], s->zs[i]));
+            s->zs[i] = fr_neg(fr_mul(s->zs[i], s->z[j]));
+        }
+    return PS_OK;
+}
+// The interpolant of (z_j, y_j): r = sum_j y_j w_j Z_S / (X - z_j), k coefficients lowest first, Montgomery form; s.zs is
+// there.  Two products per (j, i).  Lazy ranges: b_{i-1} = c_i + z_j b_i is a Horner step -- a coefficient in (-9r/8, 9r/8) plus a
+// product, limbs at class 2 at most, straight into the next product; the sums over j are fr_norm'ed after every addition and
+// reduced behind every 32nd, as the device accumulators are (|V| < 38 r between two reductions).
+static std::vector<Fr> kzg_set_interpolate(const KzgSet& s, const std::vector<Fr>& y) {
+    const size_t k = s.z.size();
+    std::vector<Fr> r(k, fr_zero()), b(k);
+    for (size_t j = 0; j < k; j++) {
+        b[k - 1] = s.zs[k];  // synthetic division of Z_S by (X - z_j)
+        for (size_t i = k - 1; i >= 1; i--) b[i - 1] = fr_add(s.zs[i], fr_mul(s.z[j], b[i]));
+        const Fr c = fr_mul(y[j], s.w[j]);
+        const bool reduce = poly_scan_set_reduce_after(j) || j + 1 == k;
+        for (size_t i = 0; i < k; i++) {
+            r[i] = fr_norm(fr_add(r[i], fr_mul(c, b[i])));
+            if (reduce) r[i] = fr_reduce(r[i]);
+        }
+    }
+    return r;
+}
+
+// Arguments shared by ps_poly_div_roots and ps_kzg_open_set
+static int kzg_set_args(const std::string& who, const ps_ctx* c, const ps_scalars* p, const uint8_t* z_be32, size_t k, const uint8_t* y_be32) {
+    if (!c || !p || !z_be32 || !y_be32) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (p->n == 0) return fail(PS_ERR_LENGTH, who + ": empty polynomial");
+    if (k == 0) return fail(PS_ERR_ARG, who + ": an empty set (division by the constant 1 is a copy and is not offered)");
+    if (!poly_scan_set_points_ok(k)) return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points, at most " + std::to_string(PS_KZG_SET_MAX) + " in a set");
+    if (!poly_scan_set_size_ok(p->n, k))
+        return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points x " + std::to_string(p->n) + " coefficients reach 2^32");
+    return PS_OK;
+}
+
+// *q = the n - k coefficients of (p - r) / Z_S and y_be32[j] = p(z_j), for n > k: totals, carries, the set apply pass into
+// ceil(k / G) partial rows, and their sum by k_fr_lincomb with unit weights where there is more than one.  *q is the caller's.
+static int kzg_set_quotient(ps_ctx* c, const std::string& who, const ps_scalars* p, const KzgSet& s, const std::vector<FrPow2Table>& tabs, uint8_t* y_be32,
+                            ps_scalars** q) {
+    const u64 n = p->n, k = tabs.size(), nq = poly_scan_set_quotient_len(n, k), groups = poly_scan_set_groups(k);
+    const u32 tiles = (u32)poly_scan_tiles(n);
+    hipStream_t st = c->stream;
+    Scope scope(st);
+    if (int rc = scalars_fresh(c, who.c_str(), nq, scope.result(q))) return rc;
+    FrPow2Table* d_tabs = nullptr;
+    Fr *totals = nullptr, *carries = nullptr, *d_w = nullptr;
+    u32 *d_y = nullptr, *partial = (u32*)(*q)->st->p;
+    hipError_t e;
+    if ((e = scope.device(&d_tabs, k)) != hipSuccess || (e = scope.device(&totals, poly_scan_total_elems(n, k))) != hipSuccess ||
+        (e = scope.device(&carries, poly_scan_total_elems(n, k))) != hipSuccess || (e = scope.device(&d_y, poly_scan_value_words(k))) != hipSuccess ||
+        (e = scope.device(&d_w, poly_scan_set_weight_elems(k))) != hipSuccess ||
+        (groups > 1 && (e = scope.device(&partial, poly_scan_set_partial_words(n, k))) != hipSuccess))
+        return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+    if (storage_wait_ready(p->st, st)) return fail(PS_ERR_HIP, who + ": event wait failed");
+    if ((e = hipMemcpyAsync(d_tabs, tabs.data(), sizeof(FrPow2Table) * k, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_w, s.w.data(), sizeof(Fr) * k, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": copy of the tables: " + hipGetErrorString(e));
+    const u32* coef = scalars_ptr(p);
+    hipLaunchKernelGGL(k_poly_scan_tile<false>, dim3(tiles, (u32)k), dim3(POLY_SCAN_THREADS), 0, st, coef, n, tiles, (const FrPow2Table*)d_tabs, totals,
+                       (const Fr*)nullptr, (u32*)nullptr);
+    hipLaunchKernelGGL(k_poly_scan_carries, dim3((u32)k), dim3(POLY_SCAN_THREADS), 0, st, (const Fr*)totals, carries, tiles, (const FrPow2Table*)d_tabs, d_y);
+    hipLaunchKernelGGL(k_poly_scan_set_apply, dim3(tiles, (u32)groups), dim3(POLY_SCAN_THREADS), 0, st, coef, n, tiles, (u32)k, nq,
+                       (const FrPow2Table*)d_tabs, (const Fr*)d_w, (const Fr*)carries, partial);
+    std::vector<FrLincombInput> ins(groups);
+    std::vector<FrLincombCoef> ones(groups);
+    if (groups > 1) {  // q = the sum of the partial rows: the rows as inputs of one combination with the weights 1
+        const Fr one = fr_canon(fr_one());
+        for (u64 g = 0; g < groups; g++) {
+            ins[g] = FrLincombInput{partial + poly_scan_set_partial_word(g, 0, nq), nq};
+            for (int i = 0; i < FR_L; i++) ones[g].l[i] = one.l[i];
+            ones[g].nonzero = 1;
+            ones[g].pad = 0;
+        }
+        FrLincombInput* d_in = nullptr;
+        FrLincombCoef* d_coef = nullptr;
+        if ((e = scope.device(&d_in, groups)) != hipSuccess || (e = scope.device(&d_coef, groups)) != hipSuccess)
+            return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+        if ((e = hipMemcpyAsync(d_in, ins.data(), sizeof(FrLincombInput) * groups, hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(d_coef, ones.data(), sizeof(FrLincombCoef) * groups, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(PS_ERR_HIP, who + ": copy of the tables: " + hipGetErrorString(e));
+        hipLaunchKernelGGL(k_fr_lincomb, dim3((u32)fr_lincomb_blocks(nq), 1), dim3(FR_LINCOMB_THREADS), 0, st, (const FrLincombInput*)d_in, (u32)groups,
+                           (const FrLincombCoef*)d_coef, 1u, 0u, nq, (u32*)(*q)->st->p);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, who + ": kernels: " + hipGetErrorString(e));
+    std::vector<u32> y(8 * k);
+    if ((e = hipMemcpyAsync(y.data(), d_y, 32 * k, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": run: " + hipGetErrorString(e));
+    for (u64 j = 0; j < k; j++) words_to_be32(y_be32 + 32 * j, y.data() + 8 * j);
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_poly_scan_set_group(void) { return POLY_SCAN_SET_GROUP; }
+
+extern "C" int ps_poly_div_roots(ps_ctx* c, const ps_scalars* p, const uint8_t* z_be32, size_t k, ps_scalars** q, uint8_t* y_be32, uint8_t* rem_be32) {
+    const std::string who = "ps_poly_div_roots";
+    if (!q) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *q = nullptr;
+    int rc = kzg_set_args(who, c, p, z_be32, k, y_be32);
+    if (rc) return rc;
+    KzgSet s;
+    std::vector<FrPow2Table> tabs;
+    if ((rc = kzg_set_prepare(who, z_be32, k, rem_be32 != nullptr && p->n > k, &s)) || (rc = poly_scan_tables(who.c_str(), z_be32, k, &tabs))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = p->n;
+    Scope scope(c->stream);
+    if (n <= k) {  // the quotient is empty and the remainder is p itself
+        if ((rc = scalars_fresh(c, who.c_str(), 0, scope.result(q))) || (rc = poly_scan_run(c, who.c_str(), p, tabs, nullptr, y_be32))) return rc;
+        if (rem_be32) {
+            memset(rem_be32, 0, 32 * k);
+            if ((rc = ps_scalars_download(c, p, 0, n, rem_be32))) return rc;
+        }
+        return scope.finish(PS_OK);
+    }
+    if ((rc = kzg_set_quotient(c, who, p, s, tabs, y_be32, scope.result(q)))) return rc;
+    if (rem_be32) {
+        std::vector<Fr> y(k);
+        for (size_t j = 0; j < k; j++) (void)fr_mont_from_canonical_be32(&y[j], y_be32 + 32 * j);
+        const std::vector<Fr> r = kzg_set_interpolate(s, y);
+        for (size_t i = 0; i < k; i++) fr_mont_to_be32(rem_be32 + 32 * i, r[i]);
+    }
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_kzg_open_set(ps_ctx* c, const ps_points* tau_g1, const ps_scalars* p, const uint8_t* z_be32, size_t k, uint8_t* y_be32, uint8_t* proof) {
+    const std::string who = "ps_kzg_open_set";
+    int rc = kzg_string_args(who.c_str(), c, tau_g1, p);
+    if (rc) return rc;
+    if ((rc = kzg_set_args(who, c, p, z_be32, k, y_be32))) return rc;
+    if (!proof) return fail(PS_ERR_ARG, who + ": NULL argument");
+    KzgSet s;
+    std::vector<FrPow2Table> tabs;
+    if ((rc = kzg_set_prepare(who, z_be32, k, false, &s)) || (rc = poly_scan_tables(who.c_str(), z_be32, k, &tabs))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = p->n;
+    if (n <= k) {  // p is its own interpolant: the quotient is zero
+        if ((rc = poly_scan_run(c, who.c_str(), p, tabs, nullptr, y_be32))) return rc;
+        write_identity(PS_G1, proof);
+        return PS_OK;
+    }
+    Scope scope(c->stream);
+    ps_scalars** q = scope.scalars();
+    ps_points** head = scope.points();
+    if ((rc = kzg_set_quotient(c, who, p, s, tabs, y_be32, q))) return rc;
+    if ((rc = ps_points_slice(tau_g1, 0, n - k, head))) return rc;
+    return scope.finish(ps_msm(c, *head, *q, proof));  // the lone sum; the quotient never leaves the device
+}
+
+extern "C" int ps_kzg_verify_set(ps_ctx* c, const ps_points* tau_g1, const ps_points* tau_g2, const uint8_t* commit, const uint8_t* z_be32,
+                                 const uint8_t* y_be32, size_t k, const uint8_t* proof, int check_subgroup, int* ok) {
+    const std::string who = "ps_kzg_verify_set";
+    if (!c || !tau_g1 || !tau_g2 || !commit || !z_be32 || !y_be32 || !proof || !ok) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *ok = 0;
+    if (tau_g1->group != PS_G1 || tau_g2->group != PS_G2) return fail(PS_ERR_ARG, who + ": tau_g1 is a G1 array and tau_g2 a G2 array");
+    if (k == 0) return fail(PS_ERR_ARG, who + ": an empty set");
+    if (!poly_scan_set_points_ok(k)) return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points, at most " + std::to_string(PS_KZG_SET_MAX) + " in a set");
+    if (tau_g1->n < k)  // BlindEval's panic (algebra.go:350-352)
+        return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(k) + " and the " + std::to_string(tau_g1->n) + " powers of the string");
+    if (tau_g2->n < k + 1)
+        return fail(PS_ERR_LENGTH, "mismatch of length between poly " + std::to_string(k + 1) + " and the " + std::to_string(tau_g2->n) + " powers of the string");
+    if (c->q_len) return fail(PS_ERR_ARG, who + ": sums are pending on this context (ps_msm_finish them first)");
+    KzgSet s;
+    int rc = kzg_set_prepare(who, z_be32, k, true, &s);
+    if (rc) return rc;
+    std::vector<Fr> y(k);
+    for (size_t j = 0; j < k; j++)
+        if (!fr_mont_from_canonical_be32(&y[j], y_be32 + 32 * j)) return fail(PS_ERR_ENCODING, who + ": y[" + std::to_string(j) + "] is not below r");
+    Affine<Fp> cm, pi, lhs;
+    Affine<Fp2> zs2;
+    if (!read_g1(cm, commit) || !read_g1(pi, proof)) return fail(PS_ERR_ENCODING, who + ": a point is not a canonical point on the curve");
+    if (check_subgroup && !all_in_subgroup({&cm, &pi}, {})) return PS_OK;
+    // the coefficients of r and of Z_S on the host; [r(tau)] G1 and [Z_S(tau)] G2 as two lone sums over the heads of the strings
+    const std::vector<Fr> r = kzg_set_interpolate(s, y);
+    std::vector<uint8_t> sc(32 * (2 * k + 1));
+    for (size_t i = 0; i < k; i++) fr_mont_to_be32(sc.data() + 32 * i, r[i]);
+    for (size_t i = 0; i <= k; i++) fr_mont_to_be32(sc.data() + 32 * (k + i), s.zs[i]);
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope;
+    ps_scalars **all = scope.scalars(), **rc_s = scope.scalars(), **zc_s = scope.scalars();
+    ps_points **h1 = scope.points(), **h2 = scope.points();
+    uint8_t two[2 * 96], coef[2 * 32], sum[96], z2[192];
+    if ((rc = ps_scalars_upload(c, sc.data(), 2 * k + 1, all)) || (rc = ps_scalars_slice(*all, 0, k, rc_s)) || (rc = ps_scalars_slice(*all, k, k + 1, zc_s)) ||
+        (rc = ps_points_slice(tau_g1, 0, k, h1)) || (rc = ps_points_slice(tau_g2, 0, k + 1, h2)) || (rc = ps_msm(c, *h1, *rc_s, two + 96)) ||
+        (rc = ps_msm(c, *h2, *zc_s, z2)))
+        return rc;
+    // C - R
+    memcpy(two, commit, 96);
+    memset(coef, 0, 32);
+    coef[31] = 1;
+    fr_mont_to_be32(coef + 32, fr_neg(fr_one()));
+    if ((rc = ps_points_lincomb(PS_G1, two, coef, 2, sum))) return rc;
+    if (!read_g1(lhs, sum) || !read_g2(zs2, z2)) return fail(PS_ERR_ENCODING, who + ": internal: a sum does not decode");
+    *ok = product_is_one({{lhs, generator((const Fp2*)0)}, {pairing_dev::neg_g1(pi), zs2}}) ? 1 : 0;
+    return scope.finish(PS_OK);
 }

@@ -141,6 +141,11 @@ class Poly {
         check(ps_scalars_lincomb(c.get(), hs.data(), hs.size(), coef.empty() ? nullptr : coef[0].data(), t, &h));
         return Poly(c, h);
     }
+    // func (p Poly) Div(p2 Poly) (algebra.go:119-137) by Z_S = prod (X - z), z in zs, at least one point and all distinct
+    // (ps_poly_div_roots): the size() - zs.size() quotient coefficients, lowest degree first (none for size() <= zs.size()), the
+    // values p(z), and the zs.size() coefficients of the remainder -- the interpolant of (z, p(z))
+    struct RootsDivision;
+    RootsDivision DivRoots(const std::vector<Scalar>& zs) const;
 
   private:
     friend class QAP;
@@ -148,6 +153,18 @@ class Poly {
     Context* ctx_;
     ps_scalars* h_ = nullptr;
 };
+
+struct Poly::RootsDivision {
+    Poly q;
+    std::vector<Scalar> ys, rem;
+};
+inline Poly::RootsDivision Poly::DivRoots(const std::vector<Scalar>& zs) const {
+    const size_t k = zs.size();
+    ps_scalars* h = nullptr;
+    std::vector<Scalar> ys(k), rem(k);
+    check(ps_poly_div_roots(ctx_->get(), h_, k ? zs[0].data() : nullptr, k, &h, k ? ys[0].data() : nullptr, k ? rem[0].data() : nullptr));
+    return RootsDivision{Poly(*ctx_, h), std::move(ys), std::move(rem)};
+}
 
 // type QAP (qap.go:10-27) in sparse evaluation form on the reference's domain {1..n}
 class QAP {
@@ -531,6 +548,32 @@ inline bool KZGVerifyMulti(Context& c, const uint8_t tau_g2_1[192], const Bytes&
     int ok = 0;
     check(ps_kzg_verify_multi(c.get(), tau_g2_1, commits.data(), m, t ? zs[0].data() : nullptr, t, t ? coef[0].data() : nullptr,
                               t ? opening.ys[0].data() : nullptr, proofs.data(), t ? rhos[0].data() : nullptr, check_subgroup ? 1 : 0, &ok));
+    return ok != 0;
+}
+// the values p(z), z in zs, and ONE proof [q(tau)] G1 for the whole set, q = (p - r) / prod (X - z) with r the interpolant of
+// the values (ps_kzg_open_set); at least one point, all distinct
+struct KZGSetOpening {
+    std::vector<Scalar> ys;
+    Bytes proof;
+};
+inline KZGSetOpening KZGOpenSet(Context& c, const Points& tau_g1, const Poly& p, const std::vector<Scalar>& zs) {
+    const size_t k = zs.size();
+    KZGSetOpening out;
+    out.ys.resize(k);
+    out.proof.resize(96);
+    check(ps_kzg_open_set(c.get(), tau_g1.get(), p.get(), k ? zs[0].data() : nullptr, k, k ? out.ys[0].data() : nullptr, out.proof.data()));
+    return out;
+}
+// e(C - [r(tau)] G1, G2) e(-proof, [Z_S(tau)] G2) == 1 (ps_kzg_verify_set): tau_g1 holds at least zs.size() powers of the string
+// and tau_g2 at least zs.size() + 1
+inline bool KZGVerifySet(Context& c, const Points& tau_g1, const Points& tau_g2, const Bytes& commit, const std::vector<Scalar>& zs,
+                         const KZGSetOpening& opening, bool check_subgroup = true) {
+    const size_t k = zs.size();
+    if (opening.ys.size() != k || commit.size() != 96 || opening.proof.size() != 96)
+        throw LengthMismatch("KZGVerifySet: one value per point, a commitment and a proof of 96 bytes");
+    int ok = 0;
+    check(ps_kzg_verify_set(c.get(), tau_g1.get(), tau_g2.get(), commit.data(), k ? zs[0].data() : nullptr, k ? opening.ys[0].data() : nullptr, k,
+                            opening.proof.data(), check_subgroup ? 1 : 0, &ok));
     return ok != 0;
 }
 // members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic

@@ -1143,6 +1143,60 @@ func KZGVerifyMulti(srs *HipGroth16SRS, commits []Commit, zs []Element, coef, ys
 	return ok != 0
 }
 
+// PolyScanSetGroup is the number of points one workgroup of the set apply pass folds (ps_poly_scan_set_group).
+func PolyScanSetGroup() int { return int(C.ps_poly_scan_set_group()) }
+
+// DivRootsHIP replaces `func (p Poly) Div(p2 Poly)` for the divisor Z_S = prod (X - z), z in zs, at least one and all distinct
+// (ps_poly_div_roots): the len(p) - len(zs) quotient coefficients, lowest degree first (none for len(p) <= len(zs)), the values
+// p(z), and the len(zs) coefficients of the remainder -- the interpolant of (z, p(z)).
+func (p Poly) DivRootsHIP(zs []Element) (Poly, []Element, Poly) {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	var q *C.ps_scalars
+	ys := make([]byte, 32*len(zs))
+	rem := make([]byte, 32*len(zs))
+	call(func() C.int {
+		return C.ps_poly_div_roots(hipCtx, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), &q, u8(ys), u8(rem))
+	})
+	defer C.ps_scalars_free(q)
+	quot := Poly{}
+	if len(p) > len(zs) {
+		quot = downloadPoly(q)
+	}
+	return quot, elementsFrom(ys), Poly(elementsFrom(rem))
+}
+
+// KZGOpenSet returns the values p(z), z in zs, and ONE proof [q(tau)] G1 for the whole set, q = (p - r) / prod (X - z) with r
+// the interpolant of the values (ps_kzg_open_set).  At least one point, all distinct.
+func KZGOpenSet(srs *HipGroth16SRS, p Poly, zs []Element) ([]Element, Commit) {
+	h := uploadPoly(p)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	raw := make([]byte, g1Wire)
+	call(func() C.int {
+		return C.ps_kzg_open_set(hipCtx, srs.s.tau_g1, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys), u8(raw))
+	})
+	return elementsFrom(ys), pointFrom(C.PS_G1, raw, zeroG1)
+}
+
+// KZGVerifySet checks what KZGOpenSet made: e(C - [r(tau)] G1, G2) e(-pi, [Z_S(tau)] G2) == 1 (ps_kzg_verify_set).  The string
+// holds at least len(zs) powers in G1 and len(zs) + 1 in G2.  checkSubgroup = false only for points this process made itself.
+func KZGVerifySet(srs *HipGroth16SRS, commit Commit, zs, ys []Element, proof Commit, checkSubgroup bool) bool {
+	if len(zs) != len(ys) {
+		panic(fmt.Sprintf("KZGVerifySet: %d points, %d values", len(zs), len(ys)))
+	}
+	sub := C.int(0)
+	if checkSubgroup {
+		sub = 1
+	}
+	var ok C.int
+	call(func() C.int {
+		return C.ps_kzg_verify_set(hipCtx, srs.s.tau_g1, srs.s.tau_g2, u8(affineOf(C.PS_G1, commit)), u8(marshalScalars(Poly(zs))),
+			u8(marshalScalars(Poly(ys))), C.size_t(len(zs)), u8(affineOf(C.PS_G1, proof)), sub, &ok)
+	})
+	return ok != 0
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
