@@ -63,7 +63,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      new ps_phgr13_locate_info).  Then ps_poly_scan_tile, ps_poly_eval, ps_poly_div_linear, ps_kzg_commit, ps_kzg_open,
  *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all).  Then ps_scalars_lincomb, ps_kzg_open_multi and
  *      ps_kzg_verify_multi (no struct either).  Then ps_poly_scan_set_group, ps_poly_div_roots, ps_kzg_open_set and
- *      ps_kzg_verify_set (no struct either). */
+ *      ps_kzg_verify_set (no struct either).  Then ps_poly_lagrange_tile, ps_qap_gate_values, ps_poly_eval_lagrange,
+ *      ps_poly_div_linear_lagrange, ps_kzg_commit_lagrange and ps_kzg_open_lagrange (no struct either). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -953,6 +954,39 @@ int ps_kzg_open_set(ps_ctx* ctx, const ps_points* tau_g1, const ps_scalars* p, c
  * and a point outside gives *ok = 0.  For k = 1 the equation is ps_kzg_verify's.  Needs an empty MSM queue. */
 int ps_kzg_verify_set(ps_ctx* ctx, const ps_points* tau_g1 /* >= k */, const ps_points* tau_g2 /* >= k + 1 */, const uint8_t commit[96],
                       const uint8_t* z_be32, const uint8_t* y_be32, size_t k, const uint8_t proof[96], int check_subgroup, int* ok);
+
+/* ---- Polynomials given by their VALUES on the domain 1 .. n (the Lagrange form): no interpolation, no division ----
+ * A polynomial of degree < n is the vector v of its values on the nodes 1 .. n of a ps_qap (n = its gate count; the ps_qap also
+ * supplies the factorial tables of the barycentric weights w_i = (-1)^(n-i) / ((i-1)! (n-i)!)).  With e_i = 1 / (z - i):
+ *     p(z) = prod_i (z - i) * sum_i w_i v_i e_i                      for z off the domain,  p(m) = v_m on it;
+ *     q = (p - p(z)) / (X - z) has the values q_i = (p(z) - v_i) e_i at the nodes i != z, and at a node z = m the value the
+ *     degree bound deg q <= n - 2 forces: q_m = (sum_{i != m} w_i v_i e_i - v_m sum_{i != m} w_i e_i) / w_m.
+ * The n inversions are ONE field inversion per workgroup and a few products per node.  lag_g1 is the
+ * Lagrange form of the string on the same nodes -- [l_i(tau)] G1, what ps_points_monomial_to_lagrange makes of tau_g1[0 .. n)
+ * and ps_points_lagrange_check tests -- so that sum_i q_i lag_g1[i] = [q(tau)] G1: commitments and proofs are the SAME group
+ * elements, hence the same 96 bytes, as ps_kzg_commit and ps_kzg_open give for the interpolated coefficients, and
+ * ps_kzg_verify / ps_kzg_verify_batch check them unchanged.
+ * Shared conventions: `values` and lag_g1 hold exactly n elements (PS_ERR_LENGTH otherwise); a G2 array, a NULL argument,
+ * k * n >= 2^32 or -- where a sum is taken -- a non-empty MSM queue are PS_ERR_ARG; z is 32-byte big-endian and canonical
+ * (PS_ERR_ENCODING otherwise); k = 0 is PS_OK with nothing written.  Points may repeat, and points on and off the domain may
+ * share a call.  n = 1 is no special case: y = v_1 and q = 0 for every z.
+ * ps_poly_lagrange_tile: the nodes a workgroup inverts together (tests sit on its edges; a constant of the build). */
+int ps_poly_lagrange_tile(void);
+/* *out = the n values of (L|R|O).sol on the domain -- what ps_qap_interpolate interpolates, uninterpolated.  which: 0 left,
+ * 1 right, 2 out; the argument rules are ps_qap_interpolate's.  Caller frees *out. */
+int ps_qap_gate_values(ps_ctx* ctx, const ps_qap* q, const ps_scalars* sol, int which, ps_scalars** out);
+/* y[j] = p(z_j), k * 32 bytes, for the polynomial with the given values: ps_poly_eval of the interpolated coefficients. */
+int ps_poly_eval_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, uint8_t* y_be32);
+/* *qv: k rows of n scalars, row after row (the layout ps_msm_batch reads): row j = the values on 1 .. n of
+ * (p - p(z_j)) / (X - z_j); y[j] = p(z_j).  k = 0: an empty vector.  Caller frees *qv. */
+int ps_poly_div_linear_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, ps_scalars** qv,
+                                uint8_t* y_be32 /* k */);
+/* out = sum_i v_i lag_g1[i] = [p(tau)] G1: ps_msm over arrays of one length (PS_ERR_LENGTH otherwise). */
+int ps_kzg_commit_lagrange(ps_ctx* ctx, const ps_points* lag_g1, const ps_scalars* values, uint8_t out[96]);
+/* y[j] = p(z_j) and proofs[j] = [q_j(tau)] G1 for k points: the quotient rows above, then the lone ps_msm for k = 1 and ONE
+ * ps_msm_batch of the k rows over lag_g1 otherwise; the rows never leave the device. */
+int ps_kzg_open_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32, size_t k,
+                         uint8_t* y_be32 /* k */, uint8_t* proofs /* k * 96 */);
 
 #ifdef __cplusplus
 }

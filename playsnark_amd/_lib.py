@@ -45,6 +45,8 @@ SYMBOLS = [
     "ps_poly_scan_tile", "ps_poly_eval", "ps_poly_div_linear", "ps_kzg_commit", "ps_kzg_open", "ps_kzg_verify", "ps_kzg_verify_batch",
     "ps_scalars_lincomb", "ps_kzg_open_multi", "ps_kzg_verify_multi",
     "ps_poly_scan_set_group", "ps_poly_div_roots", "ps_kzg_open_set", "ps_kzg_verify_set",
+    "ps_poly_lagrange_tile", "ps_qap_gate_values", "ps_poly_eval_lagrange", "ps_poly_div_linear_lagrange", "ps_kzg_commit_lagrange",
+    "ps_kzg_open_lagrange",
 ]
 
 
@@ -283,6 +285,13 @@ def _load():
         lib.ps_poly_div_roots.argtypes = [vp, vp, C.c_char_p, sz, pp, C.c_char_p, C.c_char_p]
         lib.ps_kzg_open_set.argtypes = [vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
         lib.ps_kzg_verify_set.argtypes = [vp, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, sz, C.c_char_p, i, C.POINTER(C.c_int)]
+    if hasattr(lib, "ps_kzg_open_lagrange"):  # likewise: polynomials given by their values on 1..n, within revision 5
+        lib.ps_poly_lagrange_tile.argtypes = []
+        lib.ps_qap_gate_values.argtypes = [vp, vp, vp, i, pp]
+        lib.ps_poly_eval_lagrange.argtypes = [vp, vp, vp, C.c_char_p, sz, C.c_char_p]
+        lib.ps_poly_div_linear_lagrange.argtypes = [vp, vp, vp, C.c_char_p, sz, pp, C.c_char_p]
+        lib.ps_kzg_commit_lagrange.argtypes = [vp, vp, vp, C.c_char_p]
+        lib.ps_kzg_open_lagrange.argtypes = [vp, vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
     return lib
 
 

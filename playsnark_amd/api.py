@@ -384,6 +384,24 @@ class Poly:
         val = lambda buf: [int.from_bytes(buf.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
         return Poly(self.ctx, h), val(ys), (val(rem) if remainder else None)
 
+    def EvalLagrange(self, qap: "QAP", zs: Sequence[int]) -> list:
+        """Eval for a polynomial held as its values on the domain 1..n of qap (self: the n values), with no interpolation
+        (ps_poly_eval_lagrange).  Points may lie on the domain."""
+        k = len(zs)
+        out = C.create_string_buffer(32 * max(k, 1))
+        _check(lib.ps_poly_eval_lagrange(self.ctx._h, qap._h, self._h, _rho_bytes(zs), k, out))
+        return [int.from_bytes(out.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+
+    def DivLinearLagrange(self, qap: "QAP", zs: Sequence[int]):
+        """DivLinear for a polynomial held as its values on the domain 1..n of qap (ps_poly_div_linear_lagrange).  Returns
+        (qv, ys): qv a Poly of len(zs) * n scalars, row j the VALUES on 1..n of (p - ys[j]) / (X - zs[j]) -- the layout
+        msm_batch reads -- and ys[j] = p(zs[j])."""
+        k = len(zs)
+        h = C.c_void_p()
+        ys = C.create_string_buffer(32 * max(k, 1))
+        _check(lib.ps_poly_div_linear_lagrange(self.ctx._h, qap._h, self._h, _rho_bytes(zs), k, C.byref(h), ys))
+        return Poly(self.ctx, h), [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+
     @staticmethod
     def LinComb(polys: Sequence["Poly"], coef_matrix: Sequence[Sequence[int]]) -> "Poly":
         """len(coef_matrix[0]) rows of N = max len(p) coefficients, row j = sum_i coef_matrix[i][j] * polys[i] with every
@@ -659,6 +677,13 @@ class QAP:
         _check(lib.ps_qap_interpolate(self.ctx._h, self._h, sol._h, which, C.byref(h)))
         return Poly(self.ctx, h)
 
+    def gate_values(self, sol: Poly, which: int) -> Poly:
+        """The n values on the domain 1..n that interpolate() interpolates -- (L|R|O).sol, uninterpolated (ps_qap_gate_values):
+        0 left, 1 right, 2 out.  What KZGCommitLagrange and KZGOpenLagrange take."""
+        h = C.c_void_p()
+        _check(lib.ps_qap_gate_values(self.ctx._h, self._h, sol._h, which, C.byref(h)))
+        return Poly(self.ctx, h)
+
     def computeAB(self, sol: Poly):
         """(left, right, h): the Groth16 route -- A and B as coefficient vectors, h = floor(A*B / z); C is never
         interpolated (what Groth16Prove needs, groth16.go:146-185)."""
@@ -845,6 +870,24 @@ def KZGOpen(tau_g1: Points, p: Poly, zs: Sequence[int]):
     ys = C.create_string_buffer(32 * max(k, 1))
     proofs = C.create_string_buffer(96 * max(k, 1))
     _check(lib.ps_kzg_open(p.ctx._h, tau_g1._h, p._h, _rho_bytes(zs), k, ys, proofs))
+    return ([int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], [proofs.raw[96 * j : 96 * j + 96] for j in range(k)])
+
+
+def KZGCommitLagrange(lag_g1: Points, values: Poly) -> bytes:
+    """[p(tau)] G1 = sum_i v_i lag_g1[i] for a polynomial held as its values on 1..n, over the Lagrange form of the string on
+    the same nodes (ps_kzg_commit_lagrange): KZGCommit's bytes for the interpolated coefficients.  Both arrays have n elements."""
+    out = C.create_string_buffer(96)
+    _check(lib.ps_kzg_commit_lagrange(values.ctx._h, lag_g1._h, values._h, out))
+    return out.raw
+
+
+def KZGOpenLagrange(qap: "QAP", lag_g1: Points, values: Poly, zs: Sequence[int]):
+    """(ys, proofs) as KZGOpen gives them for the interpolated coefficients, byte for byte, from the n values on the domain of qap
+    and the Lagrange form of the string (ps_kzg_open_lagrange): no interpolation and no division.  Points may lie on the domain."""
+    k = len(zs)
+    ys = C.create_string_buffer(32 * max(k, 1))
+    proofs = C.create_string_buffer(96 * max(k, 1))
+    _check(lib.ps_kzg_open_lagrange(values.ctx._h, qap._h, lag_g1._h, values._h, _rho_bytes(zs), k, ys, proofs))
     return ([int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], [proofs.raw[96 * j : 96 * j + 96] for j in range(k)])
 
 

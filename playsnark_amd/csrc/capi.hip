@@ -26,6 +26,7 @@
 #include "poly_scan.hpp"
 #include "fr_lincomb.hpp"
 #include "poly_scan_set.hpp"
+#include "poly_lagrange.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"

@@ -10,8 +10,15 @@
 //   ps_kzg_open_set         values and ONE proof [q(tau)] G1 for a set of k points: the scan's totals and carries, the set apply
 //                           pass (poly_scan_set.hpp), then ONE lone ps_msm
 //   ps_kzg_verify_set       e(C - [r(tau)] G1, G2) e(-pi, [Z_S(tau)] G2) == 1: r and Z_S on the host, two short sums, one product
-// The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp) and k_poly_scan_set_apply (poly_scan_set.hpp);
-// everything else is made of existing entry points.
+//   ps_poly_lagrange_tile        the tile of the value-form kernels, for tests that sit on its edges
+//   ps_qap_gate_values           the n values of (L|R|O).sol on the domain 1..n: ps_qap_interpolate without its interpolation
+//   ps_poly_eval_lagrange        y[j] = p(z_j) from the n VALUES of p on 1..n: one inversion per workgroup, no interpolation
+//   ps_poly_div_linear_lagrange  the values on 1..n of (p - p(z_j)) / (X - z_j), z_j on the domain or off it
+//   ps_kzg_commit_lagrange       sum_i v_i lag_g1[i]: ps_msm over the Lagrange-form string
+//   ps_kzg_open_lagrange         values and proofs of k points from the values: those rows, then the lone ps_msm (k = 1) or ONE
+//                                ps_msm_batch over lag_g1 -- ps_kzg_open's bytes for the interpolated coefficients
+// The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp), k_poly_scan_set_apply (poly_scan_set.hpp) and the
+// three of poly_lagrange.hpp; everything else is made of existing entry points.
 
 // {z_j^(2^i)}, i < POLY_SCAN_POWERS, for k canonical points (PS_ERR_ENCODING otherwise)
 static int poly_scan_tables(const char* who, const uint8_t* z_be32, size_t k, std::vector<FrPow2Table>* tabs) {
@@ -667,4 +674,164 @@ extern "C" int ps_kzg_verify_set(ps_ctx* c, const ps_points* tau_g1, const ps_po
     if (!read_g1(lhs, sum) || !read_g2(zs2, z2)) return fail(PS_ERR_ENCODING, who + ": internal: a sum does not decode");
     *ok = product_is_one({{lhs, generator((const Fp2*)0)}, {pairing_dev::neg_g1(pi), zs2}}) ? 1 : 0;
     return scope.finish(PS_OK);
+}
+
+// ---- polynomials given by their values on the nodes 1 .. n (the Lagrange form): no interpolation, no division ----
+
+// The k points as the kernels read them: z in Montgomery form and the node it is, if any (PS_ERR_ENCODING for a z not below r)
+static int lagr_points(const std::string& who, const uint8_t* z_be32, size_t k, u64 n, std::vector<LagrPoint>* pts) {
+    pts->assign(k, LagrPoint());
+    for (size_t j = 0; j < k; j++) {
+        u32 w[8];
+        if (!be32_to_words(w, z_be32 + 32 * j)) return fail(PS_ERR_ENCODING, who + ": z[" + std::to_string(j) + "] is not below r");
+        (*pts)[j].z = fr_to_mont(fr_from_words8(w));
+        (*pts)[j].hit = (u32)poly_lagr_hit(w, n);
+        (*pts)[j].pad = 0;
+    }
+    return PS_OK;
+}
+
+// Arguments shared by ps_poly_eval_lagrange, ps_poly_div_linear_lagrange and ps_kzg_open_lagrange; *skip: k == 0, nothing to do
+static int lagr_args(const std::string& who, const ps_ctx* c, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k,
+                     const uint8_t* y_be32, bool* skip) {
+    *skip = false;
+    if (!c || !q || !values) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (values->n != q->n)
+        return fail(PS_ERR_LENGTH, who + ": " + std::to_string(values->n) + " values on a domain of " + std::to_string(q->n) + " nodes");
+    if (k == 0) { *skip = true; return PS_OK; }
+    if (!z_be32 || !y_be32) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (!poly_lagr_total_ok(q->n, k))
+        return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points x " + std::to_string(q->n) + " values reach 2^32 (split the points)");
+    return PS_OK;
+}
+
+// The launches for k points over the n values: y_be32[j] = p(z_j); rows != nullptr: row j of rows (n scalars each) = the values
+// of (p - p(z_j)) / (X - z_j) on the nodes.  Returns with the stream idle.
+static int lagr_run(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_scalars* values, const std::vector<LagrPoint>& pts, u32* rows,
+                    uint8_t* y_be32) {
+    const u64 n = q->n, k = pts.size();
+    const u32 tiles = (u32)poly_lagr_tiles(n);
+    hipStream_t st = c->stream;
+    Scope scope(st);
+    LagrPoint* d_pts = nullptr;
+    Fr *parts = nullptr, *yq = nullptr;
+    u32* d_y = nullptr;
+    hipError_t e;
+    if ((e = scope.device(&d_pts, k)) != hipSuccess || (e = scope.device(&parts, poly_lagr_part_elems(n, k))) != hipSuccess ||
+        (e = scope.device(&yq, poly_lagr_yq_elems(k))) != hipSuccess || (e = scope.device(&d_y, poly_lagr_value_words(k))) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+    if (storage_wait_ready(values->st, st)) return fail(PS_ERR_HIP, who + ": event wait failed");
+    if ((e = hipMemcpyAsync(d_pts, pts.data(), sizeof(LagrPoint) * k, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": copy of the points: " + hipGetErrorString(e));
+    const u32* v = scalars_ptr(values);
+    const u64 plane = poly_lagr_plane_elems(n, k);
+    for (u64 j0 = 0; j0 < k; j0 += POLY_LAGR_MAX_POINTS_PER_LAUNCH) {  // blockIdx.y picks the point
+        const u32 kb = (u32)std::min<u64>(k - j0, POLY_LAGR_MAX_POINTS_PER_LAUNCH);
+        Fr* part = parts + j0 * tiles;  // the planes stay `plane` apart
+        u32* row = rows ? rows + 8 * j0 * n : nullptr;
+        if (rows)
+            hipLaunchKernelGGL(k_lagr_tile<true>, dim3(tiles, kb), dim3(POLY_LAGR_THREADS), 0, st, v, n, tiles, (const LagrPoint*)(d_pts + j0),
+                               (const Fr*)q->qt.invfact, part, plane, row);
+        else
+            hipLaunchKernelGGL(k_lagr_tile<false>, dim3(tiles, kb), dim3(POLY_LAGR_THREADS), 0, st, v, n, tiles, (const LagrPoint*)(d_pts + j0),
+                               (const Fr*)q->qt.invfact, part, plane, (u32*)nullptr);
+        hipLaunchKernelGGL(k_lagr_walk, dim3(kb), dim3(POLY_LAGR_THREADS), 0, st, (const Fr*)part, plane, tiles, (const LagrPoint*)(d_pts + j0), v, n,
+                           (const Fr*)q->qt.fact2, d_y + 8 * j0, yq + 2 * j0);
+        if (rows)
+            hipLaunchKernelGGL(k_lagr_apply, dim3((u32)poly_lagr_apply_blocks(n), kb), dim3(POLY_LAGR_THREADS), 0, st, v, n,
+                               (const LagrPoint*)(d_pts + j0), (const Fr*)(yq + 2 * j0), row);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, who + ": kernels: " + hipGetErrorString(e));
+    std::vector<u32> y(8 * k);
+    if ((e = hipMemcpyAsync(y.data(), d_y, 32 * k, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": run: " + hipGetErrorString(e));
+    for (u64 j = 0; j < k; j++) words_to_be32(y_be32 + 32 * j, y.data() + 8 * j);
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_poly_lagrange_tile(void) { return POLY_LAGR_TILE; }
+
+// The n values of (L|R|O).sol on the domain: ps_qap_interpolate without its interpolation
+extern "C" int ps_qap_gate_values(ps_ctx* c, const ps_qap* q, const ps_scalars* sol, int which, ps_scalars** out) {
+    if (!c || !q || !sol || !out) return fail(PS_ERR_ARG, "ps_qap_gate_values: NULL argument");
+    if (which < 0 || which > 2) return fail(PS_ERR_ARG, "ps_qap_gate_values: which must be 0 (left), 1 (right) or 2 (out)");
+    if (sol->n != q->m) return fail(PS_ERR_ARG, "different number of solution variables than left polynomials");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (storage_wait_ready(sol->st, st)) return fail(PS_ERR_HIP, "ps_qap_gate_values: event wait failed");
+    hipLaunchKernelGGL(k_fr_to_mont, dim3(nblk(q->m)), dim3(256), 0, st, q->sol_m, scalars_ptr(sol), (u64)q->m);
+    spmv_launch(st, q->mat[which], (const Fr*)q->sol_m, q->y[which], (u32)q->n);
+    int rc = scalars_from_mont(c, q->y[which], q->n, out);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return PS_OK;
+}
+
+extern "C" int ps_poly_eval_lagrange(ps_ctx* c, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, uint8_t* y_be32) {
+    const std::string who = "ps_poly_eval_lagrange";
+    bool skip;
+    int rc = lagr_args(who, c, q, values, z_be32, k, y_be32, &skip);
+    if (rc || skip) return rc;
+    std::vector<LagrPoint> pts;
+    if ((rc = lagr_points(who, z_be32, k, q->n, &pts))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return lagr_run(c, who, q, values, pts, nullptr, y_be32);
+}
+
+extern "C" int ps_poly_div_linear_lagrange(ps_ctx* c, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, ps_scalars** qv,
+                                           uint8_t* y_be32) {
+    const std::string who = "ps_poly_div_linear_lagrange";
+    if (!qv) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *qv = nullptr;
+    bool skip;
+    int rc = lagr_args(who, c, q, values, z_be32, k, y_be32, &skip);
+    if (rc) return rc;
+    std::vector<LagrPoint> pts;
+    if (!skip && (rc = lagr_points(who, z_be32, k, q->n, &pts))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
+    if ((rc = scalars_fresh(c, who.c_str(), (u64)k * q->n, scope.result(qv)))) return rc;  // k == 0: an empty vector
+    if (!skip && (rc = lagr_run(c, who, q, values, pts, (u32*)(*qv)->st->p, y_be32))) return rc;
+    return scope.finish(PS_OK);
+}
+
+// lag_g1 and values of one length, lag_g1 a G1 array, no sum pending
+static int lagr_string_args(const std::string& who, const ps_ctx* c, const ps_points* lag_g1, const ps_scalars* values, size_t n) {
+    if (!c || !lag_g1 || !values) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (lag_g1->group != PS_G1) return fail(PS_ERR_ARG, who + ": lag_g1 is a G1 array");
+    if (lag_g1->n != n || values->n != n)
+        return fail(PS_ERR_LENGTH, who + ": " + std::to_string(values->n) + " values and " + std::to_string(lag_g1->n) +
+                                       " points of the Lagrange-form string on a domain of " + std::to_string(n) + " nodes");
+    if (c->q_len) return fail(PS_ERR_ARG, who + ": sums are pending on this context (ps_msm_finish them first)");
+    return PS_OK;
+}
+
+extern "C" int ps_kzg_commit_lagrange(ps_ctx* c, const ps_points* lag_g1, const ps_scalars* values, uint8_t* out) {
+    const std::string who = "ps_kzg_commit_lagrange";
+    int rc = lagr_string_args(who, c, lag_g1, values, lag_g1 ? lag_g1->n : 0);
+    if (rc) return rc;
+    if (!out) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (values->n == 0) return fail(PS_ERR_LENGTH, who + ": no values");
+    return ps_msm(c, lag_g1, values, out);
+}
+
+extern "C" int ps_kzg_open_lagrange(ps_ctx* c, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32, size_t k,
+                                    uint8_t* y_be32, uint8_t* proofs) {
+    const std::string who = "ps_kzg_open_lagrange";
+    if (!q) return fail(PS_ERR_ARG, who + ": NULL argument");
+    int rc = lagr_string_args(who, c, lag_g1, values, q->n);
+    if (rc) return rc;
+    bool skip;
+    if ((rc = lagr_args(who, c, q, values, z_be32, k, y_be32, &skip)) || skip) return rc;
+    if (!proofs) return fail(PS_ERR_ARG, who + ": NULL argument");
+    std::vector<LagrPoint> pts;
+    if ((rc = lagr_points(who, z_be32, k, q->n, &pts))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
+    ps_scalars** rows = scope.scalars();
+    if ((rc = scalars_fresh(c, who.c_str(), (u64)k * q->n, rows))) return rc;
+    if ((rc = lagr_run(c, who, q, values, pts, (u32*)(*rows)->st->p, y_be32))) return rc;
+    // the quotient rows never leave the device: the lone sum for one point (measured ahead of a one-row batch), else ONE batch
+    if (k == 1) return scope.finish(ps_msm(c, lag_g1, *rows, proofs));
+    return scope.finish(ps_msm_batch(c, lag_g1, *rows, k, proofs));
 }

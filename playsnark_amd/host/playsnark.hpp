@@ -216,6 +216,33 @@ class QAP {
         check(ps_qap_column_sums(ctx_->get(), h_, which, points.get(), &h));
         return Points(*ctx_, h);
     }
+    // The n values of (L|R|O).sol on the domain 1..n, which = 0, 1, 2: what computeAggregatePoly (qap.go:164-175) interpolates,
+    // uninterpolated (ps_qap_gate_values) -- the form KZGCommitLagrange and KZGOpenLagrange take
+    Poly GateValues(const Poly& sol, int which) const {
+        ps_scalars* h = nullptr;
+        check(ps_qap_gate_values(ctx_->get(), h_, sol.get(), which, &h));
+        return Poly(*ctx_, h);
+    }
+    // p(z), z in zs, for the polynomial with the given n values on this domain, with no interpolation (ps_poly_eval_lagrange)
+    std::vector<Scalar> EvalLagrange(const Poly& values, const std::vector<Scalar>& zs) const {
+        const size_t k = zs.size();
+        std::vector<Scalar> ys(k);
+        check(ps_poly_eval_lagrange(ctx_->get(), h_, values.get(), k ? zs[0].data() : nullptr, k, k ? ys[0].data() : nullptr));
+        return ys;
+    }
+    // zs.size() rows of n scalars, row j = the VALUES on 1..n of (p - p(z_j)) / (X - z_j), and the values p(z_j)
+    // (ps_poly_div_linear_lagrange)
+    struct LagrangeDivision {
+        Poly rows;
+        std::vector<Scalar> ys;
+    };
+    LagrangeDivision DivLinearLagrange(const Poly& values, const std::vector<Scalar>& zs) const {
+        const size_t k = zs.size();
+        ps_scalars* h = nullptr;
+        std::vector<Scalar> ys(k);
+        check(ps_poly_div_linear_lagrange(ctx_->get(), h_, values.get(), k ? zs[0].data() : nullptr, k, &h, k ? ys[0].data() : nullptr));
+        return LagrangeDivision{Poly(*ctx_, h), std::move(ys)};
+    }
 
   private:
     Context* ctx_;
@@ -575,6 +602,29 @@ inline bool KZGVerifySet(Context& c, const Points& tau_g1, const Points& tau_g2,
     check(ps_kzg_verify_set(c.get(), tau_g1.get(), tau_g2.get(), commit.data(), k ? zs[0].data() : nullptr, k ? opening.ys[0].data() : nullptr, k,
                             opening.proof.data(), check_subgroup ? 1 : 0, &ok));
     return ok != 0;
+}
+// [p(tau)] G1 for a polynomial held as its n values on the domain, over the Lagrange form of the string on the same nodes
+// (ps_kzg_commit_lagrange): the bytes of Poly.Commit for the interpolated coefficients
+inline Bytes KZGCommitLagrange(Context& c, const Points& lag_g1, const Poly& values) {
+    Bytes out(96);
+    check(ps_kzg_commit_lagrange(c.get(), lag_g1.get(), values.get(), out.data()));
+    return out;
+}
+// the values p(z) and the proofs [q_z(tau)] G1, z in zs, from the n values and the Lagrange-form string (ps_kzg_open_lagrange):
+// no interpolation, no division; the bytes ps_kzg_open gives for the coefficients.  Points may lie on the domain.
+struct KZGLagrangeOpening {
+    std::vector<Scalar> ys;
+    std::vector<Bytes> proofs;
+};
+inline KZGLagrangeOpening KZGOpenLagrange(Context& c, const QAP& qap, const Points& lag_g1, const Poly& values, const std::vector<Scalar>& zs) {
+    const size_t k = zs.size();
+    KZGLagrangeOpening out;
+    out.ys.resize(k);
+    std::vector<uint8_t> flat(96 * k + 1);
+    check(ps_kzg_open_lagrange(c.get(), qap.get(), lag_g1.get(), values.get(), k ? zs[0].data() : nullptr, k, k ? out.ys[0].data() : nullptr,
+                               flat.data()));
+    for (size_t j = 0; j < k; j++) out.proofs.emplace_back(flat.begin() + 96 * j, flat.begin() + 96 * (j + 1));
+    return out;
 }
 // members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic
 inline void SetBatchChunk(Context& c, int members) { check(ps_msm_batch_set_chunk(c.get(), members)); }

@@ -1197,6 +1197,97 @@ func KZGVerifySet(srs *HipGroth16SRS, commit Commit, zs, ys []Element, proof Com
 	return ok != 0
 }
 
+// ---------------------------------------------------------------------------------------
+// KZG over polynomials held as their VALUES on the domain 1..n of a HipQAP (the Lagrange form): what a prover has -- the gate
+// vectors L.w, R.w, O.w, a column, a blob -- committed and opened with no interpolation and no division.  Commitments and proofs
+// are the group elements KZGCommit and KZGOpen give for the interpolated coefficients, so KZGVerify checks them unchanged.
+// ---------------------------------------------------------------------------------------
+
+// PolyLagrangeTile is the number of nodes one workgroup inverts together (ps_poly_lagrange_tile).
+func PolyLagrangeTile() int { return int(C.ps_poly_lagrange_tile()) }
+
+// GateValuesHIP returns the nbGates values of (L|R|O).sol on the domain, which = 0, 1, 2: what computeAggregatePoly
+// (qap.go:164-175) interpolates, uninterpolated (ps_qap_gate_values).
+func (q *HipQAP) GateValuesHIP(sol Vector, which int) Poly {
+	dsol := uploadSolution(sol)
+	defer C.ps_scalars_free(dsol)
+	var h *C.ps_scalars
+	call(func() C.int { return C.ps_qap_gate_values(hipCtx, q.h, dsol, C.int(which), &h) })
+	defer C.ps_scalars_free(h)
+	return downloadPoly(h)
+}
+
+// LagrangeStringHIP puts the first nbGates powers of the string's tau_g1 into Lagrange form on the domain
+// (ps_points_monomial_to_lagrange, once per string and domain): the array KZGCommitLagrange and KZGOpenLagrange sum over.
+// The caller frees it with ps_points_free.
+func (q *HipQAP) LagrangeStringHIP(srs *HipGroth16SRS) *C.ps_points {
+	var head, lag *C.ps_points
+	call(func() C.int { return C.ps_points_slice(srs.s.tau_g1, 0, C.size_t(q.nbGates), &head) })
+	defer C.ps_points_free(head)
+	call(func() C.int { return C.ps_points_monomial_to_lagrange(hipCtx, q.h, head, 0, &lag) })
+	return lag
+}
+
+// EvalLagrangeHIP is EvalHIP for a polynomial held as its nbGates values on the domain (ps_poly_eval_lagrange).  Points may lie
+// on the domain.
+func (q *HipQAP) EvalLagrangeHIP(values Poly, zs []Element) []Element {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	call(func() C.int {
+		return C.ps_poly_eval_lagrange(hipCtx, q.h, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys))
+	})
+	return elementsFrom(ys)
+}
+
+// DivLinearLagrangeHIP is DivLinearHIP in value form: row j holds the nbGates values on the domain of (p - p(z)) / (X - z),
+// z = zs[j], next to the values p(z) (ps_poly_div_linear_lagrange).
+func (q *HipQAP) DivLinearLagrangeHIP(values Poly, zs []Element) ([]Poly, []Element) {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	var qv *C.ps_scalars
+	ys := make([]byte, 32*len(zs))
+	call(func() C.int {
+		return C.ps_poly_div_linear_lagrange(hipCtx, q.h, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), &qv, u8(ys))
+	})
+	defer C.ps_scalars_free(qv)
+	rows := make([]Poly, len(zs))
+	if len(zs) > 0 {
+		all := downloadPoly(qv)
+		for j := range rows {
+			rows[j] = all[j*len(values) : (j+1)*len(values)]
+		}
+	}
+	return rows, elementsFrom(ys)
+}
+
+// KZGCommitLagrange returns [p(tau)] G1 for the polynomial with the given values, over the Lagrange-form string
+// (ps_kzg_commit_lagrange): the point KZGCommit gives for the interpolated coefficients.
+func KZGCommitLagrange(lagG1 *C.ps_points, values Poly) Commit {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	out := make([]byte, g1Wire)
+	call(func() C.int { return C.ps_kzg_commit_lagrange(hipCtx, lagG1, h, u8(out)) })
+	return pointFrom(C.PS_G1, out, zeroG1)
+}
+
+// KZGOpenLagrange returns p(z) and the opening proof [q_z(tau)] G1 for every z in zs from the values alone
+// (ps_kzg_open_lagrange): the points KZGOpen gives for the interpolated coefficients.
+func KZGOpenLagrange(q *HipQAP, lagG1 *C.ps_points, values Poly, zs []Element) ([]Element, []Commit) {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	raw := make([]byte, g1Wire*len(zs))
+	call(func() C.int {
+		return C.ps_kzg_open_lagrange(hipCtx, q.h, lagG1, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys), u8(raw))
+	})
+	proofs := make([]Commit, len(zs))
+	for j := range proofs {
+		proofs[j] = pointFrom(C.PS_G1, raw[g1Wire*j:g1Wire*(j+1)], zeroG1)
+	}
+	return elementsFrom(ys), proofs
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
