@@ -2170,6 +2170,7 @@ extern "C" int ps_debug_ntt_trace(unsigned long long* out, int* meta) {
 #include "pairing.inc"
 #include "pairing_dev.hpp"
 #include "locate_dev.hpp"
+#include "locate_descent.hpp"
 #include "verify_batch.inc"
 #include "verify_locate.inc"
 #include "locate_phgr13_dev.hpp"

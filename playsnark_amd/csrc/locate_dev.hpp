@@ -2,7 +2,8 @@
 // Included by capi.hip after pairing_dev.hpp; its PS_HD part alone (the index arithmetic and the modular addition of plain
 // words) by tests/host_locate_index.cpp, which runs it on the host under ASan + UBSan; tests/device_locate_check.hip
 // includes it whole and launches k_g1_pair_sums and k_fr_row_pair_sums directly (tests/test_device_locate.py: every node
-// of every level against Python integers and the oracle's point addition).
+// of every level against Python integers and the oracle's point addition).  The descent over these trees is locate_bisect
+// (locate_descent.hpp, on top of the PS_HD part), which the same host test runs as it ships.
 //
 // Every tree is laid out as the product tree of k_f12_product: level 0 holds one value per proof, level l + 1 has
 // ceil(n_l / 2) nodes, node i combines nodes 2i and 2i + 1 of the level below and the odd one out is carried up unchanged.
@@ -44,6 +45,9 @@ PS_HD inline void node_range(int l, u64 i, u64 n, u64* lo, u64* hi) {
 }
 // Node i of a level whose level BELOW has `below` nodes: two children (2i, 2i + 1), or the carried node 2i alone
 PS_HD inline bool node_has_two_children(u64 i, u64 below) { return 2 * i + 1 < below; }
+// First value of level l of an F tree whose level 0 is followed by `diff` more values (the loops with the key's points of a
+// PHGR13 batch, locate_phgr13_dev.hpp; 0 for Groth16: off[l])
+PS_HD inline u64 f_level_base(const u64* off, int l, u64 diff) { return off[l] + (l > 0 ? diff : 0); }
 
 // acc = acc + x mod r for plain canonical words (both below r < 2^255: the sum fits 256 bits)
 PS_HD inline void words8_add_mod_r(u32* acc, const u32* x) {

@@ -1,7 +1,7 @@
 // Device side of ps_phgr13_verify_batch_locate (verify_phgr13_locate.inc): what the bisection of a rejected PHGR13 batch
 // reads beyond the trees of locate_dev.hpp.  Included by capi.hip after locate_dev.hpp; its PS_HD part alone (which trees an
 // equation reads, where a node lies; PS_LOCATE_INDEX_ONLY) by tests/host_phgr13_locate_index.cpp, which runs it on the host
-// under ASan + UBSan;
+// under ASan + UBSan together with the descent itself, locate_bisect of locate_descent.hpp, which both locators share;
 // tests/device_phgr13_locate_check.hip includes it whole and launches k_g2_pair_sums and k_f12_segment_products directly
 // (tests/test_device_phgr13_locate.py: every node against the oracle's G2 addition, every product against Python integers).
 //
@@ -42,7 +42,7 @@ PS_HD inline int element_slots(u32 mask, int* slot) {
 // First node of segment `seg` of level l of `segs` trees kept level-major (size, off: locate::tree_levels)
 PS_HD inline u64 segment_node(const u64* size, const u64* off, int l, u64 segs, u64 seg) { return segs * off[l] + seg * size[l]; }
 // First value of level l of the F tree over N proofs whose level 0 is followed by the `diff` loops of the key
-PS_HD inline u64 f_level_base(const u64* off, int l, u64 diff) { return off[l] + (l > 0 ? diff : 0); }
+using locate::f_level_base;
 // The batch's product lies behind the levels and the key's loops, and behind it the levels of the product tree over the
 // key's loops (ceil(diff / 2) values, then half of that ..: fewer than diff + MAX_LEVELS in all)
 PS_HD inline u64 f_product_at(const u64* off, int levels, u64 diff) { return off[levels] + diff; }

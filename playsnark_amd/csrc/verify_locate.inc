@@ -7,15 +7,46 @@
 //   1. the batch check of ps_groth16_verify_batch (verify_batch_impl), the levels of its product tree kept: accepted ->
 //      done, one check, nothing else launched;
 //   2. otherwise the C tree and the scalar tree (locate_dev.hpp), built once;
-//   3. from the root down, both children of every failing node, all nodes of a level in one round: their values gathered
-//      on the device (one launch per array), X_S by k_ec_scale and segmented k_g1_pair_sums, one batch normalisation, one
-//      download; the three Miller loops with the key's G2 points and the final exponentiation of every set on at most 16
-//      host threads.  A node with one (carried) child hands its verdict down without a check.
+//   3. the descent: locate_bisect (locate_descent.hpp, shared with verify_phgr13_locate.inc, run as it ships by
+//      tests/host_locate_index.cpp) with a one-bit mask.  A round (locate_check_sets): the sets' values gathered on the device
+//      (one launch per array), X_S by k_ec_scale and segmented k_g1_pair_sums, one batch normalisation, one download; the
+//      three Miller loops with the key's G2 points and the final exponentiation of every set on at most 16 host threads.
 // No step after the batch check passes over the proofs of a set again: b bad proofs among N cost <= 2 b ceil(log2 N) checks.
 
 constexpr size_t PS_VERIFY_LOCATE_MAX = (size_t)1 << 20;  // the F tree is 1 344 B per proof: 1.4 GB here
 constexpr size_t PS_LOCATE_ROUND_POINTS = (size_t)1 << 20;  // sets x public inputs one pass of a round scales and sums (two XYZZ buffers: 448 MB)
 constexpr unsigned PS_LOCATE_THREADS = 16;
+static size_t locate_per_pass(size_t diff) { return std::max<size_t>(1, PS_LOCATE_ROUND_POINTS / std::max<size_t>(diff, 1)); }  // sets of one pass
+
+// The round helpers of both locators, down to locate_parallel.  k_gather_words on c->stream; an empty gather (PHGR13 rounds
+// have them) launches nothing.  No Groth16 gather is empty: count = K >= 1 sets or segments, width W12, WX, 8 or, where
+// diff >= 1, a multiple of diff -- the guard holds back no launch there.
+static void locate_gather(ps_ctx* c, const void* in, const u32* ix, size_t count, u64 stride, u64 off, size_t width, void* out) {
+    if (count * width)
+        hipLaunchKernelGGL(k_gather_words, dim3(nblocks(count * width)), dim3(256), 0, c->stream, (const u32*)in, ix, (u32)count, stride, off, (u32)width, (u32*)out);
+}
+
+// Regions of c->lc_work one behind the other, each rounded up to 256 bytes: take() is where the next one starts
+struct LocateCarve {
+    size_t at = 0;
+    size_t take(size_t bytes) { return std::exchange(at, at + ((bytes + 255) & ~(size_t)255)); }
+    size_t total() const { return at; }
+};
+
+// A lap of the wall clock into lc_ms / plc_ms: *ms += the time since *t, which becomes now
+static void locate_lap(float* ms, std::chrono::steady_clock::time_point* t) {
+    const auto was = std::exchange(*t, std::chrono::steady_clock::now());
+    *ms += std::chrono::duration<float, std::milli>(*t - was).count();
+}
+
+// The levels of a product tree above level 0, each to its own place: level l at f + f_level_base(off, l, diff)
+static void locate_product_levels(ps_ctx* c, pairing_dev::Fp12* f, const u64* size, const u64* off, int nl, size_t diff, u32 simds) {
+    for (int l = 0; l + 1 < nl; l++) {
+        const u32 lpw = pairing_dev::spread_lanes(size[l + 1], simds);
+        hipLaunchKernelGGL(k_f12_product, dim3((unsigned)((size[l + 1] + lpw - 1) / lpw)), dim3(64), 0, c->stream,
+                           (const pairing_dev::Fp12*)(f + locate::f_level_base(off, l, diff)), (u32)size[l], lpw, f + locate::f_level_base(off, l + 1, diff));
+    }
+}
 
 static int locate_miller_levels(ps_ctx* c, const Affine<Fp>* g1, const Affine<Fp2>* g2, size_t n, const pairing_dev::Fp12** res, VbClock* clk) {
     typedef pairing_dev::Fp12 D12;
@@ -28,14 +59,10 @@ static int locate_miller_levels(ps_ctx* c, const Affine<Fp>* g1, const Affine<Fp
         return fail(PS_ERR_HIP, "ps_groth16_verify_batch_locate: no device memory for the levels of the product tree (" +
                                     std::to_string(sizeof(D12) * off[nl]) + " bytes for " + std::to_string(n) + " proofs)");
     D12* f = (D12*)c->lc_f12.p;
-    u32 lpw = pairing_dev::spread_lanes(n, simds);
+    const u32 lpw = pairing_dev::spread_lanes(n, simds);
     hipLaunchKernelGGL(k_miller_batch, dim3((unsigned)((n + lpw - 1) / lpw)), dim3(64), 0, c->stream, g1, g2, (u32)n, lpw, f);
     if (clk) clk->mark(2);
-    for (int l = 0; l + 1 < nl; l++) {  // every level to its own place
-        lpw = pairing_dev::spread_lanes(size[l + 1], simds);
-        hipLaunchKernelGGL(k_f12_product, dim3((unsigned)((size[l + 1] + lpw - 1) / lpw)), dim3(64), 0, c->stream, (const D12*)(f + off[l]), (u32)size[l], lpw,
-                           f + off[l + 1]);
-    }
+    locate_product_levels(c, f, size, off, nl, 0, simds);
     HIP_TRY(hipGetLastError());
     if (clk) clk->mark(3);
     *res = f + off[nl - 1];
@@ -105,8 +132,7 @@ static int locate_build_trees(ps_ctx* c, const ps_groth16_vk* vk, const ps_scala
 // descent below (X_S) and by ps_phgr13_verify_batch (the io part of rho_i gv_i, verify_phgr13_batch.inc).
 static void segment_sums(ps_ctx* c, const Xyzz<Fp>* base, size_t diff, size_t K, const Fr* scal_mont, Xyzz<Fp>** src, Xyzz<Fp>** dst) {
     constexpr size_t WX = sizeof(Xyzz<Fp>) / 4;
-    hipLaunchKernelGGL(k_gather_words, dim3(nblocks(K * WX * diff)), dim3(256), 0, c->stream, (const u32*)base, (const u32*)nullptr, (u32)K, (u64)0, (u64)0,
-                       (u32)(WX * diff), (u32*)*src);  // base, K times
+    locate_gather(c, base, nullptr, K, 0, 0, WX * diff, *src);  // base, K times
     hipLaunchKernelGGL(k_ec_scale<Fp>, dim3(nblocks(K * diff)), dim3(256), 0, c->stream, *src, (u32)(K * diff), scal_mont, ~0ull);
     for (size_t n = diff; n > 1; n = (n + 1) / 2) {  // K segments of diff points, the sum of a segment ends in its first slot
         hipLaunchKernelGGL(k_g1_pair_sums, dim3(nblocks(K * ((n + 1) / 2))), dim3(256), 0, c->stream, (const Xyzz<Fp>*)*src, (u32)n, (u32)K, (u32)diff, *dst,
@@ -115,40 +141,37 @@ static void segment_sums(ps_ctx* c, const Xyzz<Fp>* base, size_t diff, size_t K,
     }
 }
 
-// check(S) for the K nodes idx[] of level l: pass[k] = 1 / 0
-static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep, int l, const u32* idx, size_t K, uint8_t* pass) {
+// check(S) for the K nodes idx[] of level l: fail_mask[k] = 1 where it fails, else 0 -- the one-bit mask of locate_bisect
+static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep, int l, const u32* idx, size_t K, uint8_t* fail_mask) {
     typedef pairing_dev::Fp12 D12;
     constexpr size_t WX = sizeof(Xyzz<Fp>) / 4, W12 = sizeof(D12) / 4;
     const size_t diff = t.diff, cols = diff + 1, pd = std::max<size_t>(diff, 1);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // one workspace: node indices | F_S | R_S | t_S plain, Montgomery | two buffers of K x diff points | 2K points and their
     // chain products for the normalisation | 2K affine points
-    const size_t o_idx = 0, o_f = o_idx + al(4 * K), o_r = o_f + al(sizeof(D12) * K), o_t = o_r + al(32 * K), o_tm = o_t + al(32 * K * pd),
-                 o_p0 = o_tm + al(sizeof(Fr) * K * pd), o_p1 = o_p0 + al(sizeof(Xyzz<Fp>) * K * pd), o_n = o_p1 + al(sizeof(Xyzz<Fp>) * K * pd),
-                 o_a = o_n + al(batch_affine_tmp_bytes(2 * K, sizeof(Xyzz<Fp>))), total = o_a + al(sizeof(Affine<Fp>) * 2 * K);
+    LocateCarve work;
+    const size_t o_idx = work.take(4 * K), o_f = work.take(sizeof(D12) * K), o_r = work.take(32 * K), o_t = work.take(32 * K * pd),
+                 o_tm = work.take(sizeof(Fr) * K * pd), o_p0 = work.take(sizeof(Xyzz<Fp>) * K * pd), o_p1 = work.take(sizeof(Xyzz<Fp>) * K * pd),
+                 o_n = work.take(batch_affine_tmp_bytes(2 * K, sizeof(Xyzz<Fp>))), o_a = work.take(sizeof(Affine<Fp>) * 2 * K), total = work.total();
     if (c->lc_work.ensure(total))
         return fail(PS_ERR_HIP, "ps_groth16_verify_batch_locate: no device memory for a round of " + std::to_string(K) + " sets (" + std::to_string(total) + " bytes)");
     char* w = (char*)c->lc_work.p;
     u32* d_idx = (u32*)(w + o_idx);
-    const auto t0 = std::chrono::steady_clock::now();
+    auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipMemcpyAsync(d_idx, idx, 4 * K, hipMemcpyHostToDevice, c->stream));
     const u32* rows = t.rows + 8 * cols * t.off[l];
-    auto gather = [&](const void* in, const u32* ix, size_t count, u64 stride, u64 off, size_t width, void* out) {
-        hipLaunchKernelGGL(k_gather_words, dim3(nblocks(count * width)), dim3(256), 0, c->stream, (const u32*)in, ix, (u32)count, stride, off, (u32)width, (u32*)out);
-    };
-    gather(t.f + t.off[l], d_idx, K, W12, 0, W12, w + o_f);
-    gather(rows, d_idx, K, 8 * cols, 0, 8, w + o_r);
+    locate_gather(c, t.f + t.off[l], d_idx, K, W12, 0, W12, w + o_f);
+    locate_gather(c, rows, d_idx, K, 8 * cols, 0, 8, w + o_r);
     Xyzz<Fp>* norm = (Xyzz<Fp>*)(w + o_n);
     if (diff) {
-        gather(rows, d_idx, K, 8 * cols, 8, 8 * diff, w + o_t);
+        locate_gather(c, rows, d_idx, K, 8 * cols, 8, 8 * diff, w + o_t);
         hipLaunchKernelGGL(k_fr_to_mont, dim3(nblocks(K * diff)), dim3(256), 0, c->stream, (Fr*)(w + o_tm), (const u32*)(w + o_t), (u64)(K * diff));
         Xyzz<Fp>*src = (Xyzz<Fp>*)(w + o_p0), *dst = (Xyzz<Fp>*)(w + o_p1);
         segment_sums(c, t.iolp, diff, K, (const Fr*)(w + o_tm), &src, &dst);
-        gather(src, nullptr, K, WX * diff, 0, WX, norm);
+        locate_gather(c, src, nullptr, K, WX * diff, 0, WX, norm);
     } else {
         HIP_TRY(hipMemsetAsync(norm, 0, sizeof(Xyzz<Fp>) * K, c->stream));  // X_S is the identity (ZZ = 0)
     }
-    gather(t.pts + t.off[l], d_idx, K, WX, 0, WX, norm + K);
+    locate_gather(c, t.pts + t.off[l], d_idx, K, WX, 0, WX, norm + K);
     batch_to_affine<Fp>(c->stream, (char*)norm, 2 * K, w + o_a, (u32)sizeof(Affine<Fp>));
     HIP_TRY(hipGetLastError());
     std::vector<D12> hf(K);
@@ -158,7 +181,7 @@ static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep
     HIP_TRY(hipMemcpyAsync(hr.data(), w + o_r, 32 * K, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(ha.data(), w + o_a, sizeof(Affine<Fp>) * 2 * K, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const auto t1 = std::chrono::steady_clock::now();
+    locate_lap(&c->lc_ms[1], &t0);
     // the host's share: 3K Miller loops, then K products and final exponentiations
     typedef Affine<Fq> H1;
     std::vector<pairing::Fp12> loops(3 * K);
@@ -180,50 +203,28 @@ static int locate_check_sets(ps_ctx* c, const LocateTrees& t, const VbKeep& keep
     locate_parallel(K, [&](size_t k) {
         pairing::Fp12 f = f12_to_host(hf[k]);
         for (int j = 0; j < 3; j++) f = pairing::f12_mul(f, loops[3 * k + j]);
-        pass[k] = pairing::f12_eq(pairing::final_exp(f), pairing::f12_one()) ? 1 : 0;
+        fail_mask[k] = pairing::f12_eq(pairing::final_exp(f), pairing::f12_one()) ? 0 : 1;
     });
-    const auto t2 = std::chrono::steady_clock::now();
-    c->lc_ms[1] += std::chrono::duration<float, std::milli>(t1 - t0).count();
-    c->lc_ms[2] += std::chrono::duration<float, std::milli>(t2 - t1).count();
+    locate_lap(&c->lc_ms[2], &t0);
     return PS_OK;
 }
 
 static int locate_descent(ps_ctx* c, const ps_groth16_vk* vk, const ps_scalars* io, size_t N, const VbKeep& keep, uint8_t* valid, size_t* ninvalid) {
     memset(valid, 1, N);
     ps_verify_locate_info& info = c->lc_info;
-    if (N == 1) {  // the root is the proof
-        valid[0] = 0;
-        *ninvalid = info.invalid = 1;
-        return PS_OK;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
     LocateTrees t;
-    int rc = locate_build_trees(c, vk, io, N, keep, &t);
-    if (rc) return rc;
-    if (c->timing) (void)hipStreamSynchronize(c->stream);
-    c->lc_ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const size_t per_pass = std::max<size_t>(1, PS_LOCATE_ROUND_POINTS / std::max<size_t>(t.diff, 1));
-    std::vector<u32> failing{0}, tests, next;
-    std::vector<uint8_t> pass;
-    for (int l = t.nl - 1; l > 0 && !failing.empty(); l--) {
-        tests.clear();
-        next.clear();
-        for (u32 i : failing) {
-            if (locate::node_has_two_children(i, t.size[l - 1])) { tests.push_back(2 * i); tests.push_back(2 * i + 1); }
-            else next.push_back(2 * i);  // carried: the same set, the same verdict
-        }
-        pass.assign(tests.size(), 0);
-        for (size_t at = 0; at < tests.size(); at += per_pass)
-            if ((rc = locate_check_sets(c, t, keep, l - 1, tests.data() + at, std::min(per_pass, tests.size() - at), pass.data() + at))) return rc;
-        for (size_t k = 0; k < tests.size(); k++)
-            if (!pass[k]) next.push_back(tests[k]);
-        std::sort(next.begin(), next.end());
-        info.checks += (u32)tests.size();
-        info.levels = (u32)(t.nl - l);
-        failing.swap(next);
+    if (N > 1) {  // (one proof: the root is the leaf, the descent reads no tree)
+        auto t0 = std::chrono::steady_clock::now();
+        if (int rc = locate_build_trees(c, vk, io, N, keep, &t)) return rc;
+        if (c->timing) (void)hipStreamSynchronize(c->stream);
+        locate_lap(&c->lc_ms[0], &t0);
     }
-    for (u32 i : failing) valid[i] = 0;  // level 0: a failing leaf is an invalid proof
-    *ninvalid = info.invalid = (u32)failing.size();
+    std::vector<u32> leaves;
+    std::vector<uint8_t> masks;  // one equation: every failing leaf has mask 1
+    auto check = [&](int l, const u32* idx, const uint8_t*, size_t K, uint8_t* fmask) { return locate_check_sets(c, t, keep, l, idx, K, fmask); };
+    if (int rc = locate_bisect(N, 1, locate_per_pass(t.diff), check, &leaves, &masks, &info.checks, &info.levels)) return rc;
+    for (u32 i : leaves) valid[i] = 0;  // level 0: a failing leaf is an invalid proof
+    *ninvalid = info.invalid = (u32)leaves.size();
     return PS_OK;
 }
 
@@ -237,18 +238,19 @@ extern "C" int ps_groth16_verify_batch_locate(ps_ctx* c, const ps_groth16_vk* vk
     int ok = 0;
     VbKeep keep;
     int rc = verify_batch_impl(c, "ps_groth16_verify_batch_locate", PS_VERIFY_LOCATE_MAX, "2^20", vk, io, proofs, nproofs, rho_be32, &ok, &keep);
-    Scope scope;  // what a rejected batch handed over is this call's from here on
+    Scope scope(c->stream);  // what a rejected batch handed over is this call's from here on, on every way out
+    scope.in_flight();       // ... and a failed descent leaves a round's copies behind on the stream: wait for them
     *scope.points() = keep.c_pts;
     *scope.scalars() = keep.rho;
     if (rc || nproofs == 0) return rc;
     c->lc_info.checks = 1;
     if (ok) {
         memset(valid, 1, nproofs);
-        return PS_OK;
+        return scope.finish(PS_OK);
     }
     rc = locate_descent(c, vk, io, nproofs, keep, valid, ninvalid);
     if (rc) *ninvalid = 0;
-    return rc;
+    return scope.finish(rc);
 }
 
 extern "C" int ps_groth16_verify_batch_locate_info(ps_ctx* c, ps_verify_locate_info* out) {

@@ -12,12 +12,12 @@
 //   1. the batch check of ps_phgr13_verify_batch (phgr13_verify_batch_impl), the levels of its product tree kept:
 //      accepted -> done, one check and five products, nothing else launched;
 //   2. otherwise the trees the failed equations read (locate_phgr13_dev.hpp), built once;
-//   3. from the root down, both children of every failing node on the equations of the parent's mask, all nodes of a level
-//      in one round: their values gathered on the device, sum_j t_S,j ys_j by segment_sums, the K diff loops with the key's
-//      ws_k on the device and reduced with F_S to ONE value per set (k_f12_segment_products), one normalisation per group,
-//      one download; the remaining loops and one final exponentiation per tested (set, equation) on at most 16 host
-//      threads.  A node with one (carried) child hands verdict and mask down without a check.
-// No step after the batch check passes over the proofs of a set again.
+//   3. the descent: locate_bisect (locate_descent.hpp, shared with verify_locate.inc and run as it ships by
+//      tests/host_phgr13_locate_index.cpp) from the root's mask of failed equations.  A round (phgr13_locate_check_sets): the
+//      sets' values gathered on the device, sum_j t_S,j ys_j by segment_sums, the K diff loops with the key's ws_k on the
+//      device and reduced with F_S to ONE value per set (k_f12_segment_products), one normalisation per group, one download;
+//      the remaining loops and one final exponentiation per tested (set, equation) on at most 16 host threads.  The round
+//      helpers are those of verify_locate.inc.  No step after the batch check passes over the proofs of a set again.
 
 // The Miller values of a locating batch: k_miller_batch over all n + diff pairs into c->lc_f12, the levels of the product
 // tree over the FIRST n (every level kept, as locate_miller_levels keeps them), and the product of the key's diff loops taken
@@ -37,11 +37,7 @@ static int phgr13_miller_levels(ps_ctx* c, const std::string& fn, const Affine<F
     D12* f = (D12*)c->lc_f12.p;
     u32 lpw = pairing_dev::spread_lanes(n + diff, simds);
     hipLaunchKernelGGL(k_miller_batch, dim3((unsigned)((n + diff + lpw - 1) / lpw)), dim3(64), 0, c->stream, g1, g2, (u32)(n + diff), lpw, f);
-    for (int l = 0; l + 1 < nl; l++) {
-        lpw = pairing_dev::spread_lanes(size[l + 1], simds);
-        hipLaunchKernelGGL(k_f12_product, dim3((unsigned)((size[l + 1] + lpw - 1) / lpw)), dim3(64), 0, c->stream,
-                           (const D12*)(f + phgr13_locate::f_level_base(off, l, diff)), (u32)size[l], lpw, f + phgr13_locate::f_level_base(off, l + 1, diff));
-    }
+    locate_product_levels(c, f, size, off, nl, diff, simds);
     // the key's loops: a product tree of their own (a chain of diff products on one lane costs 13 ms at diff = 63), then root x root
     const D12* key = f + n;
     D12* lvl = f + phgr13_locate::f_key_levels_at(off, nl, diff);
@@ -91,11 +87,11 @@ static int phgr13_locate_build_trees(ps_ctx* c, const std::string& fn, const ps_
     const bool div = t->division() && diff;  // the trees E0 alone reads beyond hs and yss
     t->segs = t->nseg + (div ? diff : 0);
     const u64 nodes = t->off[t->nl];
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // leaves' workspace: the needed elements side by side (affine) | rho repeated for them | rho_i gv_i in XYZZ form | the
     // transposed inputs in Montgomery form
-    const size_t o_aff = 0, o_rho = o_aff + al(sizeof(Affine<Fp>) * t->nseg * N), o_gv = o_rho + al(sizeof(Fr) * t->nseg * N),
-                 o_tm = o_gv + al(div ? sizeof(Xyzz<Fp>) * N : 0), work = o_tm + al(div ? sizeof(Fr) * diff * N : 0);
+    LocateCarve carve;
+    const size_t o_aff = carve.take(sizeof(Affine<Fp>) * t->nseg * N), o_rho = carve.take(sizeof(Fr) * t->nseg * N),
+                 o_gv = carve.take(div ? sizeof(Xyzz<Fp>) * N : 0), o_tm = carve.take(div ? sizeof(Fr) * diff * N : 0), work = carve.total();
     const size_t b_g1 = sizeof(Xyzz<Fp>) * t->segs * nodes, b_g2 = t->g2() ? sizeof(Xyzz<Fp2>) * nodes : 0, b_rows = div ? 32 * cols * nodes : 0,
                  b_ys = sizeof(Xyzz<Fp>) * std::max<size_t>(diff, 1);
     if (c->lc_pts.ensure(b_g1) || c->plc_g2.ensure(b_g2) || c->lc_rows.ensure(b_rows) || c->lc_iolp.ensure(b_ys) || c->lc_work.ensure(work))
@@ -104,17 +100,13 @@ static int phgr13_locate_build_trees(ps_ctx* c, const std::string& fn, const ps_
     char* w = (char*)c->lc_work.p;
     Xyzz<Fp>* g1 = (Xyzz<Fp>*)c->lc_pts.p;
     const Fr* rho_m = (const Fr*)c->vb_rho.p;
-    auto gather = [&](const void* in, size_t count, size_t width, void* out) {  // `in` (width words) repeated `count` times
-        hipLaunchKernelGGL(k_gather_words, dim3(nblocks(count * width)), dim3(256), 0, c->stream, (const u32*)in, (const u32*)nullptr, (u32)count, (u64)0, (u64)0,
-                           (u32)width, (u32*)out);
-    };
     // element trees: rho_i X_i for the elements in play, one scaling for all of them
     if (t->nseg) {
         for (int e = 0; e < phgr13_locate::G1_ELEMENTS; e++)
             if (t->has(e))
                 HIP_TRY(hipMemcpyAsync((Affine<Fp>*)(w + o_aff) + (size_t)t->slot[e] * N, points_ptr(keep.view[e]), sizeof(Affine<Fp>) * N, hipMemcpyDeviceToDevice,
                                        c->stream));
-        gather(rho_m, t->nseg, WR * N, w + o_rho);
+        locate_gather(c, rho_m, nullptr, t->nseg, 0, 0, WR * N, w + o_rho);  // rho, once per element
         hipLaunchKernelGGL(k_ec_from_affine<Fp>, dim3(nblocks(t->nseg * N)), dim3(256), 0, c->stream, (const Affine<Fp>*)(w + o_aff), (u32)(t->nseg * N),
                            (u32)(t->nseg * N), g1);
         hipLaunchKernelGGL(k_ec_scale<Fp>, dim3(nblocks(t->nseg * N)), dim3(256), 0, c->stream, g1, (u32)(t->nseg * N), (const Fr*)(w + o_rho), ~0ull);
@@ -124,7 +116,7 @@ static int phgr13_locate_build_trees(ps_ctx* c, const std::string& fn, const ps_
         Xyzz<Fp>* leaves = g1 + t->nseg * N;
         hipLaunchKernelGGL(k_ec_from_affine<Fp>, dim3(nblocks(N)), dim3(256), 0, c->stream, (const Affine<Fp>*)points_ptr(keep.rgv), (u32)N, (u32)N,
                            (Xyzz<Fp>*)(w + o_gv));
-        gather(w + o_gv, diff, WX * N, leaves);
+        locate_gather(c, w + o_gv, nullptr, diff, 0, 0, WX * N, leaves);  // rho_i gv_i, once per public input
         hipLaunchKernelGGL(k_fr_to_mont, dim3(nblocks(diff * N)), dim3(256), 0, c->stream, (Fr*)(w + o_tm), scalars_ptr(keep.iot), (u64)(diff * N));
         hipLaunchKernelGGL(k_ec_scale<Fp>, dim3(nblocks(diff * N)), dim3(256), 0, c->stream, leaves, (u32)(diff * N), (const Fr*)(w + o_tm), ~0ull);
     }
@@ -187,45 +179,41 @@ static int phgr13_locate_check_sets(ps_ctx* c, const std::string& fn, const ps_p
         for (size_t k = 0; k < K; k++) h_el[s * K + k] = (u32)(segment_node(t.size, t.off, l, t.segs, s) + idx[k]);
     for (size_t k = 0; k < K0d; k++)
         for (size_t j = 0; j < diff; j++) h_p[k * diff + j] = (u32)(segment_node(t.size, t.off, l, t.segs, nseg + j) + h_div[k]);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // one workspace: index words | F_S | the loops' values | the sets' products | t_S plain, Montgomery | two buffers of
     // K0 x diff points | ws_io K0 times | G1 points to normalise (elements, sum_j t_S,j ys_j, P_S,k) and their chain products
     // | the same, affine | wss_S, chain products | affine
-    const size_t o_idx = 0, o_f = o_idx + al(4 * hidx.size()), o_m = o_f + al(sizeof(D12) * K0), o_fs = o_m + al(sizeof(D12) * K0d * diff),
-                 o_t = o_fs + al(sizeof(D12) * K0), o_tm = o_t + al(32 * K0d * diff), o_p0 = o_tm + al(sizeof(Fr) * K0d * diff),
-                 o_p1 = o_p0 + al(sizeof(Xyzz<Fp>) * K0d * diff), o_ws = o_p1 + al(sizeof(Xyzz<Fp>) * K0d * diff),
-                 o_n = o_ws + al(sizeof(Affine<Fp2>) * K0d * diff), o_a = o_n + al(batch_affine_tmp_bytes(n1, sizeof(Xyzz<Fp>))),
-                 o_n2 = o_a + al(sizeof(Affine<Fp>) * n1), o_a2 = o_n2 + al(batch_affine_tmp_bytes(K, sizeof(Xyzz<Fp2>))),
-                 total = o_a2 + al(sizeof(Affine<Fp2>) * K);
+    LocateCarve work;
+    const size_t o_idx = work.take(4 * hidx.size()), o_f = work.take(sizeof(D12) * K0), o_m = work.take(sizeof(D12) * K0d * diff),
+                 o_fs = work.take(sizeof(D12) * K0), o_t = work.take(32 * K0d * diff), o_tm = work.take(sizeof(Fr) * K0d * diff),
+                 o_p0 = work.take(sizeof(Xyzz<Fp>) * K0d * diff), o_p1 = work.take(sizeof(Xyzz<Fp>) * K0d * diff),
+                 o_ws = work.take(sizeof(Affine<Fp2>) * K0d * diff), o_n = work.take(batch_affine_tmp_bytes(n1, sizeof(Xyzz<Fp>))),
+                 o_a = work.take(sizeof(Affine<Fp>) * n1), o_n2 = work.take(batch_affine_tmp_bytes(K, sizeof(Xyzz<Fp2>))),
+                 o_a2 = work.take(sizeof(Affine<Fp2>) * K), total = work.total();
     if (c->lc_work.ensure(total))
         return fail(PS_ERR_HIP, fn + ": no device memory for a round of " + std::to_string(K) + " sets (" + std::to_string(total) + " bytes)");
     char* w = (char*)c->lc_work.p;
-    const auto t0 = std::chrono::steady_clock::now();
+    auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipMemcpyAsync(w + o_idx, hidx.data(), 4 * hidx.size(), hipMemcpyHostToDevice, c->stream));
     const u32 *d_all = (const u32*)(w + o_idx), *d_div = d_all + K, *d_el = d_div + K0, *d_p = d_el + nseg * K;
-    auto gather = [&](const void* in, const u32* ix, size_t count, u64 stride, u64 off, size_t width, void* out) {
-        if (count * width)
-            hipLaunchKernelGGL(k_gather_words, dim3(nblocks(count * width)), dim3(256), 0, c->stream, (const u32*)in, ix, (u32)count, stride, off, (u32)width, (u32*)out);
-    };
     Xyzz<Fp>* norm = (Xyzz<Fp>*)(w + o_n);
     Affine<Fp>* aff = (Affine<Fp>*)(w + o_a);
-    gather(t.g1, d_el, nseg * K, WX, 0, WX, norm);
+    locate_gather(c, t.g1, d_el, nseg * K, WX, 0, WX, norm);
     u32 simds = 0;
     int rc = ctx_simds(c, &simds);
     if (rc) return rc;
     if (K0) {
-        gather(t.f + f_level_base(t.off, l, diff), d_div, K0, W12, 0, W12, w + o_f);
+        locate_gather(c, t.f + f_level_base(t.off, l, diff), d_div, K0, W12, 0, W12, w + o_f);
         if (diff) {
             // sum_j t_S,j ys_j
-            gather(t.rows + 8 * cols * t.off[l], d_div, K0, 8 * cols, 8, 8 * diff, w + o_t);
+            locate_gather(c, t.rows + 8 * cols * t.off[l], d_div, K0, 8 * cols, 8, 8 * diff, w + o_t);
             hipLaunchKernelGGL(k_fr_to_mont, dim3(nblocks(K0 * diff)), dim3(256), 0, c->stream, (Fr*)(w + o_tm), (const u32*)(w + o_t), (u64)(K0 * diff));
             Xyzz<Fp>*src = (Xyzz<Fp>*)(w + o_p0), *dst = (Xyzz<Fp>*)(w + o_p1);
             segment_sums(c, t.ysx, diff, K0, (const Fr*)(w + o_tm), &src, &dst);
-            gather(src, nullptr, K0, WX * diff, 0, WX, norm + nseg * K);
+            locate_gather(c, src, nullptr, K0, WX * diff, 0, WX, norm + nseg * K);
             // P_S,k, and ws_io once per set
-            gather(t.g1, d_p, K0 * diff, WX, 0, WX, norm + nseg * K + K0);
+            locate_gather(c, t.g1, d_p, K0 * diff, WX, 0, WX, norm + nseg * K + K0);
             if (storage_wait_ready(vk->ws_io->st, c->stream)) return fail(PS_ERR_HIP, fn + ": event wait failed");
-            gather(points_ptr(vk->ws_io), nullptr, K0, 0, 0, WA2 * diff, w + o_ws);
+            locate_gather(c, points_ptr(vk->ws_io), nullptr, K0, 0, 0, WA2 * diff, w + o_ws);
         }
     }
     if (n1) batch_to_affine<Fp>(c->stream, (char*)norm, n1, (char*)aff, (u32)sizeof(Affine<Fp>));
@@ -240,7 +228,7 @@ static int phgr13_locate_check_sets(ps_ctx* c, const std::string& fn, const ps_p
                            (u32)diff, lpw, (D12*)(w + o_fs));
     }
     if (t.g2()) {
-        gather(t.wss + t.off[l], d_all, K, WX2, 0, WX2, w + o_n2);
+        locate_gather(c, t.wss + t.off[l], d_all, K, WX2, 0, WX2, w + o_n2);
         batch_to_affine<Fp2>(c->stream, w + o_n2, K, w + o_a2, (u32)sizeof(Affine<Fp2>));
     }
     HIP_TRY(hipGetLastError());
@@ -251,7 +239,7 @@ static int phgr13_locate_check_sets(ps_ctx* c, const std::string& fn, const ps_p
     if (!ha.empty()) HIP_TRY(hipMemcpyAsync(ha.data(), aff, sizeof(Affine<Fp>) * ha.size(), hipMemcpyDeviceToHost, c->stream));
     if (!hw.empty()) HIP_TRY(hipMemcpyAsync(hw.data(), w + o_a2, sizeof(Affine<Fp2>) * K, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const auto t1 = std::chrono::steady_clock::now();
+    locate_lap(&c->plc_ms[1], &t0);
     // the host's share: the loops of every tested (set, equation), then their products and final exponentiations
     using pairing_dev::neg_g1;
     const Affine<Fp2> g2 = generator((const Fp2*)0);
@@ -303,9 +291,7 @@ static int phgr13_locate_check_sets(ps_ctx* c, const std::string& fn, const ps_p
     for (size_t i = 0; i < tests.size(); i++)
         if (!holds[i]) fmask[tests[i].set] |= (uint8_t)(1u << tests[i].eq);
     *products += (u32)tests.size();
-    const auto t2 = std::chrono::steady_clock::now();
-    c->plc_ms[1] += std::chrono::duration<float, std::milli>(t1 - t0).count();
-    c->plc_ms[2] += std::chrono::duration<float, std::milli>(t2 - t1).count();
+    locate_lap(&c->plc_ms[2], &t0);
     return PS_OK;
 }
 
@@ -314,56 +300,25 @@ static int phgr13_locate_descent(ps_ctx* c, const std::string& fn, const ps_phgr
     memset(valid, 1, N);
     if (failed) memset(failed, 0, N);
     ps_phgr13_locate_info& info = c->plc_info;
-    auto report = [&](const std::vector<u32>& nodes, const std::vector<uint8_t>& masks) {  // level 0: a failing leaf is an invalid proof
-        for (size_t k = 0; k < nodes.size(); k++) {
-            valid[nodes[k]] = 0;
-            if (failed) failed[nodes[k]] = masks[k];
-            info.failed |= masks[k];
-        }
-        *ninvalid = info.invalid = (u32)nodes.size();
-    };
-    std::vector<u32> failing{0}, tests, next;
-    std::vector<uint8_t> fmasks{(uint8_t)root}, tmasks, nmasks, got;
-    if (N == 1) {  // the root is the proof
-        report(failing, fmasks);
-        return PS_OK;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
     Phgr13Trees t;
-    int rc = phgr13_locate_build_trees(c, fn, vk, io, N, root, keep, &t);
-    if (rc) return rc;
-    if (c->timing) (void)hipStreamSynchronize(c->stream);
-    c->plc_ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const size_t per_pass = std::max<size_t>(1, PS_LOCATE_ROUND_POINTS / std::max<size_t>(t.diff, 1));
-    for (int l = t.nl - 1; l > 0 && !failing.empty(); l--) {
-        tests.clear();
-        tmasks.clear();
-        std::vector<std::pair<u32, uint8_t>> below;
-        for (size_t k = 0; k < failing.size(); k++) {
-            const u32 i = failing[k];
-            if (locate::node_has_two_children(i, t.size[l - 1])) {
-                for (u32 ch : {2 * i, 2 * i + 1}) { tests.push_back(ch); tmasks.push_back(fmasks[k]); }
-            } else {
-                below.push_back({2 * i, fmasks[k]});  // carried: the same set, the same verdict, the same mask
-            }
-        }
-        got.assign(tests.size(), 0);
-        for (size_t at = 0; at < tests.size(); at += per_pass)
-            if ((rc = phgr13_locate_check_sets(c, fn, vk, t, keep, l - 1, tests.data() + at, tmasks.data() + at, std::min(per_pass, tests.size() - at),
-                                               got.data() + at, &info.products)))
-                return rc;
-        for (size_t k = 0; k < tests.size(); k++)
-            if (got[k]) below.push_back({tests[k], got[k]});
-        std::sort(below.begin(), below.end());
-        next.clear();
-        nmasks.clear();
-        for (const auto& b : below) { next.push_back(b.first); nmasks.push_back(b.second); }
-        info.checks += (u32)tests.size();
-        info.levels = (u32)(t.nl - l);
-        failing.swap(next);
-        fmasks.swap(nmasks);
+    if (N > 1) {  // (one proof: the root is the leaf, the descent reads no tree)
+        auto t0 = std::chrono::steady_clock::now();
+        if (int rc = phgr13_locate_build_trees(c, fn, vk, io, N, root, keep, &t)) return rc;
+        if (c->timing) (void)hipStreamSynchronize(c->stream);
+        locate_lap(&c->plc_ms[0], &t0);
     }
-    report(failing, fmasks);
+    std::vector<u32> leaves;
+    std::vector<uint8_t> masks;
+    auto check = [&](int l, const u32* idx, const uint8_t* pmask, size_t K, uint8_t* fmask) {
+        return phgr13_locate_check_sets(c, fn, vk, t, keep, l, idx, pmask, K, fmask, &info.products);
+    };
+    if (int rc = locate_bisect(N, (uint8_t)root, locate_per_pass(t.diff), check, &leaves, &masks, &info.checks, &info.levels)) return rc;
+    for (size_t k = 0; k < leaves.size(); k++) {  // level 0: a failing leaf is an invalid proof
+        valid[leaves[k]] = 0;
+        if (failed) failed[leaves[k]] = masks[k];
+        info.failed |= masks[k];
+    }
+    *ninvalid = info.invalid = (u32)leaves.size();
     return PS_OK;
 }
 

@@ -1,12 +1,14 @@
 // host_locate_index.cpp -- the index arithmetic of the locating batch verifier's trees, checked on the host.
 //     g++ -std=c++17 -O1 -fsanitize=address,undefined -fno-sanitize-recover=all
 // playsnark_amd/csrc/locate_dev.hpp keeps every level of three trees one behind the other; the descent of
-// verify_locate.inc finds a node's children, its carried nodes and the proofs it covers with the functions compiled here:
+// verify_locate.inc, locate_bisect of locate_descent.hpp, finds a node's children and its carried nodes with the functions
+// compiled here, and is itself compiled here and run as it ships:
 //   * tree_levels: the sizes halve (rounded up) down to one, the offsets are their running sum, the total is below 2 n + 32;
 //   * node_range: the nodes of a level cover [0, n) without gap or overlap, and a node covers what its children cover;
 //   * node_has_two_children: false exactly for the odd one out, whose range is its single child's;
-//   * a descent over these functions from the root, following a set of marked leaves, reaches exactly the marked leaves,
-//     with at most 2 b ceil(log2 n) tested nodes;
+//   * locate_bisect from the root, its `check` an oracle that knows a set of marked leaves, reports exactly the marked leaves
+//     in ascending order, with at most 2 b ceil(log2 n) tested nodes and ceil(log2 n) levels; cut into passes of 1 or 3 sets
+//     it reports the same and hands no pass more; a `check` that returns a code ends it with that code;
 //   * words8_add_mod_r against 128-bit arithmetic on the edges 0, 1, r - 1 and pairs that sum to exactly r.
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +31,7 @@ static int failures = 0;
             }                                                                        \
         }                                                                            \
     } while (0)
+#include "host_locate_descent.hpp"  // locate_bisect and its oracle harness, which reports through CHECK
 
 static unsigned long long rng_state = 0x6c6f63617465ull;
 static unsigned long long rnd() {  // splitmix64
@@ -78,37 +81,19 @@ static void check_tree(u64 n) {
     }
 }
 
-// the descent of verify_locate.inc with an oracle that knows the marked leaves
-static void check_descent(u64 n, const std::set<u64>& bad) {
-    u64 size[locate::MAX_LEVELS], off[locate::MAX_LEVELS + 1];
-    const int nl = locate::tree_levels(n, size, off);
-    auto fails = [&](int l, u64 i) {
+// the descent of verify_locate.inc as it ships (one equation: mask 1) with an oracle that knows the marked leaves
+static Descent check_descent(u64 n, const std::set<u64>& bad) {
+    const Descent d = descend_every_way(n, [&](int l, u64 i) {
         u64 lo, hi;
         locate::node_range(l, i, n, &lo, &hi);
         auto it = bad.lower_bound(lo);
-        return it != bad.end() && *it < hi;
-    };
-    if (bad.empty()) return;
-    std::vector<u64> failing{0}, next;
-    u64 checks = 1;
-    for (int l = nl - 1; l > 0; l--) {
-        next.clear();
-        for (u64 i : failing) {
-            if (locate::node_has_two_children(i, size[l - 1])) {
-                checks += 2;
-                for (u64 ch : {2 * i, 2 * i + 1})
-                    if (fails(l - 1, ch)) next.push_back(ch);
-            } else {
-                next.push_back(2 * i);
-            }
-        }
-        for (u64 i : next) CHECK(i < size[l - 1], "n = %llu: node %llu outside level %d", (unsigned long long)n, (unsigned long long)i, l - 1);
-        failing.swap(next);
-    }
-    CHECK(std::set<u64>(failing.begin(), failing.end()) == bad && failing.size() == bad.size(), "n = %llu, %zu marked: found %zu",
-          (unsigned long long)n, bad.size(), failing.size());
-    CHECK(checks <= 1 + 2 * bad.size() * (u64)ceil_log2(n), "n = %llu, %zu marked: %llu checks", (unsigned long long)n, bad.size(),
-          (unsigned long long)checks);
+        return it != bad.end() && *it < hi ? 1u : 0u;
+    });
+    CHECK(std::set<u64>(d.leaves.begin(), d.leaves.end()) == bad && d.leaves.size() == bad.size() && d.masks == std::vector<uint8_t>(bad.size(), 1),
+          "n = %llu, %zu marked: found %zu", (unsigned long long)n, bad.size(), d.leaves.size());
+    CHECK(1 + (u64)d.checks <= 1 + 2 * bad.size() * (u64)ceil_log2(n) && d.levels == (u32)ceil_log2(n), "n = %llu, %zu marked: %u checks, %u levels",
+          (unsigned long long)n, bad.size(), 1 + d.checks, d.levels);  // with the batch's own check
+    return d;
 }
 
 typedef unsigned __int128 u128;
@@ -169,6 +154,10 @@ int main() {
     check_descent(300, {296, 299});
     check_descent(300, {0, 1});
     check_descent(300, {0, 299});
+    // levels of 7, 4, 2, 1 nodes, leaf 6 marked: the root's two children, the two children of node 1 of 2 (nodes 2 and 3 of
+    // 4), and node 3 of 4 has the single child 6 -- 2 + 2 + 0 tested nodes
+    const Descent seven = check_descent(7, {6});
+    CHECK(seven.checks == 4 && seven.levels == 3 && seven.calls == 2, "n = 7, leaf 6: %u checks, %u levels, %zu calls", seven.checks, seven.levels, seven.calls);
     u32 r[8], zero[8] = {0}, one[8] = {1}, rm1[8];
     for (int i = 0; i < 8; i++) r[i] = FrParams::mod(i);
     std::memcpy(rm1, r, 32);

@@ -9,9 +9,10 @@
 //     all levels tile the array without gap or overlap, level by level, and a parent's children lie in its own segment;
 //   * f_level_base / f_tree_values: level 0, the key's loops, the upper levels and the batch's product tile the F buffer;
 //   * host_loops: two, two, two, two and three;
-//   * a descent with masks over these functions (children tested on the parent's mask alone, carried nodes inherit) reports
-//     exactly the marked leaves with exactly their masks, within checks <= 1 + 2 b ceil(log2 n) and
-//     products <= 5 + 2 ceil(log2 n) sum popcount(mask).
+//   * locate_bisect of locate_descent.hpp, the descent as it ships (children tested on the parent's mask alone, carried nodes
+//     inherit), its `check` an oracle that knows the marked leaves, reports exactly the marked leaves with exactly their
+//     masks, within checks <= 1 + 2 b ceil(log2 n) and products <= 5 + 2 ceil(log2 n) sum popcount(mask); cut into passes of
+//     1 or 3 sets it reports the same and hands no pass more; a `check` that returns a code ends it with that code.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +36,7 @@ static int failures = 0;
             }                                                                        \
         }                                                                            \
     } while (0)
+#include "host_locate_descent.hpp"  // locate_bisect and its oracle harness, which reports through CHECK
 
 static unsigned long long rng_state = 0x7068677231336cull;
 static unsigned long long rnd() {  // splitmix64
@@ -134,43 +136,26 @@ static void check_layout(u64 n, u64 segs, u64 diff) {
     for (u64 i = 0; i < at; i++) CHECK(f[i] == 1, "n = %llu diff = %llu: a hole in the F buffer", (unsigned long long)n, (unsigned long long)diff);
 }
 
-// the descent of verify_phgr13_locate.inc with an oracle that knows the marked leaves and their masks
-static void check_descent(u64 n, const std::map<u64, u32>& bad) {
-    u64 size[locate::MAX_LEVELS], off[locate::MAX_LEVELS + 1];
-    const int nl = locate::tree_levels(n, size, off);
-    auto mask_of = [&](int l, u64 i) {
+// the descent of verify_phgr13_locate.inc as it ships with an oracle that knows the marked leaves and their masks
+static Descent check_descent(u64 n, const std::map<u64, u32>& bad) {
+    const Descent d = descend_every_way(n, [&](int l, u64 i) {
         u64 lo, hi;
         locate::node_range(l, i, n, &lo, &hi);
         u32 m = 0;
         for (auto it = bad.lower_bound(lo); it != bad.end() && it->first < hi; ++it) m |= it->second;
         return m;
-    };
-    if (bad.empty()) return;
-    std::map<u64, u32> failing{{0, mask_of(nl - 1, 0)}}, next;
-    u64 checks = 1, products = EQUATIONS, bits = 0;
+    });
+    std::map<u64, u32> found;
+    u64 bits = 0;
+    for (size_t k = 0; k < d.leaves.size(); k++) found[d.leaves[k]] = d.masks[k];
     for (const auto& b : bad) bits += (u64)popcount(b.second);
-    for (int l = nl - 1; l > 0; l--) {
-        next.clear();
-        for (const auto& node : failing) {
-            const u64 i = node.first;
-            if (locate::node_has_two_children(i, size[l - 1])) {
-                for (u64 ch : {2 * i, 2 * i + 1}) {
-                    checks++;
-                    products += (u64)popcount(node.second);
-                    const u32 m = mask_of(l - 1, ch);
-                    CHECK((m & ~node.second) == 0, "a child fails an equation its parent passed");
-                    if (m & node.second) next[ch] = m & node.second;
-                }
-            } else {
-                next[2 * i] = node.second;
-            }
-        }
-        failing.swap(next);
-    }
-    CHECK(failing == bad, "n = %llu, %zu marked: found %zu", (unsigned long long)n, bad.size(), failing.size());
-    CHECK(checks <= 1 + 2 * bad.size() * (u64)ceil_log2(n), "n = %llu, %zu marked: %llu checks", (unsigned long long)n, bad.size(), (unsigned long long)checks);
-    CHECK(products <= EQUATIONS + 2 * (u64)ceil_log2(n) * bits, "n = %llu, %zu marked: %llu products", (unsigned long long)n, bad.size(),
-          (unsigned long long)products);
+    CHECK(found == bad && d.leaves.size() == bad.size(), "n = %llu, %zu marked: found %zu", (unsigned long long)n, bad.size(), d.leaves.size());
+    // with the batch's own check and its five products
+    CHECK(1 + (u64)d.checks <= 1 + 2 * bad.size() * (u64)ceil_log2(n) && d.levels == (u32)ceil_log2(n), "n = %llu, %zu marked: %u checks, %u levels",
+          (unsigned long long)n, bad.size(), 1 + d.checks, d.levels);
+    CHECK(EQUATIONS + d.products <= EQUATIONS + 2 * (u64)ceil_log2(n) * bits, "n = %llu, %zu marked: %llu products", (unsigned long long)n, bad.size(),
+          (unsigned long long)(EQUATIONS + d.products));
+    return d;
 }
 
 int main() {
@@ -203,6 +188,11 @@ int main() {
     }
     check_descent(7, {{1, 0b00010u}, {5, 0b01000u}});  // different equations in different halves
     check_descent(65, {{32, 0b10011u}, {33, 0b00100u}});
+    // levels of 7, 4, 2, 1 nodes, leaf 6 marked on three equations: the root's two children, the two children of node 1 of 2,
+    // and node 3 of 4 has the single child 6 -- 2 + 2 + 0 tested nodes, each on the three equations
+    const Descent seven = check_descent(7, {{6, 0b10011u}});
+    CHECK(seven.checks == 4 && seven.levels == 3 && seven.products == 12, "n = 7, leaf 6: %u checks, %u levels, %llu products", seven.checks, seven.levels,
+          (unsigned long long)seven.products);
     if (failures) {
         std::fprintf(stderr, "%d failures\n", failures);
         return 1;

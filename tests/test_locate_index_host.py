@@ -1,7 +1,9 @@
 """CPU: the index arithmetic of the locating batch verifier's trees (playsnark_amd/csrc/locate_dev.hpp: level sizes and
 offsets, the proofs a node covers, carried nodes) and its modular addition of plain words, compiled for the host under
 ASan + UBSan by tests/host_locate_index.cpp and run over every tree size up to 1 100, the sizes at the caps, and descents
-after marked leaves (the bound 1 + 2 b ceil(log2 N) on the tested nodes included)."""
+after marked leaves (the bound 1 + 2 b ceil(log2 N) on the tested nodes included).  The descent is the loop the library
+ships, locate_bisect of playsnark_amd/csrc/locate_descent.hpp, with an oracle in place of the device's checks
+(tests/host_locate_descent.hpp): also cut into passes of 1 and of 3 sets, and stopped by a check that returns an error."""
 import os
 import subprocess
 

@@ -2,7 +2,9 @@
 root mask needs, where the nodes of the level-major G1 trees and of the F tree lie, the host loops per equation), compiled
 for the host under ASan + UBSan by tests/host_phgr13_locate_index.cpp -- its own main, no Python in the process -- and run
 over every root mask, tree sizes 1 .. 70 and some larger ones with 1 .. 70 trees side by side, and descents with masks after
-marked leaves (the bounds on checks and products included)."""
+marked leaves (the bounds on checks and products included).  The descent is the loop the library ships, locate_bisect of
+playsnark_amd/csrc/locate_descent.hpp, with an oracle in place of the device's checks (tests/host_locate_descent.hpp): also
+cut into passes of 1 and of 3 sets, and stopped by a check that returns an error."""
 import os
 import subprocess
 

@@ -138,6 +138,22 @@ def test_several_bad_proofs_are_located(ps_api, ctx, co, pr, case):
     _check(ps_api, ctx, w, proofs, ios, _rhos(pr, rng, N), want)
 
 
+def test_exact_counts_of_one_carried_leaf(ps_api, ctx, co, pr):
+    """N = 7, proof 6 alone invalid, in vss (E0, E1 and E4): the counts of a rejected batch as exact numbers, worked out by
+    hand from the levels of 7, 4, 2, 1 nodes -- the batch check (1 check, 5 products); the root's two children, nodes 0 and 1
+    of 2, on the root's three equations (2 checks, 6 products), node 1 (proofs 4 .. 6) fails all three; its two children,
+    nodes 2 and 3 of 4 (2, 6), node 3 (proof 6) fails all three; node 3 has the single child 6 of 7, carried, handed down
+    without a check (0, 0).  1 + 2 + 2 + 0 = 5 checks over 3 levels, 5 + 4 popcount(mask) = 17 products."""
+    N, mask = 7, pc.MASK["vss"]
+    w = _world(ps_api, ctx, co, pr, pc.GATES, N)
+    rng = pr.SplitMix64(SEED + 5000)
+    proofs, ios = list(w.proofs), [list(v) for v in w.ios]
+    _tamper_at(ps_api, pr, co, w, proofs, ios, 6, "vss", 5006)
+    info = _check(ps_api, ctx, w, proofs, ios, _rhos(pr, rng, N), {6: mask})
+    assert _popcount(mask) == 3
+    assert info == {"checks": 5, "products": 5 + 4 * _popcount(mask), "levels": 3, "invalid": 1, "failed": mask}
+
+
 def test_tree_shape_of_the_carried_case():
     sizes = lambda n: [n] + ([] if n == 1 else sizes((n + 1) // 2))
     assert sizes(7) == [7, 4, 2, 1] and sizes(65) == [65, 33, 17, 9, 5, 3, 2, 1]

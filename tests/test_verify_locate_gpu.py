@@ -129,6 +129,19 @@ def test_several_bad_proofs_are_located(ps_api, ctx, pr, mat, tampered, case):
     assert mat.live[0] == 0
 
 
+def test_exact_counts_of_one_carried_leaf(ps_api, ctx, pr, mat, tampered):
+    """N = 7, proof 6 alone invalid: the counts of a rejected batch as exact numbers, worked out by hand from the levels of
+    7, 4, 2, 1 nodes -- the batch check (1); the root's two children, nodes 0 and 1 of 2 (2), node 1 (proofs 4 .. 6) fails;
+    its two children, nodes 2 and 3 of 4 (2), node 3 (proof 6) fails; node 3 has the single child 6 of 7, carried, handed
+    down without a check (0).  1 + 2 + 2 + 0 = 5 checks over 3 levels."""
+    n, rng = 7, pr.SplitMix64(SEED + 5000)
+    proofs, ios = list(mat.proofs[:n]), [list(v) for v in mat.ios[:n]]
+    bad = tampered[rng.next() % 48]
+    proofs[6], ios[6] = bad[0], list(bad[1])
+    info = _check(ps_api, ctx, mat, proofs, ios, _rhos(pr, rng, n, 128), [6])
+    assert info == {"checks": 5, "levels": 3, "invalid": 1}
+
+
 def test_tree_shape_of_the_carried_cases():
     """What the case names claim about N = 7 and N = 300"""
     sizes = lambda n: [n] + ([] if n == 1 else sizes((n + 1) // 2))
