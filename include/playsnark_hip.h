@@ -64,7 +64,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_kzg_verify and ps_kzg_verify_batch (no struct at all).  Then ps_scalars_lincomb, ps_kzg_open_multi and
  *      ps_kzg_verify_multi (no struct either).  Then ps_poly_scan_set_group, ps_poly_div_roots, ps_kzg_open_set and
  *      ps_kzg_verify_set (no struct either).  Then ps_poly_lagrange_tile, ps_qap_gate_values, ps_poly_eval_lagrange,
- *      ps_poly_div_linear_lagrange, ps_kzg_commit_lagrange and ps_kzg_open_lagrange (no struct either). */
+ *      ps_poly_div_linear_lagrange, ps_kzg_commit_lagrange and ps_kzg_open_lagrange (no struct either).  Then
+ *      ps_poly_lagrange_set_group, ps_poly_div_roots_lagrange and ps_kzg_open_set_lagrange (no struct either). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -987,6 +988,32 @@ int ps_kzg_commit_lagrange(ps_ctx* ctx, const ps_points* lag_g1, const ps_scalar
  * ps_msm_batch of the k rows over lag_g1 otherwise; the rows never leave the device. */
 int ps_kzg_open_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32, size_t k,
                          uint8_t* y_be32 /* k */, uint8_t* proofs /* k * 96 */);
+
+/* ---- A value-form polynomial at a SET of points: ps_poly_div_roots and ps_kzg_open_set from the values, no interpolation ----
+ * S = {z_0 .. z_{k-1}}, k distinct canonical points, on the domain or off it; c_j = 1 / prod_{l != j} (z_j - z_l), y_j = p(z_j).
+ * The partial fractions of the set section hold value by value on the nodes:
+ *     q(i) = sum_j c_j (y_j - v_i) / (z_j - i)     with the term of a point that IS node i replaced by c_j q_m, q_m the value
+ *                                                  ps_poly_div_linear_lagrange gives at its own node
+ * are the n values on 1 .. n of q = (p - r) / Z_S, of degree <= n - 1 - k, so sum_i q(i) lag_g1[i] = [q(tau)] G1: the proof of
+ * ps_kzg_open_set for the interpolated coefficients, the same 96 bytes, and ps_kzg_verify_set checks it unchanged.  The k
+ * linear quotients are folded into ONE row while they are computed: a workgroup owns a tile and a group
+ * of ps_poly_lagrange_set_group() points, and ONE field inversion serves the whole group.  Device memory beside the result:
+ * ceil(k / G) partial rows of n scalars (none for k <= G), never k * n.
+ * Conventions, the union of the two sections: two equal points are PS_ERR_ARG (the message names both indices); k = 0 is
+ * PS_ERR_ARG; `values` and lag_g1 hold exactly n elements (PS_ERR_LENGTH otherwise); z is canonical (PS_ERR_ENCODING otherwise); a
+ * G2 array, a NULL argument, k > 1024 or k * n >= 2^32 are PS_ERR_ARG, and so is a non-empty MSM queue where a sum is taken.
+ * Added within revision 5 (found by symbol, no existing struct changed).
+ * ps_poly_lagrange_set_group: G, the points that share an inversion (tests sit on its edges; a constant of the build). */
+int ps_poly_lagrange_set_group(void);
+/* *qv: the n values of q on 1 .. n, all zero for k >= n.  y[j] = p(z_j) as ps_poly_eval_lagrange gives it (k * 32 bytes).  rem,
+ * unless NULL: the k coefficients of the remainder r, lowest first, as ps_poly_div_roots gives them.  Caller frees *qv. */
+int ps_poly_div_roots_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, ps_scalars** qv,
+                               uint8_t* y_be32 /* k */, uint8_t* rem_be32 /* k coefficients, lowest first; may be NULL */);
+/* y[j] = p(z_j) and proof = [q(tau)] G1 for the whole set: the row above, then ONE ps_msm (the lone sum) over lag_g1; nothing but
+ * values and proof leaves the device.  Byte-identical to ps_kzg_open_set on ps_qap_interpolate's coefficients, and for k = 1 to
+ * ps_kzg_open_lagrange.  k >= n: the proof is the identity. */
+int ps_kzg_open_set_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32,
+                             size_t k, uint8_t* y_be32 /* k */, uint8_t proof[96]);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ SYMBOLS = [
     "ps_poly_scan_set_group", "ps_poly_div_roots", "ps_kzg_open_set", "ps_kzg_verify_set",
     "ps_poly_lagrange_tile", "ps_qap_gate_values", "ps_poly_eval_lagrange", "ps_poly_div_linear_lagrange", "ps_kzg_commit_lagrange",
     "ps_kzg_open_lagrange",
+    "ps_poly_lagrange_set_group", "ps_poly_div_roots_lagrange", "ps_kzg_open_set_lagrange",
 ]
 
 
@@ -292,6 +293,10 @@ def _load():
         lib.ps_poly_div_linear_lagrange.argtypes = [vp, vp, vp, C.c_char_p, sz, pp, C.c_char_p]
         lib.ps_kzg_commit_lagrange.argtypes = [vp, vp, vp, C.c_char_p]
         lib.ps_kzg_open_lagrange.argtypes = [vp, vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
+    if hasattr(lib, "ps_kzg_open_set_lagrange"):  # likewise: a set of points of a value-form polynomial, within revision 5
+        lib.ps_poly_lagrange_set_group.argtypes = []
+        lib.ps_poly_div_roots_lagrange.argtypes = [vp, vp, vp, C.c_char_p, sz, pp, C.c_char_p, C.c_char_p]
+        lib.ps_kzg_open_set_lagrange.argtypes = [vp, vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
     return lib
 
 

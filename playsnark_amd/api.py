@@ -402,6 +402,18 @@ class Poly:
         _check(lib.ps_poly_div_linear_lagrange(self.ctx._h, qap._h, self._h, _rho_bytes(zs), k, C.byref(h), ys))
         return Poly(self.ctx, h), [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
 
+    def DivRootsLagrange(self, qap: "QAP", zs: Sequence[int], remainder: bool = True):
+        """DivRoots for a polynomial held as its values on the domain 1..n of qap (ps_poly_div_roots_lagrange), len(zs) >= 1
+        distinct points, on the domain or off it.  Returns (qv, ys, rem): qv a Poly of n scalars, the VALUES on 1..n of
+        (p - r) / Z_S (all zero for len(zs) >= n); ys[j] = p(zs[j]); rem as DivRoots gives it, None with remainder=False."""
+        k = len(zs)
+        h = C.c_void_p()
+        ys = C.create_string_buffer(32 * max(k, 1))
+        rem = C.create_string_buffer(32 * max(k, 1)) if remainder else None
+        _check(lib.ps_poly_div_roots_lagrange(self.ctx._h, qap._h, self._h, _rho_bytes(zs), k, C.byref(h), ys, rem))
+        val = lambda buf: [int.from_bytes(buf.raw[32 * j : 32 * j + 32], "big") for j in range(k)]
+        return Poly(self.ctx, h), val(ys), (val(rem) if remainder else None)
+
     @staticmethod
     def LinComb(polys: Sequence["Poly"], coef_matrix: Sequence[Sequence[int]]) -> "Poly":
         """len(coef_matrix[0]) rows of N = max len(p) coefficients, row j = sum_i coef_matrix[i][j] * polys[i] with every
@@ -933,6 +945,17 @@ def KZGOpenSet(tau_g1: Points, p: Poly, zs: Sequence[int]):
     ys = C.create_string_buffer(32 * max(k, 1))
     proof = C.create_string_buffer(96)
     _check(lib.ps_kzg_open_set(p.ctx._h, tau_g1._h, p._h, _rho_bytes(zs), k, ys, proof))
+    return [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], proof.raw
+
+
+def KZGOpenSetLagrange(qap: "QAP", lag_g1: Points, values: Poly, zs: Sequence[int]):
+    """(ys, proof) as KZGOpenSet gives them for the interpolated coefficients, byte for byte, from the n values on the domain of
+    qap and the Lagrange form of the string (ps_kzg_open_set_lagrange): no interpolation and no division.  len(zs) >= 1 distinct
+    points, which may lie on the domain; the identity for len(zs) >= n.  KZGVerifySet checks the proof unchanged."""
+    k = len(zs)
+    ys = C.create_string_buffer(32 * max(k, 1))
+    proof = C.create_string_buffer(96)
+    _check(lib.ps_kzg_open_set_lagrange(values.ctx._h, qap._h, lag_g1._h, values._h, _rho_bytes(zs), k, ys, proof))
     return [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], proof.raw
 
 

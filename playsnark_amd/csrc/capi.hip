@@ -27,6 +27,7 @@
 #include "fr_lincomb.hpp"
 #include "poly_scan_set.hpp"
 #include "poly_lagrange.hpp"
+#include "poly_lagrange_set.hpp"
 #include "lagrange.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"

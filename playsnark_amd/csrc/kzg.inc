@@ -17,8 +17,12 @@
 //   ps_kzg_commit_lagrange       sum_i v_i lag_g1[i]: ps_msm over the Lagrange-form string
 //   ps_kzg_open_lagrange         values and proofs of k points from the values: those rows, then the lone ps_msm (k = 1) or ONE
 //                                ps_msm_batch over lag_g1 -- ps_kzg_open's bytes for the interpolated coefficients
-// The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp), k_poly_scan_set_apply (poly_scan_set.hpp) and the
-// three of poly_lagrange.hpp; everything else is made of existing entry points.
+//   ps_poly_lagrange_set_group   the points of a set that share one inversion per tile, for tests that sit on its edges
+//   ps_poly_div_roots_lagrange   the values on 1..n of (p - r) / Z_S from the values of p: the k linear quotients folded into one row
+//   ps_kzg_open_set_lagrange     values and ONE proof for a set of k points from the values: that row, then ONE lone ps_msm over
+//                                lag_g1 -- ps_kzg_open_set's bytes for the interpolated coefficients
+// The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp), k_poly_scan_set_apply (poly_scan_set.hpp), the
+// three of poly_lagrange.hpp and k_lagr_fold (poly_lagrange_set.hpp); everything else is made of existing entry points.
 
 // {z_j^(2^i)}, i < POLY_SCAN_POWERS, for k canonical points (PS_ERR_ENCODING otherwise)
 static int poly_scan_tables(const char* who, const uint8_t* z_be32, size_t k, std::vector<FrPow2Table>* tabs) {
@@ -707,29 +711,41 @@ static int lagr_args(const std::string& who, const ps_ctx* c, const ps_qap* q, c
 
 // The launches for k points over the n values: y_be32[j] = p(z_j); rows != nullptr: row j of rows (n scalars each) = the values
 // of (p - p(z_j)) / (X - z_j) on the nodes.  Returns with the stream idle.
+// set != nullptr (a set of k < n distinct points, set->w its weights c_j): rows is ONE row of n scalars and gets the values of
+// the set quotient sum_j c_j (p - p(z_j)) / (X - z_j) -- k_lagr_tile<false> and the walk as for the values alone, then k_lagr_fold
+// (poly_lagrange_set.hpp) into ceil(k / G) partial rows and, where there is more than one, their sum by k_fr_lincomb with unit
+// weights.
 static int lagr_run(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_scalars* values, const std::vector<LagrPoint>& pts, u32* rows,
-                    uint8_t* y_be32) {
-    const u64 n = q->n, k = pts.size();
+                    uint8_t* y_be32, const KzgSet* set = nullptr) {
+    const u64 n = q->n, k = pts.size(), groups = set ? poly_lagr_set_groups(k) : 0;
     const u32 tiles = (u32)poly_lagr_tiles(n);
     hipStream_t st = c->stream;
+    std::vector<FrLincombInput> ins(groups);  // (the tables of the sum outlive the scope's wait for the stream)
+    std::vector<FrLincombCoef> ones(groups);
     Scope scope(st);
     LagrPoint* d_pts = nullptr;
-    Fr *parts = nullptr, *yq = nullptr;
-    u32* d_y = nullptr;
+    Fr *parts = nullptr, *yq = nullptr, *d_w = nullptr;
+    u32 *d_y = nullptr, *partial = rows;
+    FrLincombInput* d_in = nullptr;
+    FrLincombCoef* d_coef = nullptr;
     hipError_t e;
     if ((e = scope.device(&d_pts, k)) != hipSuccess || (e = scope.device(&parts, poly_lagr_part_elems(n, k))) != hipSuccess ||
-        (e = scope.device(&yq, poly_lagr_yq_elems(k))) != hipSuccess || (e = scope.device(&d_y, poly_lagr_value_words(k))) != hipSuccess)
+        (e = scope.device(&yq, poly_lagr_yq_elems(k))) != hipSuccess || (e = scope.device(&d_y, poly_lagr_value_words(k))) != hipSuccess ||
+        (set && (e = scope.device(&d_w, poly_lagr_set_weight_elems(k))) != hipSuccess) ||
+        (groups > 1 && ((e = scope.device(&partial, poly_lagr_set_partial_words(n, k))) != hipSuccess || (e = scope.device(&d_in, groups)) != hipSuccess ||
+                        (e = scope.device(&d_coef, groups)) != hipSuccess)))
         return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
     if (storage_wait_ready(values->st, st)) return fail(PS_ERR_HIP, who + ": event wait failed");
-    if ((e = hipMemcpyAsync(d_pts, pts.data(), sizeof(LagrPoint) * k, hipMemcpyHostToDevice, st)) != hipSuccess)
+    if ((e = hipMemcpyAsync(d_pts, pts.data(), sizeof(LagrPoint) * k, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (set && (e = hipMemcpyAsync(d_w, set->w.data(), sizeof(Fr) * k, hipMemcpyHostToDevice, st)) != hipSuccess))
         return fail(PS_ERR_HIP, who + ": copy of the points: " + hipGetErrorString(e));
     const u32* v = scalars_ptr(values);
     const u64 plane = poly_lagr_plane_elems(n, k);
     for (u64 j0 = 0; j0 < k; j0 += POLY_LAGR_MAX_POINTS_PER_LAUNCH) {  // blockIdx.y picks the point
         const u32 kb = (u32)std::min<u64>(k - j0, POLY_LAGR_MAX_POINTS_PER_LAUNCH);
         Fr* part = parts + j0 * tiles;  // the planes stay `plane` apart
-        u32* row = rows ? rows + 8 * j0 * n : nullptr;
-        if (rows)
+        u32* row = rows && !set ? rows + 8 * j0 * n : nullptr;
+        if (row)
             hipLaunchKernelGGL(k_lagr_tile<true>, dim3(tiles, kb), dim3(POLY_LAGR_THREADS), 0, st, v, n, tiles, (const LagrPoint*)(d_pts + j0),
                                (const Fr*)q->qt.invfact, part, plane, row);
         else
@@ -737,9 +753,27 @@ static int lagr_run(ps_ctx* c, const std::string& who, const ps_qap* q, const ps
                                (const Fr*)q->qt.invfact, part, plane, (u32*)nullptr);
         hipLaunchKernelGGL(k_lagr_walk, dim3(kb), dim3(POLY_LAGR_THREADS), 0, st, (const Fr*)part, plane, tiles, (const LagrPoint*)(d_pts + j0), v, n,
                            (const Fr*)q->qt.fact2, d_y + 8 * j0, yq + 2 * j0);
-        if (rows)
+        if (row)
             hipLaunchKernelGGL(k_lagr_apply, dim3((u32)poly_lagr_apply_blocks(n), kb), dim3(POLY_LAGR_THREADS), 0, st, v, n,
                                (const LagrPoint*)(d_pts + j0), (const Fr*)(yq + 2 * j0), row);
+    }
+    if (set) {  // k <= POLY_LAGR_SET_MAX: the loop above ran once
+        hipLaunchKernelGGL(k_lagr_fold, dim3(tiles, (u32)groups), dim3(POLY_LAGR_THREADS), 0, st, v, n, (u32)k, (const LagrPoint*)d_pts, (const Fr*)d_w,
+                           (const Fr*)yq, partial);
+        if (groups > 1) {  // the rows as inputs of one combination with the weights 1
+            const Fr one = fr_canon(fr_one());
+            for (u64 g = 0; g < groups; g++) {
+                ins[g] = FrLincombInput{partial + poly_lagr_set_partial_word(g, 1, n), n};
+                for (int i = 0; i < FR_L; i++) ones[g].l[i] = one.l[i];
+                ones[g].nonzero = 1;
+                ones[g].pad = 0;
+            }
+            if ((e = hipMemcpyAsync(d_in, ins.data(), sizeof(FrLincombInput) * groups, hipMemcpyHostToDevice, st)) != hipSuccess ||
+                (e = hipMemcpyAsync(d_coef, ones.data(), sizeof(FrLincombCoef) * groups, hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(PS_ERR_HIP, who + ": copy of the tables: " + hipGetErrorString(e));
+            hipLaunchKernelGGL(k_fr_lincomb, dim3((u32)fr_lincomb_blocks(n), 1), dim3(FR_LINCOMB_THREADS), 0, st, (const FrLincombInput*)d_in, (u32)groups,
+                               (const FrLincombCoef*)d_coef, 1u, 0u, n, rows);
+        }
     }
     if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, who + ": kernels: " + hipGetErrorString(e));
     std::vector<u32> y(8 * k);
@@ -834,4 +868,80 @@ extern "C" int ps_kzg_open_lagrange(ps_ctx* c, const ps_qap* q, const ps_points*
     // the quotient rows never leave the device: the lone sum for one point (measured ahead of a one-row batch), else ONE batch
     if (k == 1) return scope.finish(ps_msm(c, lag_g1, *rows, proofs));
     return scope.finish(ps_msm_batch(c, lag_g1, *rows, k, proofs));
+}
+
+// ---- a value-form polynomial at a SET of points: the k linear quotients folded into one row of n values, one proof ----
+
+// Arguments shared by ps_poly_div_roots_lagrange and ps_kzg_open_set_lagrange: the set section's and the Lagrange section's
+static int lagr_set_args(const std::string& who, const ps_ctx* c, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k,
+                         const uint8_t* y_be32) {
+    if (!c || !q || !values || !z_be32 || !y_be32) return fail(PS_ERR_ARG, who + ": NULL argument");
+    if (values->n != q->n)
+        return fail(PS_ERR_LENGTH, who + ": " + std::to_string(values->n) + " values on a domain of " + std::to_string(q->n) + " nodes");
+    if (k == 0) return fail(PS_ERR_ARG, who + ": an empty set (division by the constant 1 is a copy and is not offered)");
+    if (!poly_lagr_set_points_ok(k))
+        return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points, at most " + std::to_string(POLY_LAGR_SET_MAX) + " in a set");
+    if (!poly_lagr_set_size_ok(q->n, k))
+        return fail(PS_ERR_ARG, who + ": " + std::to_string(k) + " points x " + std::to_string(q->n) + " values reach 2^32");
+    return PS_OK;
+}
+
+// *qv = the n values of (p - r) / Z_S on the nodes (zero for k >= n: p is its own interpolant) and y_be32[j] = p(z_j).  *qv is
+// the caller's (a Scope result or slot).
+static int lagr_set_quotient(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_scalars* values, const std::vector<LagrPoint>& pts,
+                             const KzgSet& s, uint8_t* y_be32, ps_scalars** qv) {
+    const u64 n = q->n, k = pts.size();
+    if (int rc = scalars_fresh(c, who.c_str(), n, qv)) return rc;
+    u32* row = (u32*)(*qv)->st->p;
+    if (!poly_lagr_set_zero(n, k)) return lagr_run(c, who, q, values, pts, row, y_be32, &s);
+    hipError_t e = hipMemsetAsync(row, 0, 32 * n, c->stream);
+    if (e != hipSuccess) return fail(PS_ERR_HIP, who + ": hipMemsetAsync: " + hipGetErrorString(e));
+    return lagr_run(c, who, q, values, pts, nullptr, y_be32);
+}
+
+extern "C" int ps_poly_lagrange_set_group(void) { return POLY_LAGR_SET_GROUP; }
+
+extern "C" int ps_poly_div_roots_lagrange(ps_ctx* c, const ps_qap* q, const ps_scalars* values, const uint8_t* z_be32, size_t k, ps_scalars** qv,
+                                          uint8_t* y_be32, uint8_t* rem_be32) {
+    const std::string who = "ps_poly_div_roots_lagrange";
+    if (!qv) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *qv = nullptr;
+    int rc = lagr_set_args(who, c, q, values, z_be32, k, y_be32);
+    if (rc) return rc;
+    KzgSet s;
+    std::vector<LagrPoint> pts;
+    if ((rc = kzg_set_prepare(who, z_be32, k, rem_be32 != nullptr, &s)) || (rc = lagr_points(who, z_be32, k, q->n, &pts))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
+    if ((rc = lagr_set_quotient(c, who, q, values, pts, s, y_be32, scope.result(qv)))) return rc;
+    if (rem_be32) {  // the interpolant of the (z_j, y_j): for k >= n it is p itself, zero-extended
+        std::vector<Fr> y(k);
+        for (size_t j = 0; j < k; j++) (void)fr_mont_from_canonical_be32(&y[j], y_be32 + 32 * j);
+        const std::vector<Fr> r = kzg_set_interpolate(s, y);
+        for (size_t i = 0; i < k; i++) fr_mont_to_be32(rem_be32 + 32 * i, r[i]);
+    }
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_kzg_open_set_lagrange(ps_ctx* c, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32, size_t k,
+                                        uint8_t* y_be32, uint8_t* proof) {
+    const std::string who = "ps_kzg_open_set_lagrange";
+    if (!q) return fail(PS_ERR_ARG, who + ": NULL argument");
+    int rc = lagr_string_args(who, c, lag_g1, values, q->n);
+    if (rc) return rc;
+    if ((rc = lagr_set_args(who, c, q, values, z_be32, k, y_be32))) return rc;
+    if (!proof) return fail(PS_ERR_ARG, who + ": NULL argument");
+    KzgSet s;
+    std::vector<LagrPoint> pts;
+    if ((rc = kzg_set_prepare(who, z_be32, k, false, &s)) || (rc = lagr_points(who, z_be32, k, q->n, &pts))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (poly_lagr_set_zero(q->n, k)) {  // p is its own interpolant: the quotient is zero
+        if ((rc = lagr_run(c, who, q, values, pts, nullptr, y_be32))) return rc;
+        write_identity(PS_G1, proof);
+        return PS_OK;
+    }
+    Scope scope(c->stream);
+    ps_scalars** row = scope.scalars();
+    if ((rc = lagr_set_quotient(c, who, q, values, pts, s, y_be32, row))) return rc;
+    return scope.finish(ps_msm(c, lag_g1, *row, proof));  // the lone sum; the row never leaves the device
 }

@@ -243,6 +243,17 @@ class QAP {
         check(ps_poly_div_linear_lagrange(ctx_->get(), h_, values.get(), k ? zs[0].data() : nullptr, k, &h, k ? ys[0].data() : nullptr));
         return LagrangeDivision{Poly(*ctx_, h), std::move(ys)};
     }
+    // the n VALUES on 1..n of (p - r) / prod (X - z), z in zs (all zero for zs.size() >= n), the values p(z), and -- unless
+    // remainder is false -- the zs.size() coefficients of r, as Poly::DivRoots gives them (ps_poly_div_roots_lagrange); at least
+    // one point, all distinct, on the domain or off it
+    Poly::RootsDivision DivRootsLagrange(const Poly& values, const std::vector<Scalar>& zs, bool remainder = true) const {
+        const size_t k = zs.size();
+        ps_scalars* h = nullptr;
+        std::vector<Scalar> ys(k), rem(remainder ? k : 0);
+        check(ps_poly_div_roots_lagrange(ctx_->get(), h_, values.get(), k ? zs[0].data() : nullptr, k, &h, k ? ys[0].data() : nullptr,
+                                         remainder && k ? rem[0].data() : nullptr));
+        return Poly::RootsDivision{Poly(*ctx_, h), std::move(ys), std::move(rem)};
+    }
 
   private:
     Context* ctx_;
@@ -624,6 +635,17 @@ inline KZGLagrangeOpening KZGOpenLagrange(Context& c, const QAP& qap, const Poin
     check(ps_kzg_open_lagrange(c.get(), qap.get(), lag_g1.get(), values.get(), k ? zs[0].data() : nullptr, k, k ? out.ys[0].data() : nullptr,
                                flat.data()));
     for (size_t j = 0; j < k; j++) out.proofs.emplace_back(flat.begin() + 96 * j, flat.begin() + 96 * (j + 1));
+    return out;
+}
+// the values p(z), z in zs, and ONE proof for the whole set from the n values and the Lagrange-form string
+// (ps_kzg_open_set_lagrange): the bytes KZGOpenSet gives for the interpolated coefficients, and KZGVerifySet checks them
+inline KZGSetOpening KZGOpenSetLagrange(Context& c, const QAP& qap, const Points& lag_g1, const Poly& values, const std::vector<Scalar>& zs) {
+    const size_t k = zs.size();
+    KZGSetOpening out;
+    out.ys.resize(k);
+    out.proof.resize(96);
+    check(ps_kzg_open_set_lagrange(c.get(), qap.get(), lag_g1.get(), values.get(), k ? zs[0].data() : nullptr, k, k ? out.ys[0].data() : nullptr,
+                                   out.proof.data()));
     return out;
 }
 // members per pass of BlindEvalBatch / SolCommitsBatch / the batch provers (ps_msm_batch_set_chunk); 0: automatic

@@ -1288,6 +1288,38 @@ func KZGOpenLagrange(q *HipQAP, lagG1 *C.ps_points, values Poly, zs []Element) (
 	return elementsFrom(ys), proofs
 }
 
+// PolyLagrangeSetGroup is the number of points of a set that share one inversion per tile (ps_poly_lagrange_set_group).
+func PolyLagrangeSetGroup() int { return int(C.ps_poly_lagrange_set_group()) }
+
+// DivRootsLagrangeHIP is DivRootsHIP in value form: the nbGates values on the domain of (p - r) / prod (X - z), z in zs (all
+// zero for len(zs) >= nbGates), the values p(z), and the len(zs) coefficients of the remainder r
+// (ps_poly_div_roots_lagrange).  At least one point, all distinct, on the domain or off it.
+func (q *HipQAP) DivRootsLagrangeHIP(values Poly, zs []Element) (Poly, []Element, Poly) {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	var qv *C.ps_scalars
+	ys := make([]byte, 32*len(zs))
+	rem := make([]byte, 32*len(zs))
+	call(func() C.int {
+		return C.ps_poly_div_roots_lagrange(hipCtx, q.h, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), &qv, u8(ys), u8(rem))
+	})
+	defer C.ps_scalars_free(qv)
+	return downloadPoly(qv), elementsFrom(ys), Poly(elementsFrom(rem))
+}
+
+// KZGOpenSetLagrange returns the values p(z), z in zs, and ONE proof for the whole set from the values alone
+// (ps_kzg_open_set_lagrange): the point KZGOpenSet gives for the interpolated coefficients, which KZGVerifySet checks unchanged.
+func KZGOpenSetLagrange(q *HipQAP, lagG1 *C.ps_points, values Poly, zs []Element) ([]Element, Commit) {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	ys := make([]byte, 32*len(zs))
+	raw := make([]byte, g1Wire)
+	call(func() C.int {
+		return C.ps_kzg_open_set_lagrange(hipCtx, q.h, lagG1, h, u8(marshalScalars(Poly(zs))), C.size_t(len(zs)), u8(ys), u8(raw))
+	})
+	return elementsFrom(ys), pointFrom(C.PS_G1, raw, zeroG1)
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
