@@ -65,7 +65,8 @@ typedef struct ps_qap ps_qap;         /* device-resident sparse QAP + per-n tabl
  *      ps_kzg_verify_multi (no struct either).  Then ps_poly_scan_set_group, ps_poly_div_roots, ps_kzg_open_set and
  *      ps_kzg_verify_set (no struct either).  Then ps_poly_lagrange_tile, ps_qap_gate_values, ps_poly_eval_lagrange,
  *      ps_poly_div_linear_lagrange, ps_kzg_commit_lagrange and ps_kzg_open_lagrange (no struct either).  Then
- *      ps_poly_lagrange_set_group, ps_poly_div_roots_lagrange and ps_kzg_open_set_lagrange (no struct either). */
+ *      ps_poly_lagrange_set_group, ps_poly_div_roots_lagrange and ps_kzg_open_set_lagrange (no struct either).  Then
+ *      ps_kzg_all_key_lagrange and ps_kzg_open_all_lagrange (no struct either). */
 #define PS_ABI_VERSION 5
 int ps_abi_version(void);
 const char* ps_last_error(void);
@@ -1014,6 +1015,32 @@ int ps_poly_div_roots_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_scalars* v
  * ps_kzg_open_lagrange.  k >= n: the proof is the identity. */
 int ps_kzg_open_set_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, const ps_scalars* values, const uint8_t* z_be32,
                              size_t k, uint8_t* y_be32 /* k */, uint8_t proof[96]);
+
+/* ---- A value-form polynomial at EVERY node of its domain: the n proofs pi_m, m = 1 .. n, in one call ----
+ * What a table prover or a data-availability sampler precomputes.  With kappa(d) = 1 / d for d != 0 and kappa(0) = 0, the
+ * quotient of node m has the values (v_m - v_i) kappa(m - i) at the nodes i != m and q_m (above) at m itself, hence
+ *     pi_m = v_m K_m - U_m + g_m lag_g1[m-1]
+ *     U_m = sum_i kappa(m - i) (v_i lag_g1[i-1])      K_m = sum_i kappa(m - i) lag_g1[i-1]
+ *     s_m = sum_i kappa(m - i) w_i v_i                c_m = sum_i kappa(m - i) w_i             g_m = (s_m - v_m c_m) / w_m
+ * -- four Toeplitz products with one multiplier, run as cyclic convolutions of size S = 2^p >= 2n - 1: two transforms over
+ * points (the NTT over points of the key conversion) and a batch of two over scalars, about (p + 1) S + 3n scalar
+ * multiplications of points where n calls of ps_kzg_open_lagrange take n sums over n points.  K_m depends
+ * on n and the string alone: ps_kzg_all_key_lagrange computes it once, and a call that is handed it runs one transform pair, not
+ * two.  kappa is antisymmetric: K and U read backwards are the NEGATED sums.
+ * Conventions, those of the value-form section: `values`, lag_g1 and all_key hold exactly n elements (PS_ERR_LENGTH otherwise); a
+ * G2 array or a NULL argument (other than all_key) is PS_ERR_ARG; n > 2^30 is PS_ERR_ARG (the S <= 2^31 points of a transform are
+ * indexed with 32 bits).  n = 1 is no special case for the caller: one identity point.  The points of lag_g1 and all_key must lie
+ * in the subgroup of order r, as ps_points_monomial_to_lagrange requires of its input (the scalar multiplications split with the
+ * endomorphism); identity entries are legal.  The values at the nodes are the input itself: there is no y output.  Each proof is
+ * the group element ps_kzg_open_lagrange gives at z = m, hence the same 96 bytes, and ps_kzg_verify / ps_kzg_verify_batch check
+ * the proofs unchanged.  Device memory of a call: S points of 224 bytes and 3 S + 2 n scalars of 40, beside the n results.  The
+ * calls return with the stream idle.  Added within revision 5 (found by symbol, no existing struct changed). */
+/* *out = K_m, m = 1 .. n: n canonical affine points on the device; depends on n and the string only.  Caller frees *out. */
+int ps_kzg_all_key_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, ps_points** out);
+/* (*proofs)[m-1] = [((p - v_m) / (X - m))(tau)] G1 for every node: n canonical affine points on the device; caller frees.
+ * all_key = what ps_kzg_all_key_lagrange returned for (q, lag_g1), or NULL: computed inside the call and dropped. */
+int ps_kzg_open_all_lagrange(ps_ctx* ctx, const ps_qap* q, const ps_points* lag_g1, const ps_points* all_key, const ps_scalars* values,
+                             ps_points** proofs);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,7 @@ SYMBOLS = [
     "ps_poly_lagrange_tile", "ps_qap_gate_values", "ps_poly_eval_lagrange", "ps_poly_div_linear_lagrange", "ps_kzg_commit_lagrange",
     "ps_kzg_open_lagrange",
     "ps_poly_lagrange_set_group", "ps_poly_div_roots_lagrange", "ps_kzg_open_set_lagrange",
+    "ps_kzg_all_key_lagrange", "ps_kzg_open_all_lagrange",
 ]
 
 
@@ -297,6 +298,9 @@ def _load():
         lib.ps_poly_lagrange_set_group.argtypes = []
         lib.ps_poly_div_roots_lagrange.argtypes = [vp, vp, vp, C.c_char_p, sz, pp, C.c_char_p, C.c_char_p]
         lib.ps_kzg_open_set_lagrange.argtypes = [vp, vp, vp, vp, C.c_char_p, sz, C.c_char_p, C.c_char_p]
+    if hasattr(lib, "ps_kzg_open_all_lagrange"):  # likewise: the proofs of every node of the domain, within revision 5
+        lib.ps_kzg_all_key_lagrange.argtypes = [vp, vp, vp, pp]
+        lib.ps_kzg_open_all_lagrange.argtypes = [vp, vp, vp, vp, vp, pp]
     return lib
 
 

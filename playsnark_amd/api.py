@@ -959,6 +959,24 @@ def KZGOpenSetLagrange(qap: "QAP", lag_g1: Points, values: Poly, zs: Sequence[in
     return [int.from_bytes(ys.raw[32 * j : 32 * j + 32], "big") for j in range(k)], proof.raw
 
 
+def KZGAllKeyLagrange(qap: "QAP", lag_g1: Points) -> Points:
+    """K_m = sum_i lag_g1[i-1] / (m - i), m = 1..n (ps_kzg_all_key_lagrange): the part of the proofs of all nodes that depends on
+    the domain and the string alone.  Computed once and handed to KZGOpenAllLagrange, it halves the work of every call."""
+    h = C.c_void_p()
+    _check(lib.ps_kzg_all_key_lagrange(qap.ctx._h, qap._h, lag_g1._h, C.byref(h)))
+    return Points(qap.ctx, h)
+
+
+def KZGOpenAllLagrange(qap: "QAP", lag_g1: Points, values: Poly, all_key: Optional[Points] = None) -> Points:
+    """The proofs of EVERY node of the domain, proofs[m-1] = [((p - v_m) / (X - m))(tau)] G1, as n points on the device, from
+    the n values on the domain of qap and the Lagrange form of the string (ps_kzg_open_all_lagrange): two transforms over points
+    in place of n sums.  Each is KZGOpenLagrange's proof at z = m, byte for byte; the values at the nodes are the input itself.
+    all_key: what KZGAllKeyLagrange(qap, lag_g1) returned, or None (computed inside the call and dropped)."""
+    h = C.c_void_p()
+    _check(lib.ps_kzg_open_all_lagrange(values.ctx._h, qap._h, lag_g1._h, all_key._h if all_key is not None else None, values._h, C.byref(h)))
+    return Points(values.ctx, h)
+
+
 def KZGVerifySet(ctx: Context, tau_g1: Points, tau_g2: Points, commit: bytes, zs: Sequence[int], ys: Sequence[int], proof: bytes,
                  check_subgroup: bool = True) -> bool:
     """e(C - [r(tau)] G1, G2) * e(-proof, [Z_S(tau)] G2) == 1 for what KZGOpenSet made (ps_kzg_verify_set): tau_g1 holds at least

@@ -29,6 +29,7 @@
 #include "poly_lagrange.hpp"
 #include "poly_lagrange_set.hpp"
 #include "lagrange.hpp"
+#include "kzg_all.hpp"
 #include "ec_spmv.hpp"
 #include "prove_batch.hpp"
 #include "share_ranges.hpp"

@@ -21,8 +21,13 @@
 //   ps_poly_div_roots_lagrange   the values on 1..n of (p - r) / Z_S from the values of p: the k linear quotients folded into one row
 //   ps_kzg_open_set_lagrange     values and ONE proof for a set of k points from the values: that row, then ONE lone ps_msm over
 //                                lag_g1 -- ps_kzg_open_set's bytes for the interpolated coefficients
+//   ps_kzg_all_key_lagrange      K_m = sum_i kappa(m - i) lag_g1[i], m = 1 .. n: the part of the proofs of all nodes that depends on
+//                                the string alone -- one correlation over points (ec_correlate)
+//   ps_kzg_open_all_lagrange     the proofs of ALL n nodes from the values: the scalar side, one correlation over points, one
+//                                combining pass -- ps_kzg_open_lagrange's bytes at z = 1 .. n
 // The kernels are the three of poly_scan.hpp, k_fr_lincomb (fr_lincomb.hpp), k_poly_scan_set_apply (poly_scan_set.hpp), the
-// three of poly_lagrange.hpp and k_lagr_fold (poly_lagrange_set.hpp); everything else is made of existing entry points.
+// three of poly_lagrange.hpp, k_lagr_fold (poly_lagrange_set.hpp) and the five of kzg_all.hpp around the transforms of ntt.hpp
+// and lagrange.hpp; everything else is made of existing entry points.
 
 // {z_j^(2^i)}, i < POLY_SCAN_POWERS, for k canonical points (PS_ERR_ENCODING otherwise)
 static int poly_scan_tables(const char* who, const uint8_t* z_be32, size_t k, std::vector<FrPow2Table>* tabs) {
@@ -944,4 +949,192 @@ extern "C" int ps_kzg_open_set_lagrange(ps_ctx* c, const ps_qap* q, const ps_poi
     ps_scalars** row = scope.scalars();
     if ((rc = lagr_set_quotient(c, who, q, values, pts, s, y_be32, row))) return rc;
     return scope.finish(ps_msm(c, lag_g1, *row, proof));  // the lone sum; the row never leaves the device
+}
+
+// ---- a value-form polynomial at EVERY node of its domain: n proofs from two transforms over points (kzg_all.hpp) ----
+
+// A <- the cyclic correlation of its S = 2^p points with a multiplier given as its stored transform khat (the order
+// ntt_run<false> leaves, the inverse's 2^-p folded in): the NTT over points, the pointwise products, the inverse NTT -- what
+// srs_xi_t and the C^T step of monomial_to_lagrange_t launch, once for the entries below.  marks: two events recorded around
+// the pointwise pass (the stage split of tools/kzg_all_sweep.py), or nullptr.
+template <class F>
+static void ec_correlate(const NttTables& tb, hipStream_t st, Xyzz<F>* A, u32 S, int p, const Fr* khat, hipEvent_t* marks = nullptr) {
+    typedef typename KernelField<F>::type KF;
+    constexpr unsigned LN = FieldTraits<KF>::LANES;
+    ec_ntt<F, false>(tb, st, A, S, p);
+    if (marks) (void)hipEventRecord(marks[0], st);
+    hipLaunchKernelGGL(k_ec_scale<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, A, S, khat, ~0ull);
+    if (marks) (void)hipEventRecord(marks[1], st);
+    ec_ntt<F, true>(tb, st, A, S, p);
+}
+
+// the checks both entries share; values == nullptr: the key entry, which takes none
+static int kzg_all_args(const std::string& who, const ps_qap* q, const ps_points* lag_g1, const ps_points* all_key, const ps_scalars* values) {
+    if (lag_g1->group != PS_G1 || (all_key && all_key->group != PS_G1)) return fail(PS_ERR_ARG, who + ": lag_g1 and all_key are G1 arrays");
+    const size_t n = q->n;
+    if (lag_g1->n != n || (values && values->n != n) || (all_key && all_key->n != n))
+        return fail(PS_ERR_LENGTH, who + ": " + (values ? std::to_string(values->n) + " values, " : std::string()) + std::to_string(lag_g1->n) +
+                                       " points of the Lagrange-form string" + (all_key ? " and " + std::to_string(all_key->n) + " of the key table" : std::string()) +
+                                       " on a domain of " + std::to_string(n) + " nodes");
+    if (!kzg_all_size_ok(n))
+        return fail(PS_ERR_ARG, who + ": " + std::to_string(n) + " nodes, at most 2^30 (the transform of 2^p >= 2n - 1 points is indexed with 32 bits)");
+    return PS_OK;
+}
+
+// one identity point: every answer on a domain of one node (the polynomial is a constant)
+static int kzg_all_identity(ps_ctx* c, const std::string& who, ps_points** out) {
+    int rc = points_alloc(c, PS_G1, 1, out);
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync((*out)->st->p, 0, sizeof(Affine<Fp>), c->stream);
+    if (e != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(PS_ERR_HIP, who + ": hipMemsetAsync: " + hipGetErrorString(e));
+    return PS_OK;
+}
+
+// kh <- the stored transform of the wrapped kappa, unscaled (S = 2^p scalars, p >= 1)
+static hipError_t kzg_all_kappa_hat(const NttTables& tb, hipStream_t st, const ps_qap* q, Fr* kh, int p) {
+    hipLaunchKernelGGL(k_kzg_all_kappa, dim3(nblk(1ull << p)), dim3(256), 0, st, kh, (const Fr*)q->qt.fact2, (const Fr*)q->qt.invfact, (u64)q->n, p);
+    return ntt_run<false>(tb, st, kh, 1ull << p, p);
+}
+
+// *out (the caller's scope owns it) = K_m, m = 1 .. n.  Arguments validated.  Returns with the stream idle.
+static int kzg_all_key_run(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_points* lag_g1, ps_points** out) {
+    typedef Fp F;
+    typedef KernelField<F>::type KF;
+    constexpr unsigned LN = FieldTraits<KF>::LANES;
+    const size_t n = q->n;
+    if (n == 1) return kzg_all_identity(c, who, out);
+    const int p = kzg_all_log(n);
+    const u32 S = (u32)kzg_all_size(n);
+    hipStream_t st = c->stream;
+    NttTables& tb = *ctx_tabs(c);
+    hipError_t e = ntt_tables_ensure(tb, p, st);
+    if (e != hipSuccess) return fail(PS_ERR_HIP, who + ": twiddles: " + hipGetErrorString(e));
+    int rc = points_alloc(c, PS_G1, n, out);
+    if (rc) return rc;
+    Scope scope(st);
+    Xyzz<F>* A = nullptr;  // S points; the chain products of the batch normalisation go behind the first n (kzg_all_normalise_fits)
+    Fr* kh = nullptr;
+    if ((e = scope.device(&A, kzg_all_point_elems(n))) != hipSuccess || (e = scope.device(&kh, kzg_all_kappa_elems(n))) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+    if (storage_wait_ready(lag_g1->st, st)) return fail(PS_ERR_HIP, who + ": event wait failed");
+    if ((e = kzg_all_kappa_hat(tb, st, q, kh, p)) != hipSuccess) return fail(PS_ERR_HIP, who + ": ntt: " + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_fr_scale, dim3(nblk(S)), dim3(256), 0, st, kh, (const Fr*)kh, fr_inv2pow_host(p), (u64)S);
+    hipLaunchKernelGGL(k_ec_from_affine<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, (const Affine<F>*)points_ptr(lag_g1), (u32)n, S, A);
+    ec_correlate<F>(tb, st, A, S, p, kh);
+    batch_to_affine<F>(st, (char*)A, n, (char*)(*out)->st->p, (u32)sizeof(Affine<F>));
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, who + ": kernels: " + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, who + ": run: " + hipGetErrorString(e));
+    return scope.finish(PS_OK);
+}
+
+enum { KZG_ALL_STAGES = 7 };  // the scalar side, load, forward, pointwise, inverse, combine, normalise
+struct KzgAllMarks {
+    hipEvent_t ev[KZG_ALL_STAGES + 1] = {};
+    bool on = false;
+    hipError_t create() {
+        on = true;
+        for (hipEvent_t& x : ev)
+            if (hipError_t e = hipEventCreate(&x)) return e;
+        return hipSuccess;
+    }
+    void mark(int i, hipStream_t st) { if (on) (void)hipEventRecord(ev[i], st); }
+    ~KzgAllMarks() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+};
+
+// *proofs (the caller's scope owns it) = pi_m, m = 1 .. n, over a key table that is there.  Arguments validated.  Returns with the
+// stream idle.  stage_ms != nullptr: KZG_ALL_STAGES times from events between the stages.
+static int kzg_all_open_run(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_points* lag_g1, const ps_points* key, const ps_scalars* values,
+                            ps_points** proofs, float* stage_ms = nullptr) {
+    typedef Fp F;
+    typedef KernelField<F>::type KF;
+    constexpr unsigned LN = FieldTraits<KF>::LANES;
+    const size_t n = q->n;
+    const int p = kzg_all_log(n);
+    const u32 S = (u32)kzg_all_size(n);
+    hipStream_t st = c->stream;
+    NttTables& tb = *ctx_tabs(c);
+    hipError_t e = ntt_tables_ensure(tb, p, st);
+    if (e != hipSuccess) return fail(PS_ERR_HIP, who + ": twiddles: " + hipGetErrorString(e));
+    int rc = points_alloc(c, PS_G1, n, proofs);
+    if (rc) return rc;
+    KzgAllMarks marks;
+    if (stage_ms && (e = marks.create()) != hipSuccess) return fail(PS_ERR_HIP, who + ": hipEventCreate: " + hipGetErrorString(e));
+    Scope scope(st);
+    Xyzz<F>* A = nullptr;  // S points: v_i L_i, then U_m, then pi_m; the chain products of the normalisation go behind the first n
+    Fr *kh = nullptr, *x = nullptr, *vm = nullptr, *g = nullptr;
+    if ((e = scope.device(&A, kzg_all_point_elems(n))) != hipSuccess || (e = scope.device(&kh, kzg_all_kappa_elems(n))) != hipSuccess ||
+        (e = scope.device(&x, kzg_all_scalar_elems(n))) != hipSuccess || (e = scope.device(&vm, kzg_all_value_elems(n))) != hipSuccess ||
+        (e = scope.device(&g, kzg_all_value_elems(n))) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": hipMalloc: " + hipGetErrorString(e));
+    if (storage_wait_ready(lag_g1->st, st) || storage_wait_ready(key->st, st) || storage_wait_ready(values->st, st))
+        return fail(PS_ERR_HIP, who + ": event wait failed");
+    const Affine<F>*lag = (const Affine<F>*)points_ptr(lag_g1), *kp = (const Affine<F>*)points_ptr(key);
+    marks.mark(0, st);
+    // the scalar side: kappa's stored transform, [w.v | w] convolved with it as a batch of two, g; then 2^-p into the stored
+    // transform for the inverse over points, which does not scale
+    if ((e = kzg_all_kappa_hat(tb, st, q, kh, p)) != hipSuccess) return fail(PS_ERR_HIP, who + ": ntt: " + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_kzg_all_weights, dim3(nblk(kzg_all_scalar_elems(n))), dim3(256), 0, st, x, vm, scalars_ptr(values), (const Fr*)q->qt.invfact, (u64)n, p);
+    if ((e = ntt_conv(tb, st, x, kzg_all_scalar_elems(n), p, NttFuse(), NttFuse(), kh, (u64)S - 1)) != hipSuccess)
+        return fail(PS_ERR_HIP, who + ": ntt: " + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_kzg_all_finish, dim3(nblk(n)), dim3(256), 0, st, g, (const Fr*)x, (const Fr*)vm, (const Fr*)q->qt.fact2, (u64)n, p);
+    hipLaunchKernelGGL(k_fr_scale, dim3(nblk(S)), dim3(256), 0, st, kh, (const Fr*)kh, fr_inv2pow_host(p), (u64)S);
+    marks.mark(1, st);
+    // the points: U = the correlation of v_i L_i, combined per node with the key table and the string
+    hipLaunchKernelGGL(k_kzg_all_load<KF>, dim3(nblocks((size_t)S * LN)), dim3(256), 0, st, lag, (const Fr*)vm, (u32)n, S, A);
+    marks.mark(2, st);
+    ec_correlate<F>(tb, st, A, S, p, kh, marks.on ? marks.ev + 3 : nullptr);
+    marks.mark(5, st);
+    hipLaunchKernelGGL(k_kzg_all_combine<KF>, dim3(nblocks(n * LN)), dim3(256), 0, st, A, kp, lag, (const Fr*)vm, (const Fr*)g, (u32)n);
+    marks.mark(6, st);
+    batch_to_affine<F>(st, (char*)A, n, (char*)(*proofs)->st->p, (u32)sizeof(Affine<F>));
+    marks.mark(7, st);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(PS_ERR_HIP, who + ": kernels: " + hipGetErrorString(e));
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(PS_ERR_HIP, who + ": run: " + hipGetErrorString(e));
+    for (int i = 0; stage_ms && i < KZG_ALL_STAGES; i++)
+        if ((e = hipEventElapsedTime(&stage_ms[i], marks.ev[i], marks.ev[i + 1])) != hipSuccess) return fail(PS_ERR_HIP, who + ": events: " + hipGetErrorString(e));
+    return scope.finish(PS_OK);
+}
+
+extern "C" int ps_kzg_all_key_lagrange(ps_ctx* c, const ps_qap* q, const ps_points* lag_g1, ps_points** out) {
+    const std::string who = "ps_kzg_all_key_lagrange";
+    if (!c || !q || !lag_g1 || !out) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *out = nullptr;
+    int rc = kzg_all_args(who, q, lag_g1, nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
+    return scope.finish(kzg_all_key_run(c, who, q, lag_g1, scope.result(out)));
+}
+
+static int kzg_all_open(ps_ctx* c, const std::string& who, const ps_qap* q, const ps_points* lag_g1, const ps_points* all_key, const ps_scalars* values,
+                        ps_points** proofs, float* stage_ms) {
+    if (!c || !q || !lag_g1 || !values || !proofs) return fail(PS_ERR_ARG, who + ": NULL argument");
+    *proofs = nullptr;
+    int rc = kzg_all_args(who, q, lag_g1, all_key, values);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    Scope scope(c->stream);
+    if (q->n == 1) {
+        for (int i = 0; stage_ms && i < KZG_ALL_STAGES; i++) stage_ms[i] = 0.f;
+        return scope.finish(kzg_all_identity(c, who, scope.result(proofs)));
+    }
+    if (!all_key) {  // computed inside the call and dropped
+        ps_points** slot = scope.points();
+        if ((rc = kzg_all_key_run(c, who, q, lag_g1, slot))) return rc;
+        all_key = *slot;
+    }
+    return scope.finish(kzg_all_open_run(c, who, q, lag_g1, all_key, values, scope.result(proofs), stage_ms));
+}
+
+extern "C" int ps_kzg_open_all_lagrange(ps_ctx* c, const ps_qap* q, const ps_points* lag_g1, const ps_points* all_key, const ps_scalars* values,
+                                        ps_points** proofs) {
+    return kzg_all_open(c, "ps_kzg_open_all_lagrange", q, lag_g1, all_key, values, proofs, nullptr);
+}
+
+// Measurement hook (not in the header, like ps_debug_points_scale): ps_kzg_open_all_lagrange with the times of its stages in
+// ms[0 .. 6] -- the scalar side, load, forward, pointwise, inverse, combine, normalise (tools/kzg_all_sweep.py).
+extern "C" int ps_debug_kzg_all_stage_ms(ps_ctx* c, const ps_qap* q, const ps_points* lag_g1, const ps_points* all_key, const ps_scalars* values,
+                                         ps_points** proofs, float* ms) {
+    if (!ms) return fail(PS_ERR_ARG, "ps_debug_kzg_all_stage_ms: NULL argument");
+    return kzg_all_open(c, "ps_debug_kzg_all_stage_ms", q, lag_g1, all_key, values, proofs, ms);
 }

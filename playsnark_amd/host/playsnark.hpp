@@ -223,6 +223,21 @@ class QAP {
         check(ps_qap_gate_values(ctx_->get(), h_, sol.get(), which, &h));
         return Poly(*ctx_, h);
     }
+    // K_m = sum_i lag_g1[i-1] / (m - i), m = 1..n: the part of the proofs of all nodes that depends on this domain and the
+    // string alone (ps_kzg_all_key_lagrange); computed once, it halves the work of every KZGOpenAllLagrange
+    Points KZGAllKeyLagrange(const Points& lag_g1) const {
+        ps_points* h = nullptr;
+        check(ps_kzg_all_key_lagrange(ctx_->get(), h_, lag_g1.get(), &h));
+        return Points(*ctx_, h);
+    }
+    // the proofs of EVERY node of this domain, element m - 1 = [((p - v_m) / (X - m))(tau)] G1, on the device, from the n values and
+    // the Lagrange-form string (ps_kzg_open_all_lagrange): KZGOpenLagrange's bytes at z = m.  all_key: KZGAllKeyLagrange(lag_g1)
+    // or nullptr (computed inside the call and dropped)
+    Points KZGOpenAllLagrange(const Points& lag_g1, const Poly& values, const Points* all_key = nullptr) const {
+        ps_points* h = nullptr;
+        check(ps_kzg_open_all_lagrange(ctx_->get(), h_, lag_g1.get(), all_key ? all_key->get() : nullptr, values.get(), &h));
+        return Points(*ctx_, h);
+    }
     // p(z), z in zs, for the polynomial with the given n values on this domain, with no interpolation (ps_poly_eval_lagrange)
     std::vector<Scalar> EvalLagrange(const Poly& values, const std::vector<Scalar>& zs) const {
         const size_t k = zs.size();

@@ -1320,6 +1320,33 @@ func KZGOpenSetLagrange(q *HipQAP, lagG1 *C.ps_points, values Poly, zs []Element
 	return elementsFrom(ys), pointFrom(C.PS_G1, raw, zeroG1)
 }
 
+// KZGAllKeyLagrange returns K_m = sum_i lagG1[i-1] / (m - i), m = 1..nbGates, on the device (ps_kzg_all_key_lagrange): the part
+// of the proofs of all nodes that depends on the domain and the string alone.  The caller frees it with ps_points_free.
+func KZGAllKeyLagrange(q *HipQAP, lagG1 *C.ps_points) *C.ps_points {
+	var key *C.ps_points
+	call(func() C.int { return C.ps_kzg_all_key_lagrange(hipCtx, q.h, lagG1, &key) })
+	return key
+}
+
+// KZGOpenAllLagrange returns the opening proofs of EVERY node of the domain, element m - 1 for the node m, from the values alone
+// (ps_kzg_open_all_lagrange): the points KZGOpenLagrange gives at z = 1..nbGates, from two transforms over points instead of
+// nbGates sums.  allKey is what KZGAllKeyLagrange returned for (q, lagG1), or nil (computed inside the call and dropped).
+func KZGOpenAllLagrange(q *HipQAP, lagG1, allKey *C.ps_points, values Poly) []Commit {
+	h := uploadPoly(values)
+	defer C.ps_scalars_free(h)
+	var dev *C.ps_points
+	call(func() C.int { return C.ps_kzg_open_all_lagrange(hipCtx, q.h, lagG1, allKey, h, &dev) })
+	defer C.ps_points_free(dev)
+	n := int(C.ps_points_len(dev))
+	raw := make([]byte, g1Wire*maxInt(n, 1))
+	call(func() C.int { return C.ps_points_download(hipCtx, dev, 0, C.size_t(n), u8(raw)) })
+	proofs := make([]Commit, n)
+	for m := range proofs {
+		proofs[m] = pointFrom(C.PS_G1, raw[g1Wire*m:g1Wire*(m+1)], zeroG1)
+	}
+	return proofs
+}
+
 // LagrangeCheckHIP: are the Lagrange-form arrays of the key what ToLagrange() makes of its monomial ones, without making
 // them (ps_points_lagrange_check, once per array)?  False for a key that has no Lagrange form.
 func (hs *HipGroth16) LagrangeCheckHIP() bool {
